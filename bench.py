@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """Headline benchmark: slides/sec of the Snuffy MIL aggregator + sparse-attention HBM GB/s on MI355X.
 
-  python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR]
+  python bench.py --full ...              (every leg below, not only the headline)
   python bench.py --gpus N ...            (no launcher: re-executes itself as N ranks under torch.distributed.run)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-The headline leg is the reference's arithmetic (--precision fp32: fp32 tensors, products as split-bf16 x3 on the matrix cores);
-the bf16 path is timed beside it (value_bf16 / roofline_bf16).  With N > 1 ranks an eval run also times training steps
-(value_train): that is where the path's one collective, the flat-gradient RCCL all-reduce, lives.
+The headline leg is the reference's arithmetic (--precision fp32: fp32 tensors, products as split-bf16 x3 on the matrix cores).
+A plain run times that leg only: set-up, --warmup steps, the untimed pre-roll, EXACTLY --steps timed steps, the result line.
+--full adds everything else: the bf16 path beside it (value_bf16 / roofline_bf16), the other forwards and the training leg
+(value_train: with N > 1 ranks that is where the path's one collective, the flat-gradient RCCL all-reduce, lives), the kernel
+rooflines, the ViT and small-bag legs and the CPU baseline.  --dump-outputs DIR writes what the headline leg computed in its last
+timed step as DIR/<name>.npy (float32).  The timed region starts from the state the warm-up steps left (the pre-roll is undone:
+sampler offset; in training weights, AdamW state, dropout generator), so the same arguments give the same outputs on every run.
 
 A step = one bag (slide) through MILNet (critic -> top-Lambda -> sparse attention -> FFN -> head) per rank, bags already
 resident in HBM.  Workload = BASELINE.json's metric shape (config B): N=32768 patches, D=768, h=6, Lambda=200.
@@ -89,6 +94,62 @@ def timed(fn, iters, warmup=2):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / iters
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6     # --dump-outputs: array payload in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(outputs, path):
+    """--dump-outputs: every tensor of `outputs` (name -> tensor) as path/<name>.npy, float32 (float64 stays float64).  Should the
+    arrays exceed DUMP_BUDGET_BYTES in all, each is cut to the same share of its elements at positions drawn with a fixed seed
+    (sorted flat indices: the same positions on every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        arrs[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BUDGET_BYTES:
+        share = DUMP_BUDGET_BYTES / total
+        for name, a in arrs.items():
+            n = max(1, int(a.size * share))
+            if n < a.size:
+                idx = np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))
+                arrs[name] = a.reshape(-1)[idx]
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrs)
+
+
+def snapshot_train_state(net, optimizer, device):
+    """Weights, optimizer state and RNG states of a training leg (the attention dropout draws its masks from torch's CPU
+    generator), so that its timed region can start from a fixed state."""
+    return ([p.detach().clone() for p in net.parameters()],
+            {p: {k: v.clone() if torch.is_tensor(v) else v for k, v in s.items()} for p, s in optimizer.state.items()},
+            torch.get_rng_state(), torch.cuda.get_rng_state(device))
+
+
+def restore_train_state(net, optimizer, device, snap):
+    """Writes a snapshot_train_state() record back in place (same tensors, so fused AdamW keeps its buffers) and marks every
+    cache derived from the weights stale, as an optimizer step does."""
+    from snuffy_amd import functional as SF
+    params, opt_state, cpu_rng, dev_rng = snap
+    with torch.no_grad():
+        for p, v in zip(net.parameters(), params):
+            p.copy_(v)
+    for p in [q for q in optimizer.state if q not in opt_state]:
+        del optimizer.state[p]
+    for p, s in opt_state.items():
+        cur = optimizer.state[p]
+        for k, v in s.items():
+            if torch.is_tensor(v) and torch.is_tensor(cur.get(k)) and cur[k].shape == v.shape:
+                cur[k].copy_(v)
+            else:
+                cur[k] = v.clone() if torch.is_tensor(v) else v
+    SF.bump_param_epoch()
+    torch.set_rng_state(cpu_rng)
+    torch.cuda.set_rng_state(dev_rng, device)
 
 
 def kernel_rooflines(wl, precision, device, wl_name="cfgB"):
@@ -323,8 +384,9 @@ def vit_leg(device, precision, steps, warmup, world=1, dist=None):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     for _ in range(steps):
-        model(x)
+        out = model(x)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -345,7 +407,8 @@ def vit_leg(device, precision, steps, warmup, world=1, dist=None):
                               frac=round(flops_img * rate / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4), traffic=None,
                               issued_bf16_tflops=round(issued * flops_img * rate / 1e12, 1),
                               note="model FLOPs (9.2 GFLOP / image) over the dense bf16 MFMA peak; fp32 issues three bf16 "
-                                   "products per product"))
+                                   "products per product"),
+                last_output=out)
 
 
 def cpu_baseline(wl, budget_s=25.0):
@@ -405,7 +468,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--workload", default="cfgB", choices=sorted(WORKLOADS) + ["vit"],
                     help="cfgB (default, BASELINE.json's metric shape) / cfgA / cfgC / cam16: the MIL aggregator; vit: the patch-embedding "
-                         "extractor of configs[3] as the headline (the default run reports it beside the aggregator as vit_*)")
+                         "extractor of configs[3] as the headline (a --full run reports it beside the aggregator as vit_*)")
     # the headline arithmetic is the reference's: fp32 tensors (products on the matrix cores as split-bf16 x3, fp32-class);
     # the bf16 path (north_star's 1e-2 class) rides beside it as value_bf16 / roofline_bf16
     ap.add_argument("--precision", default="fp32", choices=["bf16", "fp32"])
@@ -420,15 +483,27 @@ def main():
                          "replay removes ~0.24 ms of host-side issue per bag: +50 %% and more for bags of <= 8k patches, "
                          "within 1 %% for config B on a fast host, +15 %% on a slow one")
     ap.add_argument("--headline-only", action="store_true",
-                    help="time only --precision (default: the other precision and the A-materialising forward are timed as "
-                         "well and reported as value_f32 / value_bf16 / value_with_attention_output)")
+                    help="with --full: time only --precision (otherwise --full times the other precision and the A-materialising "
+                         "forward as well and reports them as value_f32 / value_bf16 / value_with_attention_output)")
     ap.add_argument("--gemm-table", action="store_true",
                     help="apply snuffy_amd/tuning/gemm_gfx950.csv (library-GEMM selections; helps the training shapes, "
                          "nothing measurable for the eval forward)")
     ap.add_argument("--train-steps", type=int, default=None,
-                    help="timed steps of the training leg that an N > 1 eval run adds (value_train: fwd + bwd + AdamW + the "
+                    help="timed steps of the training leg that a --full eval run adds (value_train: fwd + bwd + AdamW + the "
                          "flat-gradient RCCL all-reduce); default min(100, max(5, steps // 20))")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (the other precision, the A-materialising forward, fp32 library "
+                         "GEMMs, the reference sampler, the training leg, the kernel rooflines, the ViT and small-bag legs, the CPU "
+                         "baseline; --headline-only / --no-roofline / --no-cpu-baseline still drop theirs).  Default: the headline "
+                         "leg alone")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline leg computed in its last step as DIR/<name>.npy (float32; "
+                         "training: the loss and the parameters after the step; a seeded sample should it exceed 60 MB)")
     args = ap.parse_args()
+    # a plain run does only what the headline needs; the other legs are --full's
+    extra_legs = args.full and not args.headline_only
+    rooflines = args.full and not args.no_roofline
+    cpu_base = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: run the same command line as N ranks of ONE node (one process per
@@ -464,16 +539,18 @@ def main():
         use_pretuned_gemms()
 
     if args.workload == "vit":
-        steps = min(args.steps, 50)
-        leg = vit_leg(device, args.precision, steps, min(args.warmup, 5), world, dist)
+        steps = args.steps
+        leg = vit_leg(device, args.precision, steps, args.warmup, world, dist)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs({"features": leg["last_output"]}, args.dump_outputs)
             other = "fp32" if args.precision == "bf16" else "bf16"
             line = {"metric": "images/sec", "value": leg["value"], "unit": "img/s", "n_gpus": world, "steps": steps,
-                    "warmup": min(args.warmup, 5), "ms_per_step": leg["ms_per_batch"], "higher_is_better": True, "scaling": "weak",
+                    "warmup": args.warmup, "ms_per_step": leg["ms_per_batch"], "higher_is_better": True, "scaling": "weak",
                     "vs_baseline": None, "dtype": {"bf16": "bf16", "fp32": "f32"}[args.precision], "data": "synthetic",
                     "config": {"workload": leg["workload"], "parallelism": "tile batches x%d (independent, no collective)" % world},
                     "roofline": leg["roofline"]}
-            if not args.headline_only and world == 1:
+            if extra_legs and world == 1:
                 o = vit_leg(device, other, max(3, steps // 3), 2)
                 line["value_" + {"bf16": "bf16", "fp32": "f32"}[other]] = o["value"]
                 line["roofline_" + {"bf16": "bf16", "fp32": "f32"}[other]] = o["roofline"]
@@ -513,9 +590,11 @@ def main():
         bags = [torch.randn(1, N, D, generator=g).to(device) for _ in range(nbags)]
     labels = [torch.tensor([float(i % 2)], device=device) for i in range(nbags)]
 
-    def measure(precision, return_attention=False, steps=None, warmup=None, use_graph=None, mode=None, sampler="device"):
+    def measure(precision, return_attention=False, steps=None, warmup=None, use_graph=None, mode=None, sampler="device",
+                outputs=None):
         """Times `steps` steps of one configuration (barrier + synchronize on both sides, max over ranks).
-        Returns (elapsed seconds, per-rank seconds, launch mode)."""
+        Returns (elapsed seconds, per-rank seconds, launch mode).  outputs (a dict): filled after the timed region with what the
+        last timed step computed (eval: classes, prediction_bag[, attention]; train: the loss and the parameters after the step)."""
         steps = args.steps if steps is None else steps
         warmup = args.warmup if warmup is None else warmup
         use_graph = args.graph if use_graph is None else use_graph
@@ -530,7 +609,7 @@ def main():
             stepper = BagParallelStepper(net, world_size=world, dist=dist, device=device, precision=precision)
 
             def step(i):
-                stepper.step(bags[i % nbags], labels[i % nbags])
+                return stepper.step(bags[i % nbags], labels[i % nbags])
         else:
             net.eval()
             if use_graph:
@@ -554,11 +633,14 @@ def main():
 
             def step(i):
                 with torch.no_grad():
-                    net(bags[i % nbags])
+                    return net(bags[i % nbags])
 
         for i in range(warmup):
             step(i)
         torch.cuda.synchronize()
+        smp = net.b_classifier.cfg._device_sampler
+        smp_state = smp.state.clone() if smp is not None else None
+        train_snap = snapshot_train_state(net, stepper.optimizer, device) if mode == "train" else None
         # untimed pre-roll by TIME on top of the W warm-up steps: a short timed region (the driver times 20 steps = 26 ms) would
         # otherwise sit on the clock ramp of a GPU that was idle a moment ago (round 3: 758 slides/s over 20 steps against
         # 777-818 over 2000).  Same steps, same bags, not timed; the timed region below is still EXACTLY `steps` steps.
@@ -569,12 +651,21 @@ def main():
                 step(warmup + j)
                 j += 1
             torch.cuda.synchronize()
+        # the timed region starts from the state the W warm-up steps left, however many steps the pre-roll ran: the random share's
+        # draws at the same offset and, in training, the same weights, AdamW state and dropout stream
+        smp = net.b_classifier.cfg._device_sampler
+        if smp is not None:
+            smp.state.copy_(smp_state if smp_state is not None else torch.tensor([smp.seed, smp.offset0], dtype=torch.int64))
+        if train_snap is not None:
+            restore_train_state(net, stepper.optimizer, device, train_snap)
+            del train_snap
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        last = None
         for i in range(steps):
-            step(warmup + i)
+            last = step(warmup + i)
         torch.cuda.synchronize()
         mine_s = time.perf_counter() - t0
         if dist is not None:
@@ -589,12 +680,23 @@ def main():
             allr = [torch.zeros(1, device=device, dtype=torch.float64) for _ in range(world)]
             dist.all_gather(allr, torch.tensor([mine_s], device=device, dtype=torch.float64))
             per_rank = [float(v.item()) for v in allr]
+        if outputs is not None:
+            if mode == "train":
+                outputs["loss"] = last
+                outputs.update(("param." + k, p) for k, p in net.named_parameters())
+            else:
+                outputs.update((k, v) for k, v in zip(("classes", "prediction_bag", "attention"), last) if v is not None)
         del net
         return elapsed, per_rank, launch
 
-    elapsed, per_rank, launch = measure(args.precision)            # the headline leg: EXACTLY args.steps timed steps
+    last_outputs = {} if args.dump_outputs else None
+    # the headline leg: EXACTLY args.steps timed steps
+    elapsed, per_rank, launch = measure(args.precision, outputs=last_outputs)
+    if last_outputs is not None and rank == 0:
+        dump_outputs(last_outputs, args.dump_outputs)
+    del last_outputs
     extra = {}
-    if not args.headline_only:
+    if extra_legs:
         # the reference's own arithmetic (fp32) next to the bf16 headline (or the other way round), same bags, same loop
         other = "fp32" if args.precision == "bf16" else "bf16"
         steps_o = args.steps if args.mode == "eval" else max(3, args.steps // 3)
@@ -616,13 +718,13 @@ def main():
             finally:
                 SF.FP32_GEMM = keep
             extra["f32_library_gemm"] = dict(elapsed=e4, steps=steps_l, launch=l4)
-    if r_share > 0 and args.mode == "eval" and not args.headline_only:
+    if r_share > 0 and args.mode == "eval" and extra_legs:
         # the same forward with the random share drawn by the reference's np.random.choice on the host (bit-exact parity mode)
         steps_r = max(5, args.steps // 4)
         e6, _, l6 = measure(args.precision, steps=steps_r, warmup=min(args.warmup, 10), sampler="reference")
         extra["reference_sampler"] = dict(elapsed=e6, steps=steps_r, launch=l6)
     train_leg = None
-    if args.mode == "eval" and (dist is not None or not args.headline_only):   # at N = 1 too: one short leg, so that the
+    if args.mode == "eval" and args.full and (dist is not None or not args.headline_only):   # at N = 1 too: one short leg, so that the
         # driver's single-GPU record also carries a training number (no collective at world 1: the stepper is the trainer)
         # the eval forward has no collective in its data path (bags are independent): an N-rank eval line says nothing about
         # the one exchange the north star names, the flat-gradient all-reduce.  The same ranks therefore also time training
@@ -679,20 +781,20 @@ def main():
             "f32": "fp32 tensors; products as split-bf16 x3 on the MFMA units (2^-17 per product, fp32 accumulate), "
                    "logits within 1e-5 of plain fp32 (north_star's 1e-3 class); value_f32_library_gemm = the same forward "
                    "with fp32 library GEMMs"}
-        if not args.no_roofline:   # rank 0 only, after the timed region (the other ranks wait at the closing barrier)
+        if rooflines:   # rank 0 only, after the timed region (the other ranks wait at the closing barrier)
             line.update(kernel_rooflines(wl, args.precision, device, args.workload))
             if not args.headline_only:
                 other = "fp32" if args.precision == "bf16" else "bf16"
                 for k, v in kernel_rooflines(wl, other, device, args.workload).items():
                     line[k + "_" + dt_name[other]] = v
-        if world == 1 and not args.headline_only and args.workload == "cfgB":
+        if world == 1 and extra_legs and args.workload == "cfgB":
             # BASELINE.json configs[3] beside the aggregator: the ViT-S/16 + adapter extractor, both arithmetics
             for prec, st in (("bf16", 8), ("fp32", 3)):
                 leg = vit_leg(device, prec, st, 2)
                 line["vit_" + dt_name[prec]] = {k: leg[k] for k in ("value", "unit", "ms_per_batch", "steps", "batch", "workload", "roofline")}
-        if world == 1 and not args.headline_only and args.workload == "cfgB":
+        if world == 1 and extra_legs and args.workload == "cfgB":
             line["small_bags"] = small_bag_leg(device, args.precision)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_base:
             line["cpu_baseline"] = cpu_baseline(wl)
         print(json.dumps(line), flush=True)
     if dist is not None:

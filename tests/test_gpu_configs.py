@@ -222,7 +222,7 @@ def test_bench_rccl_path_on_one_rank(mode):
     env = dict(os.environ, SNF_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29541" if mode == "eval" else "29542", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "cfgA",
-           "--steps", "6", "--warmup", "2", "--headline-only", "--no-cpu-baseline", "--no-roofline", "--mode", mode,
+           "--steps", "6", "--warmup", "2", "--full", "--headline-only", "--no-cpu-baseline", "--no-roofline", "--mode", mode,
            "--precision", "bf16"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -2,7 +2,7 @@
 # micro-benchmarks.  Everything lands under gpurun_out/r06/; copy what is to be judged into profiles/.   bash tools/run_profiles.sh
 R=r06; O=gpurun_out/$R; mkdir -p $O
 T="timeout 600"
-$T python bench.py > $O/bench_cfgB.json 2> $O/bench_cfgB.err
+$T python bench.py --full > $O/bench_cfgB.json 2> $O/bench_cfgB.err
 $T bash tools/prof_bench.sh ${R}_f32 --precision fp32 --steps 200 > $O/prof_f32.txt 2>&1
 $T bash tools/prof_bench.sh ${R}_bf16 --precision bf16 --steps 200 > $O/prof_bf16.txt 2>&1
 $T bash tools/prof_bench.sh ${R}_train_bf16 --mode train --precision bf16 --steps 20 --warmup 5 > $O/prof_train_bf16.txt 2>&1
@@ -15,13 +15,13 @@ $T bash tools/pmc_traffic_x3p.sh cfgC $O/traffic_x3p_cfgC > $O/traffic_x3p_cfgC.
 $T bash tools/pmc_traffic_x3p.sh cfgA $O/traffic_x3p_cfgA > $O/traffic_x3p_cfgA.txt 2>&1
 $T bash tools/pmc_x3p.sh $O/pmc_x3p > $O/attn_x3p_pmc_sq.txt 2>&1
 WHAT=attnB $T bash tools/pmc_attn.sh $O/pmc_bf16 > /dev/null 2>&1; python tools/pmc_summary.py $O/pmc_bf16 sparse_attn_mfma > $O/attn_mfma_pmc_sq.txt 2>&1
-$T python bench.py --mode train --precision bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $O/bench_cfgB_train_bf16.json 2>/dev/null
-$T python bench.py --mode train --precision fp32 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $O/bench_cfgB_train_f32.json 2>/dev/null
-$T python bench.py --workload cfgA --no-cpu-baseline --steps 200 > $O/bench_cfgA.json 2>/dev/null
-$T python bench.py --workload cfgC --no-cpu-baseline --steps 50 > $O/bench_cfgC.json 2>/dev/null
-$T python bench.py --workload cam16 --no-cpu-baseline --headline-only --steps 100 > $O/bench_cam16.json 2>/dev/null
-$T python bench.py --workload vit --steps 10 > $O/bench_vit.json 2>/dev/null
-for w in readme_dino_scratch readme_dino_adapter readme_mae_adapter; do $T python bench.py --workload $w --steps 200 --warmup 20 > $O/bench_$w.json 2>/dev/null; done
+$T python bench.py --full --mode train --precision bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $O/bench_cfgB_train_bf16.json 2>/dev/null
+$T python bench.py --full --mode train --precision fp32 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $O/bench_cfgB_train_f32.json 2>/dev/null
+$T python bench.py --full --workload cfgA --no-cpu-baseline --steps 200 > $O/bench_cfgA.json 2>/dev/null
+$T python bench.py --full --workload cfgC --no-cpu-baseline --steps 50 > $O/bench_cfgC.json 2>/dev/null
+$T python bench.py --full --workload cam16 --no-cpu-baseline --headline-only --steps 100 > $O/bench_cam16.json 2>/dev/null
+$T python bench.py --full --workload vit --steps 10 > $O/bench_vit.json 2>/dev/null
+for w in readme_dino_scratch readme_dino_adapter readme_mae_adapter; do $T python bench.py --full --workload $w --steps 200 --warmup 20 > $O/bench_$w.json 2>/dev/null; done
 $T bash tools/prof_bench.sh ${R}_cfgA_f32 --workload cfgA --precision fp32 --steps 300 > $O/prof_cfgA_f32.txt 2>&1
 $T bash tools/prof_bench.sh ${R}_cfgC_f32 --workload cfgC --precision fp32 --steps 50 > $O/prof_cfgC_f32.txt 2>&1
 $T bash tools/prof_bench.sh ${R}_readme_mae_f32 --workload readme_mae_adapter --precision fp32 --steps 100 > $O/prof_readme_mae_f32.txt 2>&1

@@ -7,11 +7,11 @@ $T bash tools/prof_bench.sh ${R}_readme_mae_f32 --workload readme_mae_adapter --
 $T bash tools/prof_bench.sh ${R}_readme_scratch_f32 --workload readme_dino_scratch --precision fp32 --steps 100 > $O/prof_readme_scratch_f32.txt 2>&1
 $T bash tools/prof_bench.sh ${R}_train_bf16 --mode train --precision bf16 --steps 20 --warmup 5 > $O/prof_train_bf16.txt 2>&1
 $T bash tools/prof_bench.sh ${R}_train_f32 --mode train --precision fp32 --steps 20 --warmup 5 > $O/prof_train_f32.txt 2>&1
-$T python bench.py --workload cfgA --no-cpu-baseline --steps 200 > $O/bench_cfgA.json 2>/dev/null
-$T python bench.py --workload vit --steps 10 > $O/bench_vit.json 2>/dev/null
-$T python bench.py --mode train --precision bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $O/bench_cfgB_train_bf16.json 2>/dev/null
-$T python bench.py --mode train --precision fp32 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $O/bench_cfgB_train_f32.json 2>/dev/null
-for w in readme_dino_scratch readme_dino_adapter readme_mae_adapter; do $T python bench.py --workload $w --steps 200 --warmup 20 > $O/bench_$w.json 2>/dev/null; done
+$T python bench.py --full --workload cfgA --no-cpu-baseline --steps 200 > $O/bench_cfgA.json 2>/dev/null
+$T python bench.py --full --workload vit --steps 10 > $O/bench_vit.json 2>/dev/null
+$T python bench.py --full --mode train --precision bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $O/bench_cfgB_train_bf16.json 2>/dev/null
+$T python bench.py --full --mode train --precision fp32 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $O/bench_cfgB_train_f32.json 2>/dev/null
+for w in readme_dino_scratch readme_dino_adapter readme_mae_adapter; do $T python bench.py --full --workload $w --steps 200 --warmup 20 > $O/bench_$w.json 2>/dev/null; done
 $T python tools/gemm_bench.py cfgB cfgA vit > $O/gemm_bench.txt 2>&1
 $T python tools/gemm_x3_bench.py cfgB cfgA vit > $O/gemm_x3_bench.txt 2>&1
 for n in cfgA_f32 vit_f32 vit_bf16 readme_mae_f32 readme_scratch_f32 train_bf16 train_f32; do cp gpurun_out/prof_${R}_$n/p_kernel_stats.csv $O/${n}_kernel_stats.csv 2>/dev/null; done
