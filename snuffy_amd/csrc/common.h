@@ -12,6 +12,10 @@ void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 int cu_count();
 unsigned long long device_bit();
+// Raises `kernel`'s dynamic-LDS limit to `bytes` once per device (hipFuncSetAttribute is per device).  *mask is the calling site's
+// own `static thread_local unsigned long long mask = 0;`, one device_bit() per device that has the opt-in.  SNF_OK, or SNF_ELAUNCH
+// with the error "<who>: cannot reserve <bytes> bytes of LDS".
+int lds_opt_in(const void* kernel, size_t bytes, unsigned long long* mask, const char* who);
 // gemm.hip: x [r, k] w [c, k]^T + bias written as the Kp fragment image of sparse_attn_x3p.hip (see SkinnyFrag there)
 // idx (nullable): input row i is row idx[i] of x [n_rows, ldx]; xs (nullable) receives the gathered rows, map (nullable) the row -> slot map
 int skinny_linear_x3_kpfrag(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, int r, int c, int k, int dk,

@@ -46,6 +46,18 @@ unsigned long long device_bit() {
     return dev >= 63 ? 0ull : 1ull << dev;     // 0 = never remembered: always set
 }
 
+int lds_opt_in(const void* kernel, size_t bytes, unsigned long long* mask, const char* who) {
+    const unsigned long long bit = device_bit();
+    if (*mask & bit) return SNF_OK;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+        set_error("%s: cannot reserve %zu bytes of LDS", who, bytes);
+        (void)hipGetLastError();
+        return SNF_ELAUNCH;
+    }
+    *mask |= bit;
+    return SNF_OK;
+}
+
 }  // namespace snf
 
 extern "C" {

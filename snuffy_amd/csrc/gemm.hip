@@ -27,19 +27,9 @@
 //     after its last read was issued (two barrier pairs in between, the reads are consumed by MFMAs one pair earlier).
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
 
 struct GemmParams {
     const unsigned short* a;   // [M, lda] bf16
@@ -115,11 +105,6 @@ __device__ __forceinline__ float activate(float v) {
         return sc * (v > 0.f ? v : al * (__builtin_amdgcn_exp2f(v * 1.44269504088896340736f) - 1.0f));
     }
     return v;
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
 }
 
 // NI = 16-column W fragments per wave: 4 -> BN = 256, 2 -> BN = 128.  OUT: 0 = bf16 output, 1 = fp32, 2 = the bf16 image
@@ -975,18 +960,9 @@ __global__ __launch_bounds__(512, 2) void gemm_hl_kernel(GemmParams P) {
 template <int ACT, int OUT>
 int launch_hl(const GemmParams& P, hipStream_t s) {
     constexpr int lds = 2 * 2 * BM * 128 + (((OUT == 1 || OUT == 3) && ACT != SNF_ACT_GELU && ACT != SNF_ACT_SELU) ? 8 * 4096 : 0);
-    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    const unsigned long long attr_set_bit = snf::device_bit();
-    const bool attr_set = (attr_set_mask & attr_set_bit) != 0;
     auto kern = gemm_hl_kernel<ACT, OUT>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            snf::set_error("gemm_hl: cannot reserve %d bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        attr_set_mask |= attr_set_bit;
-    }
+    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "gemm_hl")) return rc;
     const int ntiles = P.tiles_m * P.tiles_n;
     int grid = snf::cu_count() & ~7;
     if (grid < 8) grid = 8;
@@ -1000,35 +976,18 @@ int launch_hl(const GemmParams& P, hipStream_t s) {
     int rc = snf::check_launch("gemm_hl_kernel");
     if (rc || P.split_cap < 2) return rc;
     // the last, partly filled round: every remainder tile on 2 .. 4 workgroups, a K range each (same grid: same tile -> XCD map)
-    static thread_local unsigned long long attr_set2_mask = 0;   // devices (bit = device id) that have the opt-in
-    const unsigned long long attr_set2_bit = snf::device_bit();
-    const bool attr_set2 = (attr_set2_mask & attr_set2_bit) != 0;
     auto kern2 = gemm_hl_kernel<ACT, OUT, true>;
-    if (!attr_set2) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern2), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            snf::set_error("gemm_hl: cannot reserve %d bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        attr_set2_mask |= attr_set2_bit;
-    }
+    static thread_local unsigned long long attr_set2_mask = 0;   // devices (bit = device id) that have the opt-in
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern2), lds, &attr_set2_mask, "gemm_hl")) return rc;
     hipLaunchKernelGGL(kern2, dim3(grid), dim3(512), lds, s, P);
     return snf::check_launch("gemm_hl_kernel<split>");
 }
 
 int launch_hl_gated(const GemmParams& P, hipStream_t s) {
     constexpr int lds = 2 * 2 * BM * 128 + 8 * 4096;
-    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    const unsigned long long bit = snf::device_bit();
     auto kern = gemm_hl_kernel<SNF_ACT_NONE, 3, false, true>;
-    if (!(attr_set_mask & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            snf::set_error("gemm_hl: cannot reserve %d bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        attr_set_mask |= bit;
-    }
+    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "gemm_hl")) return rc;
     const int ntiles = P.tiles_m * P.tiles_n;
     int grid = snf::cu_count() & ~7;
     if (grid < 8) grid = 8;
@@ -1053,19 +1012,9 @@ template <int NI, int ACT, int OUT, int EPI = 0, int MI = 8>
 int launch(const GemmParams& P, hipStream_t s) {
     constexpr int lds = NBUF * (A_BYTES + (MI == 8 ? 64 : 32) * NI * ROWB) +
                         ((EPI == 2 || (OUT == 0 && NI == 4 && ACT != SNF_ACT_GELU && ACT != SNF_ACT_SELU)) ? 8 * 4096 : 0);
-    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    const unsigned long long attr_set_bit = snf::device_bit();
-    const bool attr_set = (attr_set_mask & attr_set_bit) != 0;
     auto kern = gemm_bf16_kernel<NI, ACT, OUT, EPI, MI>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-            hipSuccess) {
-            snf::set_error("gemm_bf16: cannot reserve %d bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        attr_set_mask |= attr_set_bit;
-    }
+    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "gemm_bf16")) return rc;
     const int ntiles = P.tiles_m * P.tiles_n;
     int grid = snf::cu_count() & ~7;          // one persistent workgroup per CU, a multiple of the 8 XCDs
     if (grid < 8) grid = 8;
@@ -1106,16 +1055,6 @@ int launch_act(const GemmParams& P, hipStream_t s) {
 // v_mfma_f32_32x32x16_bf16; the partial blocks are summed through LDS in a fixed order.  Rows / columns past R / C are clamped
 // on load and masked on store.  k % 16 == 0, rows 16-byte aligned.
 // ---------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(16))) float f32x16s;
-typedef __attribute__((ext_vector_type(8))) float f32x8s;
-__device__ __forceinline__ void skinny_split8(const f32x8s v, bf16x8& hi, bf16x8& lo) {
-    hi = __builtin_convertvector(v, bf16x8);
-    lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x8s), bf16x8);
-}
-__device__ __forceinline__ f32x8s skinny_load8(const float* p) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-    return f32x8s{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 // FRAG: the result leaves as the MFMA A-fragment image the pipelined attention kernel keeps in registers (sparse_attn_x3p.hip,
 // x3p_prep_kp_kernel: [chunk][head][key block][dk / 16][hi | lo][64 lanes] x 16 bytes, value * fr.c_exp split into bf16 hi + lo,
 // padded keys zero) instead of as a [r, c] matrix: the key projection then needs no fp32 Kp tensor and no prep launch.
@@ -1181,7 +1120,7 @@ __global__ __launch_bounds__(512) void skinny_linear_x3_kernel(const float* __re
     const int s_lo = wv * per, s_hi = s_lo + per < steps ? s_lo + per : steps;
     const float* xp = x + (int64_t)xr * ldx + 8 * hf;
     const float* wp = w + (int64_t)wr * ldw + 8 * hf;
-    f32x16s acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     // A = w fragment (output column on the lane), B = x fragment (row on the lane): C[col, row] -- lane (row j, half hf) then holds
@@ -1189,12 +1128,12 @@ __global__ __launch_bounds__(512) void skinny_linear_x3_kernel(const float* __re
     for (int s0 = s_lo; s0 < s_hi; s0 += BATCH) {
         // branch-free on purpose: a predicate around the loads makes the compiler wait for each pair before it requests the next
         // (six serial round trips: 12 us for 200 x 768 x 768).  Steps past the wave's share re-read its last step and contribute 0.
-        f32x8s xv[BATCH], wvv[BATCH];
+        f32x8 xv[BATCH], wvv[BATCH];
 #pragma unroll
         for (int u = 0; u < BATCH; ++u) {
             const int st = s0 + u < s_hi ? s0 + u : s_hi - 1;
-            xv[u] = skinny_load8(xp + 16 * st);
-            wvv[u] = skinny_load8(wp + 16 * st);
+            xv[u] = load8(xp + 16 * st);
+            wvv[u] = load8(wp + 16 * st);
         }
         __builtin_amdgcn_sched_barrier(0);   // every load of the batch is requested before the first split / MFMA
         if constexpr (FRAG) {
@@ -1212,8 +1151,8 @@ __global__ __launch_bounds__(512) void skinny_linear_x3_kernel(const float* __re
         for (int u = 0; u < BATCH; ++u) {
             bf16x8 xh, xl, wh, wl;
             const float live = s0 + u < s_hi ? 1.f : 0.f;
-            skinny_split8(xv[u] * live, xh, xl);
-            skinny_split8(wvv[u], wh, wl);
+            split8(xv[u] * live, xh, xl);
+            split8(wvv[u], wh, wl);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc, 0, 0, 0);
@@ -1255,11 +1194,11 @@ __global__ __launch_bounds__(512) void skinny_linear_x3_kernel(const float* __re
             const int nkb = fr.chunk_size < r ? (fr.chunk_size + 31) >> 5 : (kc + 31) >> 5, nks = fr.dk >> 4;
             const int a = col0 / fr.dk, cin = col0 - a * fr.dk + 8 * gq;
             const int kb = cin >> 4, hf2 = (cin >> 3) & 1;
-            f32x8s v;
+            f32x8 v;
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = (blk[j][8 * gq + e] + (bias ? bias[col0 + 8 * gq + e] : 0.f)) * fr.c_exp;
             bf16x8 hi, lo;
-            skinny_split8(v, hi, lo);
+            split8(v, hi, lo);
             u32x4 uh = __builtin_bit_cast(u32x4, hi), ul = __builtin_bit_cast(u32x4, lo);
             if (row0 + j >= r) uh = ul = u32x4{0u, 0u, 0u, 0u};
             u32x4* dst = reinterpret_cast<u32x4*>(out) + ch * fr.chunk_stride + ((int64_t)(a * nkb + b) * nks * 2 + 2 * kb) * 64 + 32 * hf2 + j;

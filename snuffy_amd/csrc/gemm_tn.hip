@@ -26,16 +26,9 @@
 // an operand's step image is 32 rows x 1024 bytes holding both planes as they lie in HBM -- full-line DMA, one row per instruction --
 // and the same swizzle on 64 chunk positions; only the fragment addresses differ (block bi, plane pl -> chunk 8 (bi >> 1) + 4 pl +
 // 2 (bi & 1) + half).  The training chain's images in this layout are 4 bytes per element instead of 6.
-#include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
 
 constexpr int TM = 256, TN_ = 256, KS = 32;          // tile (p x q), rows per step
 constexpr int IMG = KS * TM * 2;                      // one plane's step image: 32 rows x 512 B = 16 KiB
@@ -54,16 +47,9 @@ struct TnParams {
     int64_t ldc;
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 template <int PITCH>
 __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p) {   // rows r .. r + 3 and r + 16 .. r + 19 of one 16-column block
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 16 * PITCH));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+    return tr_frag(p, p + 16 * PITCH);
 }
 
 template <bool X3, bool HL>
@@ -256,17 +242,9 @@ int tn_parts(int64_t steps, int ntiles) {
 template <bool X3, bool HL = false>
 int launch_tn(const TnParams& P, hipStream_t s) {
     constexpr int lds = 2 * 2 * (X3 ? 2 : 1) * IMG;
-    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    const unsigned long long bit = snf::device_bit();
     auto kern = gemm_tn_kernel<X3, HL>;
-    if (!(attr_set_mask & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            snf::set_error("gemm_tn: cannot reserve %d bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        attr_set_mask |= bit;
-    }
+    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "gemm_tn")) return rc;
     const int nitems = P.tiles_p * P.tiles_q * P.parts;
     const int grid = ((nitems + 7) / 8) * 8;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, P);

@@ -21,23 +21,10 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "common.h"
+#include "mfma.h"
 #include "philox.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) float f32x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int TILE_ROWS = 128;  // query rows per workgroup step (4 waves x 32)
 
@@ -61,33 +48,6 @@ struct BwdParams {
     snf::DropoutState drop;   // mask regenerated in registers when thresh != 0 (and mask == null): same stream as the forward
 };
 
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-__device__ __forceinline__ bf16x8 load_frag(const float* p) {
-    f32x4 lo = *reinterpret_cast<const f32x4*>(p);
-    f32x4 hi = *reinterpret_cast<const f32x4*>(p + 4);
-    f32x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_convertvector(v, bf16x8);
-}
-__device__ __forceinline__ bf16x8 load_frag(const unsigned short* p) {
-    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p));
-}
-__device__ __forceinline__ float xhalf_sum(float v) {
-    const unsigned u = __float_as_uint(v);
-    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ bf16x8 lds_tr_frag(const unsigned char* p0, const unsigned char* p1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
-}
 __device__ __forceinline__ unsigned pack2(float a, float b) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
 }
@@ -346,8 +306,8 @@ __global__ __launch_bounds__(256, 1) void sparse_attn_bwd_mfma_kernel(BwdParams 
                 constexpr int koff = (32 * jb + 16 * u) * RP;
                 static_for<0, NCB>([&](auto db_t) __attribute__((always_inline)) {
                     constexpr int db = decltype(db_t)::value;
-                    const bf16x8 ao = lds_tr_frag(img_do + rt0[db] + koff, img_do + rt1[db] + koff);
-                    const bf16x8 ak = lds_tr_frag(img_kp + rt0[db] + koff, img_kp + rt1[db] + koff);
+                    const bf16x8 ao = tr_frag(img_do + rt0[db] + koff, img_do + rt1[db] + koff);
+                    const bf16x8 ak = tr_frag(img_kp + rt0[db] + koff, img_kp + rt1[db] + koff);
                     acc_v[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, __builtin_bit_cast(bf16x8, pb), acc_v[db], 0, 0, 0);
                     acc_q[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ak, __builtin_bit_cast(bf16x8, sb), acc_q[db], 0, 0, 0);
                 });
@@ -409,19 +369,9 @@ inline bool make_bwd_plan(int64_t n, int k, int h, int dk, BwdPlan* pl) {
 template <int DK, int NKB, typename QT, int MODE>
 int launch_bwd_mode(const BwdParams& P, const BwdPlan& pl, hipStream_t s) {
     const size_t lds = (size_t)2 * 32 * NKB * 2 * DK;
-    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    const unsigned long long attr_set_bit = snf::device_bit();
-    const bool attr_set = (attr_set_mask & attr_set_bit) != 0;
     auto kern = sparse_attn_bwd_mfma_kernel<DK, NKB, QT, MODE>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess) {
-            snf::set_error("sparse_attn_bwd_mfma: cannot reserve %zu bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        attr_set_mask |= attr_set_bit;
-    }
+    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "sparse_attn_bwd_mfma")) return rc;
     hipLaunchKernelGGL(kern, dim3(pl.num_wg), dim3(256), lds, s, P);
     return snf::check_launch("sparse_attn_bwd_mfma_kernel");
 }

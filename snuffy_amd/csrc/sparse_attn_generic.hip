@@ -13,7 +13,7 @@
 
 #include <atomic>
 
-#include "common.h"
+#include "mfma.h"
 #include "philox.h"
 
 namespace {
@@ -165,9 +165,6 @@ __global__ __launch_bounds__(256) void pt_v_kernel(const float* __restrict__ p /
 //   pt_v_mfma: a WAVE owns a [64 keys, 32 CT columns] tile of O over a slice of the rows; A = P^T and B = V are single coalesced
 //     dword loads (the lane layouts of the instruction ARE the memory layouts), 2 CT MFMAs per row pair.
 // ---------------------------------------------------------------------------------------------------------------
-typedef float mf32x16 __attribute__((ext_vector_type(16)));
-typedef float mf32x4 __attribute__((ext_vector_type(4)));
-
 template <int KBW>   // key blocks per wave: k <= 128 * KBW
 __global__ __launch_bounds__(256, KBW <= 4 ? 3 : 2) void scores_softmax_mfma_kernel(const float* __restrict__ q, const float* __restrict__ kp, int64_t n,
                                                                   int k, int h, int dk, float scale, float* __restrict__ p_out,
@@ -185,14 +182,14 @@ __global__ __launch_bounds__(256, KBW <= 4 ? 3 : 2) void scores_softmax_mfma_ker
     for (int e = threadIdx.x; e < 32 * dk4; e += 256) {
         const int r = e / dk4, c4 = e - r * dk4;
         const int64_t row = row0 + r;
-        mf32x4 val = {0.f, 0.f, 0.f, 0.f};
-        if (row < n) val = *reinterpret_cast<const mf32x4*>(q + row * d_model + a * dk + 4 * c4);
-        *reinterpret_cast<mf32x4*>(lq + r * pitch + 4 * c4) = val;
+        f32x4 val = {0.f, 0.f, 0.f, 0.f};
+        if (row < n) val = *reinterpret_cast<const f32x4*>(q + row * d_model + a * dk + 4 * c4);
+        *reinterpret_cast<f32x4*>(lq + r * pitch + 4 * c4) = val;
     }
     __syncthreads();
     const int nkb = (k + 31) >> 5;
     const int nt = dk >> 3;
-    mf32x16 S[KBW];
+    f32x16 S[KBW];
     const float* qr = lq + j * pitch + 4 * hf;
 #pragma unroll
     for (int c = 0; c < KBW; ++c) {
@@ -205,11 +202,11 @@ __global__ __launch_bounds__(256, KBW <= 4 ? 3 : 2) void scores_softmax_mfma_ker
             const float* kr = kp + (int64_t)key * d_model + a * dk + 4 * hf;
             int t = 0;
             for (; t + 4 <= nt; t += 4) {      // four steps' operands requested together (Kp comes from L2)
-                mf32x4 a4[4], b4[4];
+                f32x4 a4[4], b4[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    a4[u] = *reinterpret_cast<const mf32x4*>(kr + 8 * (t + u));
-                    b4[u] = *reinterpret_cast<const mf32x4*>(qr + 8 * (t + u));
+                    a4[u] = *reinterpret_cast<const f32x4*>(kr + 8 * (t + u));
+                    b4[u] = *reinterpret_cast<const f32x4*>(qr + 8 * (t + u));
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
@@ -217,8 +214,8 @@ __global__ __launch_bounds__(256, KBW <= 4 ? 3 : 2) void scores_softmax_mfma_ker
                     for (int e = 0; e < 4; ++e) S[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u][e], b4[u][e], S[c], 0, 0, 0);
             }
             for (; t < nt; ++t) {
-                const mf32x4 a4 = *reinterpret_cast<const mf32x4*>(kr + 8 * t);
-                const mf32x4 b4 = *reinterpret_cast<const mf32x4*>(qr + 8 * t);
+                const f32x4 a4 = *reinterpret_cast<const f32x4*>(kr + 8 * t);
+                const f32x4 b4 = *reinterpret_cast<const f32x4*>(qr + 8 * t);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) S[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], b4[e], S[c], 0, 0, 0);
             }
@@ -265,9 +262,9 @@ __global__ __launch_bounds__(256, KBW <= 4 ? 3 : 2) void scores_softmax_mfma_ker
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
                     const int key0 = 32 * kb + 8 * q4 + 4 * hf;
-                    const mf32x4 pv = {S[c][4 * q4] * inv, S[c][4 * q4 + 1] * inv, S[c][4 * q4 + 2] * inv, S[c][4 * q4 + 3] * inv};
+                    const f32x4 pv = {S[c][4 * q4] * inv, S[c][4 * q4 + 1] * inv, S[c][4 * q4 + 2] * inv, S[c][4 * q4 + 3] * inv};
                     if (vec && key0 + 4 <= k) {
-                        *reinterpret_cast<mf32x4*>(prow + key0) = pv;
+                        *reinterpret_cast<f32x4*>(prow + key0) = pv;
                     } else {
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
@@ -311,7 +308,7 @@ __global__ __launch_bounds__(256, 2) void pt_v_mfma_kernel(const float* __restri
         if (!cok[c]) col[c] = dk - 1;
         offb[c] = hf * ldv + col[c];
     }
-    mf32x16 acc[2][CT];
+    f32x16 acc[2][CT];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -392,16 +389,7 @@ __global__ __launch_bounds__(256, 2) void pt_v_mfma_kernel(const float* __restri
 //   against 313: five operand splits per six tile products, and 40 dword loads per 18 MFMAs) -- that product wants pre-split images,
 //   which is what the pipelined kernels do.
 // ---------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) __bf16 xbf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 xbf16x4;
-typedef __attribute__((ext_vector_type(8))) float mf32x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int xu32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int xu32x2;
-
-__device__ __forceinline__ void x3u_split8(const mf32x8 x, xbf16x8& hi, xbf16x8& lo) {
-    hi = __builtin_convertvector(x, xbf16x8);
-    lo = __builtin_convertvector(x - __builtin_convertvector(hi, mf32x8), xbf16x8);
-}
 
 // RT = 32-row tiles per workgroup.  At RT = 1 every workgroup of 32 rows pulls the whole Kp of its head through L1 (16 key blocks x 24 KiB at
 // k = 500, dk = 192: the texture path, not the matrix pipe, sets the pace); RT = 2 uses every Kp fragment -- and its split -- for two row tiles.
@@ -421,25 +409,25 @@ __global__ __launch_bounds__(256, (KBW * RT <= 4) ? 3 : 2) void scores_softmax_x
     for (int e = threadIdx.x; e < 32 * RT * dk4; e += 256) {
         const int r = e / dk4, c4 = e - r * dk4;
         const int64_t row = row0 + r;
-        mf32x4 val = {0.f, 0.f, 0.f, 0.f};
-        if (row < n) val = *reinterpret_cast<const mf32x4*>(q + row * ldq + a * dk + 4 * c4);
+        f32x4 val = {0.f, 0.f, 0.f, 0.f};
+        if (row < n) val = *reinterpret_cast<const f32x4*>(q + row * ldq + a * dk + 4 * c4);
         const xbf16x4 hi = __builtin_convertvector(val, xbf16x4);
-        const xbf16x4 lo = __builtin_convertvector(val - __builtin_convertvector(hi, mf32x4), xbf16x4);
-        *reinterpret_cast<xu32x2*>(ldsb + r * pitch + 8 * c4) = __builtin_bit_cast(xu32x2, hi);
-        *reinterpret_cast<xu32x2*>(ldsb + r * pitch + 2 * dk + 8 * c4) = __builtin_bit_cast(xu32x2, lo);
+        const xbf16x4 lo = __builtin_convertvector(val - __builtin_convertvector(hi, f32x4), xbf16x4);
+        *reinterpret_cast<u32x2*>(ldsb + r * pitch + 8 * c4) = __builtin_bit_cast(u32x2, hi);
+        *reinterpret_cast<u32x2*>(ldsb + r * pitch + 2 * dk + 8 * c4) = __builtin_bit_cast(u32x2, lo);
     }
     __syncthreads();
     const int nkb = (k + 31) >> 5;
     const int nt = dk >> 4;                    // 16-deep steps
-    mf32x16 S[KBW][RT];
+    f32x16 S[KBW][RT];
     const unsigned char* qr = ldsb + j * pitch + 16 * hf;          // + 32 rt pitch: row tile rt
-    auto step = [&](mf32x16 (&Sc)[RT], const mf32x4 x0, const mf32x4 x1, int t) __attribute__((always_inline)) {
-        xbf16x8 kh, kl;
-        x3u_split8(mf32x8{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]}, kh, kl);
+    auto step = [&](f32x16 (&Sc)[RT], const f32x4 x0, const f32x4 x1, int t) __attribute__((always_inline)) {
+        bf16x8 kh, kl;
+        split8(f32x8{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]}, kh, kl);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-            const xbf16x8 qh = __builtin_bit_cast(xbf16x8, *reinterpret_cast<const xu32x4*>(qr + 32 * rt * pitch + 32 * t));
-            const xbf16x8 ql = __builtin_bit_cast(xbf16x8, *reinterpret_cast<const xu32x4*>(qr + 32 * rt * pitch + 2 * dk + 32 * t));
+            const bf16x8 qh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qr + 32 * rt * pitch + 32 * t));
+            const bf16x8 ql = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qr + 32 * rt * pitch + 2 * dk + 32 * t));
             Sc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, ql, Sc[rt], 0, 0, 0);
             Sc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl, qh, Sc[rt], 0, 0, 0);
             Sc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qh, Sc[rt], 0, 0, 0);
@@ -458,17 +446,17 @@ __global__ __launch_bounds__(256, (KBW * RT <= 4) ? 3 : 2) void scores_softmax_x
             const float* kr = kp + (int64_t)key * d_model + a * dk + 8 * hf;
             int t = 0;
             for (; t + 2 <= nt; t += 2) {      // two steps' Kp rows requested together (L2)
-                mf32x4 x[2][2];
+                f32x4 x[2][2];
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
-                    x[u][0] = *reinterpret_cast<const mf32x4*>(kr + 16 * (t + u));
-                    x[u][1] = *reinterpret_cast<const mf32x4*>(kr + 16 * (t + u) + 4);
+                    x[u][0] = *reinterpret_cast<const f32x4*>(kr + 16 * (t + u));
+                    x[u][1] = *reinterpret_cast<const f32x4*>(kr + 16 * (t + u) + 4);
                 }
 #pragma unroll
                 for (int u = 0; u < 2; ++u) step(S[c], x[u][0], x[u][1], t + u);
             }
             for (; t < nt; ++t) {
-                const mf32x4 x0 = *reinterpret_cast<const mf32x4*>(kr + 16 * t), x1 = *reinterpret_cast<const mf32x4*>(kr + 16 * t + 4);
+                const f32x4 x0 = *reinterpret_cast<const f32x4*>(kr + 16 * t), x1 = *reinterpret_cast<const f32x4*>(kr + 16 * t + 4);
                 step(S[c], x0, x1, t);
             }
         }
@@ -524,9 +512,9 @@ __global__ __launch_bounds__(256, (KBW * RT <= 4) ? 3 : 2) void scores_softmax_x
 #pragma unroll
                     for (int q4 = 0; q4 < 4; ++q4) {
                         const int key0 = 32 * kb + 8 * q4 + 4 * hf;
-                        const mf32x4 pv = {S[c][rt][4 * q4] * inv, S[c][rt][4 * q4 + 1] * inv, S[c][rt][4 * q4 + 2] * inv, S[c][rt][4 * q4 + 3] * inv};
+                        const f32x4 pv = {S[c][rt][4 * q4] * inv, S[c][rt][4 * q4 + 1] * inv, S[c][rt][4 * q4 + 2] * inv, S[c][rt][4 * q4 + 3] * inv};
                         if (vec && key0 + 4 <= k) {
-                            *reinterpret_cast<mf32x4*>(prow + key0) = pv;
+                            *reinterpret_cast<f32x4*>(prow + key0) = pv;
                         } else {
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
@@ -746,14 +734,14 @@ __global__ __launch_bounds__(256, KBW <= 2 ? 3 : 2) void bwd_ds_mfma_kernel(cons
     for (int e = threadIdx.x; e < 32 * dk4; e += 256) {
         const int r = e / dk4, c4 = e - r * dk4;
         const int64_t row = row0 + r;
-        mf32x4 val = {0.f, 0.f, 0.f, 0.f};
-        if (row < n) val = *reinterpret_cast<const mf32x4*>(v + row * ldv + a * dk + 4 * c4);
-        *reinterpret_cast<mf32x4*>(lv + r * pitch + 4 * c4) = val;
+        f32x4 val = {0.f, 0.f, 0.f, 0.f};
+        if (row < n) val = *reinterpret_cast<const f32x4*>(v + row * ldv + a * dk + 4 * c4);
+        *reinterpret_cast<f32x4*>(lv + r * pitch + 4 * c4) = val;
     }
     __syncthreads();
     const int nkb = (k + 31) >> 5;
     const int nt = dk >> 3;
-    mf32x16 D[KBW];
+    f32x16 D[KBW];
     const float* vr = lv + j * pitch + 4 * hf;
 #pragma unroll
     for (int c = 0; c < KBW; ++c) {
@@ -766,11 +754,11 @@ __global__ __launch_bounds__(256, KBW <= 2 ? 3 : 2) void bwd_ds_mfma_kernel(cons
             const float* orow = dout + (int64_t)key * d_model + a * dk + 4 * hf;
             int t = 0;
             for (; t + 4 <= nt; t += 4) {
-                mf32x4 a4[4], b4[4];
+                f32x4 a4[4], b4[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    a4[u] = *reinterpret_cast<const mf32x4*>(orow + 8 * (t + u));
-                    b4[u] = *reinterpret_cast<const mf32x4*>(vr + 8 * (t + u));
+                    a4[u] = *reinterpret_cast<const f32x4*>(orow + 8 * (t + u));
+                    b4[u] = *reinterpret_cast<const f32x4*>(vr + 8 * (t + u));
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
@@ -778,8 +766,8 @@ __global__ __launch_bounds__(256, KBW <= 2 ? 3 : 2) void bwd_ds_mfma_kernel(cons
                     for (int e = 0; e < 4; ++e) D[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u][e], b4[u][e], D[c], 0, 0, 0);
             }
             for (; t < nt; ++t) {
-                const mf32x4 a4 = *reinterpret_cast<const mf32x4*>(orow + 8 * t);
-                const mf32x4 b4 = *reinterpret_cast<const mf32x4*>(vr + 8 * t);
+                const f32x4 a4 = *reinterpret_cast<const f32x4*>(orow + 8 * t);
+                const f32x4 b4 = *reinterpret_cast<const f32x4*>(vr + 8 * t);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) D[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], b4[e], D[c], 0, 0, 0);
             }
@@ -791,7 +779,7 @@ __global__ __launch_bounds__(256, KBW <= 2 ? 3 : 2) void bwd_ds_mfma_kernel(cons
     const int64_t base = ((int64_t)a * n + (rvalid ? row : n - 1)) * k;
     const bool vec = (k & 3) == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(ds) |
                                        (mask ? reinterpret_cast<uintptr_t>(mask) : 0)) & 15) == 0;
-    mf32x16 Pr[KBW];
+    f32x16 Pr[KBW];
     float dsum = 0.f;
 #pragma unroll
     for (int c = 0; c < KBW; ++c) {
@@ -799,17 +787,17 @@ __global__ __launch_bounds__(256, KBW <= 2 ? 3 : 2) void bwd_ds_mfma_kernel(cons
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4) {
             const int key0 = 32 * kb + 8 * q4 + 4 * hf;
-            mf32x4 pv = {0.f, 0.f, 0.f, 0.f}, mv = {1.f, 1.f, 1.f, 1.f};
+            f32x4 pv = {0.f, 0.f, 0.f, 0.f}, mv = {1.f, 1.f, 1.f, 1.f};
             if (kb < nkb) {
                 // the dropout mask of the forward: a tensor, or (round 6) regenerated from the forward's Philox state -- the same
                 // function of (head, row, key group) the forward kernel applied (philox.h), nothing to read
                 if (!mask && drop.thresh) {
                     const snf::philox_f4 m4 = snf::dropout_mask4(drop, a, n, rvalid ? row : n - 1, k, key0);
-                    mv = mf32x4{m4[0], m4[1], m4[2], m4[3]};
+                    mv = f32x4{m4[0], m4[1], m4[2], m4[3]};
                 }
                 if (vec && key0 + 4 <= k) {
-                    pv = *reinterpret_cast<const mf32x4*>(p + base + key0);
-                    if (mask) mv = *reinterpret_cast<const mf32x4*>(mask + base + key0);
+                    pv = *reinterpret_cast<const f32x4*>(p + base + key0);
+                    if (mask) mv = *reinterpret_cast<const f32x4*>(mask + base + key0);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
@@ -840,11 +828,11 @@ __global__ __launch_bounds__(256, KBW <= 2 ? 3 : 2) void bwd_ds_mfma_kernel(cons
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4) {
             const int key0 = 32 * kb + 8 * q4 + 4 * hf;
-            mf32x4 o;
+            f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = Pr[c][4 * q4 + e] * (D[c][4 * q4 + e] - dsum) * scale;
             if (vec && key0 + 4 <= k) {
-                *reinterpret_cast<mf32x4*>(ds + base + key0) = o;
+                *reinterpret_cast<f32x4*>(ds + base + key0) = o;
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
@@ -879,7 +867,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_dv_mfma_kernel(const float* __r
         cok[c] = col[c] < dk;
         if (!cok[c]) col[c] = dk - 1;
     }
-    mf32x16 av[CT], aq[CT];
+    f32x16 av[CT], aq[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c)
 #pragma unroll
@@ -890,16 +878,16 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_dv_mfma_kernel(const float* __r
     const float* kb_ = kp + a * dk;
     // operands of one group of 8 keys (4 MFMAs per accumulator); the NEXT group's are requested before the current group's MFMAs
     struct Grp {
-        mf32x4 p4, s4;
+        f32x4 p4, s4;
         float od[4][CT], kd[4][CT];
     };
     auto load_grp = [&](int t8, Grp& g) __attribute__((always_inline)) {
         const int key0 = t8 + 4 * hf;
-        g.p4 = mf32x4{0.f, 0.f, 0.f, 0.f}, g.s4 = mf32x4{0.f, 0.f, 0.f, 0.f};
+        g.p4 = f32x4{0.f, 0.f, 0.f, 0.f}, g.s4 = f32x4{0.f, 0.f, 0.f, 0.f};
         if (vec && key0 + 4 <= k) {
-            g.p4 = *reinterpret_cast<const mf32x4*>(prow + t8);
-            g.s4 = *reinterpret_cast<const mf32x4*>(srow + t8);
-            if (mrow) g.p4 *= *reinterpret_cast<const mf32x4*>(mrow + t8);
+            g.p4 = *reinterpret_cast<const f32x4*>(prow + t8);
+            g.s4 = *reinterpret_cast<const f32x4*>(srow + t8);
+            if (mrow) g.p4 *= *reinterpret_cast<const f32x4*>(mrow + t8);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -974,7 +962,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_dv_lds_kernel(const float* __re
     // B: thread t fetches float4 number t + 256 i (i < CT) of the chunk: key (t + 256 i) / (8 CT), columns 4 ((t + 256 i) % (8 CT)) ..
     const int r8 = lane >> 3, q4 = lane & 7;
     struct Stage {
-        mf32x4 pa[4], sa[4], bo[CT], bk[CT];
+        f32x4 pa[4], sa[4], bo[CT], bk[CT];
     };
     auto load_stage = [&](int kc0, Stage& st) __attribute__((always_inline)) {
         // (opaque indices: hoisted out of the chunk loop the per-thread address terms did not fit the registers next to 128 accumulators -- hipcc
@@ -988,14 +976,14 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_dv_lds_kernel(const float* __re
             int64_t row = row0 + 8 * i + r8;
             if (row > n - 1) row = n - 1;
             const int64_t off = ((int64_t)a * n + row) * k + key;
-            st.pa[i] = mf32x4{0.f, 0.f, 0.f, 0.f}, st.sa[i] = mf32x4{0.f, 0.f, 0.f, 0.f};
+            st.pa[i] = f32x4{0.f, 0.f, 0.f, 0.f}, st.sa[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (kok) {
-                st.pa[i] = *reinterpret_cast<const mf32x4*>(p + off);
-                st.sa[i] = *reinterpret_cast<const mf32x4*>(ds + off);
-                if constexpr (MASK == 1) st.pa[i] *= *reinterpret_cast<const mf32x4*>(mask + off);
+                st.pa[i] = *reinterpret_cast<const f32x4*>(p + off);
+                st.sa[i] = *reinterpret_cast<const f32x4*>(ds + off);
+                if constexpr (MASK == 1) st.pa[i] *= *reinterpret_cast<const f32x4*>(mask + off);
                 if constexpr (MASK == 2) {
                     const snf::philox_f4 m4 = snf::dropout_mask4(drop, a, n, row, k, key);
-                    st.pa[i] *= mf32x4{m4[0], m4[1], m4[2], m4[3]};
+                    st.pa[i] *= f32x4{m4[0], m4[1], m4[2], m4[3]};
                 }
             }
         }
@@ -1003,29 +991,29 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_dv_lds_kernel(const float* __re
         for (int i = 0; i < CT; ++i) {
             const int idx = tix + 256 * i;
             const int bkey = kc0 + idx / (8 * CT), col = 32 * cb0 + 4 * (idx % (8 * CT));
-            st.bo[i] = mf32x4{0.f, 0.f, 0.f, 0.f}, st.bk[i] = mf32x4{0.f, 0.f, 0.f, 0.f};
+            st.bo[i] = f32x4{0.f, 0.f, 0.f, 0.f}, st.bk[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (bkey < k && col + 4 <= dk) {
                 const int64_t off = (int64_t)bkey * d_model + a * dk + col;
-                st.bo[i] = *reinterpret_cast<const mf32x4*>(dout + off);
-                st.bk[i] = *reinterpret_cast<const mf32x4*>(kp + off);
+                st.bo[i] = *reinterpret_cast<const f32x4*>(dout + off);
+                st.bk[i] = *reinterpret_cast<const f32x4*>(kp + off);
             }
         }
     };
     auto park_stage = [&](const Stage& st) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<mf32x4*>(my_a + (8 * i + r8) * PA + 4 * q4) = st.pa[i];
-            *reinterpret_cast<mf32x4*>(my_a + 32 * PA + (8 * i + r8) * PA + 4 * q4) = st.sa[i];
+            *reinterpret_cast<f32x4*>(my_a + (8 * i + r8) * PA + 4 * q4) = st.pa[i];
+            *reinterpret_cast<f32x4*>(my_a + 32 * PA + (8 * i + r8) * PA + 4 * q4) = st.sa[i];
         }
 #pragma unroll
         for (int i = 0; i < CT; ++i) {
             const int idx = threadIdx.x + 256 * i;
             const int o = (idx / (8 * CT)) * PB + 4 * (idx % (8 * CT));
-            *reinterpret_cast<mf32x4*>(lds_b + o) = st.bo[i];
-            *reinterpret_cast<mf32x4*>(lds_b + 32 * PB + o) = st.bk[i];
+            *reinterpret_cast<f32x4*>(lds_b + o) = st.bo[i];
+            *reinterpret_cast<f32x4*>(lds_b + 32 * PB + o) = st.bk[i];
         }
     };
-    mf32x16 av[CT], aq[CT];
+    f32x16 av[CT], aq[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c)
 #pragma unroll
@@ -1042,8 +1030,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_dv_lds_kernel(const float* __re
 #pragma unroll
         for (int T = 0; T < 4; ++T) {
             if (kc0 + 8 * T >= k) break;                      // (wave-uniform) the last chunk's groups of 8 keys past k hold zeros
-            const mf32x4 p4 = *reinterpret_cast<const mf32x4*>(ar + 8 * T);
-            const mf32x4 s4 = *reinterpret_cast<const mf32x4*>(ar + 32 * PA + 8 * T);
+            const f32x4 p4 = *reinterpret_cast<const f32x4*>(ar + 8 * T);
+            const f32x4 s4 = *reinterpret_cast<const f32x4*>(ar + 32 * PA + 8 * T);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
 #pragma unroll
@@ -1075,19 +1063,11 @@ int launch_dq_dv_lds(const float* p, const float* mask, const float* ds, const f
                      float* dq, float* dv, dim3 grid, hipStream_t s, const snf::DropoutState drop) {
     constexpr int lds = (2 * 32 * 32 * CT + 4 * 2 * 32 * 36) * (int)sizeof(float);
     static thread_local unsigned long long set_mask[3] = {0, 0, 0};    // devices that have the LDS opt-in, per instantiation
-    const unsigned long long bit = snf::device_bit();
     const int which = mask ? 1 : drop.thresh ? 2 : 0;
     const void* fn = which == 1 ? reinterpret_cast<const void*>(bwd_dq_dv_lds_kernel<CT, 1>)
                                 : which == 2 ? reinterpret_cast<const void*>(bwd_dq_dv_lds_kernel<CT, 2>)
                                              : reinterpret_cast<const void*>(bwd_dq_dv_lds_kernel<CT, 0>);
-    if (!(set_mask[which] & bit)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            snf::set_error("bwd_dq_dv_lds: cannot reserve %d bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        set_mask[which] |= bit;
-    }
+    if (int rc = snf::lds_opt_in(fn, lds, &set_mask[which], "bwd_dq_dv_lds")) return rc;
     if (which == 1)
         hipLaunchKernelGGL((bwd_dq_dv_lds_kernel<CT, 1>), grid, dim3(256), lds, s, p, mask, ds, dout, kp, n, k, h, dk, dq, dv, drop);
     else if (which == 2)
@@ -1197,7 +1177,7 @@ __global__ __launch_bounds__(256, 2) void pt_v_lds_kernel(const float* __restric
     const float* pa = p + (int64_t)a * n * k;
     const float* va = v + a * dk;
     struct Stage {
-        mf32x4 pp[8], vv[CT];
+        f32x4 pp[8], vv[CT];
     };
     auto load_stage = [&](int64_t r0, Stage& st) __attribute__((always_inline)) {
 #pragma unroll
@@ -1205,31 +1185,31 @@ __global__ __launch_bounds__(256, 2) void pt_v_lds_kernel(const float* __restric
             const int idx = threadIdx.x + 256 * i;
             const int64_t row = r0 + (idx >> 6);
             const int key = kt0 + 4 * (idx & 63);
-            st.pp[i] = mf32x4{0.f, 0.f, 0.f, 0.f};
-            if (row < r_end && key + 4 <= k) st.pp[i] = *reinterpret_cast<const mf32x4*>(pa + row * k + key);
+            st.pp[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (row < r_end && key + 4 <= k) st.pp[i] = *reinterpret_cast<const f32x4*>(pa + row * k + key);
         }
 #pragma unroll
         for (int i = 0; i < CT; ++i) {
             const int idx = threadIdx.x + 256 * i;
             const int64_t row = r0 + idx / (8 * CT);
             const int col = 32 * cb0 + 4 * (idx % (8 * CT));
-            st.vv[i] = mf32x4{0.f, 0.f, 0.f, 0.f};
-            if (row < r_end && col + 4 <= dk) st.vv[i] = *reinterpret_cast<const mf32x4*>(va + row * ldv + col);
+            st.vv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (row < r_end && col + 4 <= dk) st.vv[i] = *reinterpret_cast<const f32x4*>(va + row * ldv + col);
         }
     };
     auto park_stage = [&](const Stage& st) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int idx = threadIdx.x + 256 * i;
-            *reinterpret_cast<mf32x4*>(lp + (idx >> 6) * PP + 4 * (idx & 63)) = st.pp[i];
+            *reinterpret_cast<f32x4*>(lp + (idx >> 6) * PP + 4 * (idx & 63)) = st.pp[i];
         }
 #pragma unroll
         for (int i = 0; i < CT; ++i) {
             const int idx = threadIdx.x + 256 * i;
-            *reinterpret_cast<mf32x4*>(lv + (idx / (8 * CT)) * PV + 4 * (idx % (8 * CT))) = st.vv[i];
+            *reinterpret_cast<f32x4*>(lv + (idx / (8 * CT)) * PV + 4 * (idx % (8 * CT))) = st.vv[i];
         }
     };
-    mf32x16 acc[2][CT];
+    f32x16 acc[2][CT];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -1633,13 +1613,10 @@ int snf_sparse_attn_fwd_ragged_f32(const float* q, int64_t ldq, const float* v, 
     static thread_local size_t lds_set = 0;
     static thread_local unsigned long long lds_dev = ~0ull;          // the opt-in is per device
     if (lds_dev != snf::device_bit()) lds_set = 0, lds_dev = snf::device_bit();
-    if (lds > lds_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ragged_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) {
-            snf::set_error("snf_sparse_attn_fwd_ragged_f32: cannot reserve %zu bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
+    if (lds > lds_set) {   // the size grows with the shapes seen: remembered here as a size, not as the helper's bit
+        unsigned long long unset = 0;
+        if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(ragged_attn_kernel), lds, &unset, "snf_sparse_attn_fwd_ragged_f32"))
+            return rc;
         lds_set = lds;
     }
     hipLaunchKernelGGL(ragged_attn_kernel, dim3((unsigned)bags, (unsigned)h), dim3(256), lds, snf::as_stream(stream), q, ldq, v, ldv,

@@ -30,7 +30,8 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "attn_plan.h"
+#include "mfma.h"
 #include "philox.h"
 
 namespace snf {
@@ -71,61 +72,23 @@ struct AttnParams {
     // reduction pass for that bag (a 64 x 1000-patch batch spent 29 us copying single partial tiles).  Null: always partials.
     float* out_direct;
 };
-// One bag of a varlen launch.  The grid is the concatenation of per-bag grids: every bag keeps a plan of its own (make_plan with
-// packed = true, a function of the bag's length only) and workgroup wg0 + i does what workgroup i of a launch of that bag alone
-// would do (same tiles, same partial tiles, same summation order in the reduction) -- a bag's result does not depend on what it
-// is packed with, bit for bit.  Against the single-bag entry points (latency plan: one tile per workgroup for small bags) only
-// the fp32 summation order of the partial tiles can differ.
-constexpr int VL_DESC = 12;   // wg0, row0, n, out_row0 (= first Kp / output row), tiles_per_head, tiles_per_wg, total_tiles,
-                              // seg_count, part0 (first partial slot), num_wg, direct (one workgroup per head), 0
-struct Plan {
-    int num_wg, tiles_per_head, tiles_per_wg, total_tiles, seg_count, nkb;
-};
+using Plan = TilePlan;   // make_plan below; the varlen table (VL_DESC, make_varlen_table) is described in attn_plan.h
 }  // namespace snf_attn
 
 namespace {
 using snf_attn::AttnParams;
 using snf_attn::Plan;
 using snf_attn::VL_DESC;
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) float f32x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+using snf_attn::VarlenPlan;
+using snf_attn::p_row_bytes;
 
 constexpr int TILE_ROWS = 128;  // query rows per workgroup step (4 waves x 32)
-// row pitch (bytes) of the bf16 P image in LDS: 64 bytes per key block, an ODD number of 64-byte units (bank rule below)
-constexpr int p_row_bytes(int nkb) { return 64 * (nkb | 1); }
-
-
-
-// compile-time loop: every index into the register-resident fragment arrays must be a constant, or the arrays go to
-// scratch (a "#pragma unroll" is only a hint and gives up on the larger variants)
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 __device__ __forceinline__ bf16x8 zero_frag() {
     u32x4 z = {0u, 0u, 0u, 0u};
     return __builtin_bit_cast(bf16x8, z);
 }
 
-// 8 consecutive elements -> bf16x8 (f32 source converted with v_cvt_pk_bf16_f32, round-to-nearest-even)
-__device__ __forceinline__ bf16x8 load_frag(const float* p) {
-    f32x4 lo = *reinterpret_cast<const f32x4*>(p);
-    f32x4 hi = *reinterpret_cast<const f32x4*>(p + 4);
-    f32x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_convertvector(v, bf16x8);
-}
-__device__ __forceinline__ bf16x8 load_frag(const unsigned short* p) {
-    u32x4 v = *reinterpret_cast<const u32x4*>(p);
-    return __builtin_bit_cast(bf16x8, v);
-}
 // S = Q Kp^T accumulates in ARCHITECTURAL VGPRs: the softmax reads S with the VALU, and the compiler's own choice for a
 // builtin MFMA result is the AGPR half of the file, which costs a v_accvgpr_read per element and -- with the O
 // accumulators already filling the AGPRs -- a storm of v_accvgpr_mov live-range splits (640 per tile, measured).
@@ -150,34 +113,6 @@ __device__ __forceinline__ void mfma_vgpr_zero_c(f32x16& acc, bf16x8 a, bf16x8 b
 }
 __device__ __forceinline__ void park_after_mfma(f32x16& x) { asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 7" : "+v"(x)); }
 __device__ __forceinline__ void pin_vgpr(f32x16& x) { asm volatile("" : "+v"(x)); }
-
-// One GEMM2 A operand (P^T fragment: key on the lane, 8 consecutive query rows in registers) out of the row-major P image:
-// two hardware transpose-reads.  ds_read_b64_tr_b16 semantics (probed on gfx950, tools/probes/tr16_probe.hip): every lane
-// supplies the address of its own 8-byte chunk; inside each group of 16 lanes the 16 chunks form a [4 rows][16 columns]
-// bf16 matrix (lane i = row i>>2, columns 4(i&3)..+3) and lane i receives column i.
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-__device__ __forceinline__ bf16x8 lds_read_p_frag(const unsigned char* p0, const unsigned char* p1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
-}
-// all-reduce across the two half-waves (lane l <-> lane l^32) on the VALU: v_permlane32_swap(x, x) = {x.lo, x.lo}, {x.hi, x.hi}
-__device__ __forceinline__ float xhalf_max(float v) {
-    const unsigned u = __float_as_uint(v);
-    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xhalf_sum(float v) {
-    const unsigned u = __float_as_uint(v);
-    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 
 // AUX = the caller asked for the attention matrix and/or the row log-sum-exp (extra stores after the softmax).
 // EXT = key-chunked launch: the row statistics come from sparse_attn_stats_kernel (all chunks), not from this chunk's scores.
@@ -585,7 +520,7 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
             if constexpr (m < M2) {
                 constexpr int sk = m / NT, ti = m % NT;
                 constexpr int off = sk * 16 * RS + ti * (4 / NCB) * 64;
-                pfr[m % 4] = lds_read_p_frag(rbase0 + off, rbase1 + off);
+                pfr[m % 4] = tr_frag(rbase0 + off, rbase1 + off);
             }
         };
         auto gemm2_one = [&](auto m_tag) __attribute__((always_inline)) {
@@ -593,14 +528,14 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
             constexpr int sk = m / NT, ti = m % NT;
             const int t_idx = w + 4 * ti;  // tile = kb * NCB + cb ; cb == t_idx % NCB is constant per wave
             if constexpr (m == 0) {
-                vfr[0] = lds_read_p_frag(vbase0, vbase1);
+                vfr[0] = tr_frag(vbase0, vbase1);
                 p_read(std::integral_constant<int, 0>{});
                 p_read(std::integral_constant<int, 1>{});
                 p_read(std::integral_constant<int, 2>{});
             }
             p_read(std::integral_constant<int, m + 3>{});
             if constexpr (ti == 0 && sk + 1 < 8)
-                vfr[(sk + 1) & 1] = lds_read_p_frag(vbase0 + (sk + 1) * 16 * VRS, vbase1 + (sk + 1) * 16 * VRS);
+                vfr[(sk + 1) & 1] = tr_frag(vbase0 + (sk + 1) * 16 * VRS, vbase1 + (sk + 1) * 16 * VRS);
             if (NT * 4 == NKB * NCB || t_idx < NKB * NCB)
                 acc_o[ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pfr[m % 4], vfr[sk & 1], acc_o[ti], 0, 0, 0);
         };
@@ -882,43 +817,17 @@ inline bool make_plan(int64_t n, int k, int h, int dk, Plan* pl, bool packed = f
         }
     if (!sel) return false;
     if (n > 0xffff00ll) return false;   // 24-bit row x pitch products inside the kernel
-    int64_t tph = (n + TILE_ROWS - 1) / TILE_ROWS;
-    int64_t total = tph * h;
-    if (total > 0x7fffffff) return false;
-    int cus = snf::cu_count();
-    int64_t num_wg = total < cus ? total : cus;
-    int64_t tpw = (total + num_wg - 1) / num_wg;
-    // A bag inside a PACKED (varlen) launch does not have the chip to itself: at least SMALL_BAG_TILES tiles (1024 rows) per
-    // workgroup, so a head of a small bag is one or two partial tiles instead of one per 128 rows -- the partial tiles are the
-    // bulk of such a launch's bytes (measured: 64 bags x 1000 rows, 87 -> 54 us + reduction 40 -> 29 us).  A bag launched ALONE
-    // keeps one tile per workgroup: its tiles run side by side on idle CUs (8 in a row cost it ~25 us of latency, measured).
-    constexpr int64_t SMALL_BAG_TILES = 8;
-    if (packed && total <= cus) tpw = tph < SMALL_BAG_TILES ? tph : SMALL_BAG_TILES;
-    num_wg = (total + tpw - 1) / tpw;
-    pl->num_wg = (int)num_wg;
-    pl->tiles_per_head = (int)tph;
-    pl->tiles_per_wg = (int)tpw;
-    pl->total_tiles = (int)total;
-    pl->seg_count = (int)((tpw + tph - 1) / tph + 1);
     pl->nkb = sel;
-    return true;
+    return snf_attn::make_tile_plan(n, h, TILE_ROWS, /*small_bag_tiles=*/8, packed, pl);
 }
 
 template <int DK, int NKB, typename QT, bool AUX, bool EXT = false, int TAILP = 8, bool VL = false>
 int launch_variant(const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
     constexpr int NKS = DK / 16;
     const size_t lds = (size_t)(NKB * NKS) * 1024 + (size_t)TILE_ROWS * (p_row_bytes(NKB) + 2 * DK);
-    static thread_local bool attr_set = false;
     auto kern = sparse_attn_mfma_kernel<DK, NKB, QT, AUX, EXT, TAILP, VL>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) {
-            snf::set_error("sparse_attn_mfma: cannot reserve %zu bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        attr_set = true;
-    }
+    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "sparse_attn_mfma")) return rc;
     hipLaunchKernelGGL(kern, dim3(pl.num_wg), dim3(512), lds, s, P);
     int rc = snf::check_launch("sparse_attn_mfma_kernel");
     if (rc) return rc;
@@ -962,35 +871,10 @@ int launch_nkb_varlen(const AttnParams& P, const Plan& pl, float* out, hipStream
 }
 
 // Geometry of a varlen launch: every bag keeps the plan of its own launch (make_plan), the grids are concatenated.
-// table (host memory, may be null to size it) = [bags][VL_DESC] descriptors, then the bag index of every workgroup.
-struct VarlenPlan {
-    int64_t total_wg, partial_slots;   // workgroups of the whole launch; partial tiles-slots (num_wg * seg_count summed)
-    int nkb;
-    bool all_direct;                   // every bag has one workgroup per head: no reduction pass at all
-};
 inline bool make_varlen_plan(const int64_t* offsets, int bags, int k, int h, int dk, VarlenPlan* vp, int32_t* table,
                              size_t table_ints) {
-    vp->total_wg = 0, vp->partial_slots = 0, vp->nkb = 0, vp->all_direct = true;
-    for (int b = 0; b < bags; ++b) {
-        const int64_t n = offsets[b + 1] - offsets[b];
-        Plan pl;
-        if (n < 1 || offsets[b] > 0x7fffffffll || !make_plan(n, k, h, dk, &pl, true)) return false;
-        const bool direct = pl.tiles_per_wg == pl.tiles_per_head;   // workgroup i of the bag = head i, whole
-        vp->all_direct = vp->all_direct && direct;
-        if (table) {
-            if ((size_t)(VL_DESC * bags) + (size_t)(vp->total_wg + pl.num_wg) > table_ints) return false;
-            int32_t* d = table + (size_t)VL_DESC * b;
-            d[0] = (int32_t)vp->total_wg, d[1] = (int32_t)offsets[b], d[2] = (int32_t)n, d[3] = b * k;
-            d[4] = pl.tiles_per_head, d[5] = pl.tiles_per_wg, d[6] = pl.total_tiles, d[7] = pl.seg_count;
-            d[8] = (int32_t)vp->partial_slots, d[9] = pl.num_wg, d[10] = direct ? 1 : 0, d[11] = 0;
-            for (int i = 0; i < pl.num_wg; ++i) table[(size_t)VL_DESC * bags + vp->total_wg + i] = b;
-        }
-        vp->total_wg += pl.num_wg;
-        vp->partial_slots += (int64_t)pl.num_wg * pl.seg_count;
-        vp->nkb = pl.nkb;
-        if (vp->total_wg > 0x3fffffff || vp->partial_slots > 0x3fffffff) return false;
-    }
-    return bags >= 1;
+    return snf_attn::make_varlen_table(offsets, bags, k, vp, table, table_ints,
+                                       [&](int64_t n, Plan* pl) { return make_plan(n, k, h, dk, pl, true); });
 }
 
 #define SNF_ATTN_CASE(NB, EXT)                                                                     \

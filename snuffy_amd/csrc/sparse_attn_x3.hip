@@ -25,24 +25,16 @@
 // LDS at dk = 128, 224 keys: Q hi+lo 32 KiB | P hi+lo 56 KiB | V 2 x (hi+lo) 64 KiB | row statistics 4 KiB = 156 KiB.
 #include <math.h>
 
-#include <type_traits>
-
-#include "common.h"
+#include "attn_plan.h"
+#include "mfma.h"
 #include "philox.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) float f32x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+using snf_attn::VL_DESC;
+using snf_attn::p_row_bytes;
+using X3Plan = snf_attn::TilePlan;
+using X3VarlenPlan = snf_attn::VarlenPlan;
 
 struct X3Params {
     const float* q;    // [n, ldq]
@@ -61,63 +53,25 @@ struct X3Params {
     float* partial;    // [num_wg * seg_count][tiles][4][64][4]
     int tiles_per_head, tiles_per_wg, total_tiles, seg_count;
     int64_t n_stride;  // rows per head of attn / lse (= n; the packed row count of a varlen launch)
-    const int* vl;     // varlen launch: [bags][VL_DESC] descriptors, then the bag of every workgroup (see below)
+    const int* vl;     // varlen launch: [bags][VL_DESC] descriptors, then the bag of every workgroup (attn_plan.h)
     int vl_bags;
     float* out_direct; // varlen: output [rows, h * dk] for bags with one workgroup per head (descriptor flag 10): stored straight from the
                        // accumulators, no partial tile and no reduction pass for that bag; null = always partials
     snf::DropoutState drop = {0u, 0u, 0u, 0u, 0u, 1.f};   // DROP instantiations (training, snuffy.py:166-167): O = (P o M)^T V, attn = P
 };
-// Varlen launch (many bags in one grid, single key chunk): the grid is the concatenation of per-bag grids -- every bag keeps a
-// plan of its own (x3_plan with packed = true, a function of its length only), so a bag's result does not depend on what it is
-// packed with, bit for bit; against snf_sparse_attn_fwd_x3 only the fp32 summation order of the partial tiles can differ.
-// descriptor: wg0, row0, n, out_row0 (first Kp / output row), tiles_per_head, tiles_per_wg, total_tiles, seg_count, part0, num_wg,
-// direct (tiles_per_wg == tiles_per_head: workgroup i of the bag is head i, whole)
-constexpr int VL_DESC = 12;
 
 constexpr int TROWS = 64;   // query rows per step (two 32-row blocks)
-constexpr int p_row_bytes(int nkb) { return 64 * (nkb | 1); }   // odd multiple of 64 B (bank rule of the transpose-read)
 
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// x (8 fp32) -> hi = bf16(x), lo = bf16(x - hi)
-__device__ __forceinline__ void split8(const f32x8 x, u32x4& hi, u32x4& lo) {
-#ifdef X3_ABL_NOSPLIT   // timing ablation (tools/x3_ablate.sh): two cheap packs instead of the split, wrong numbers
+// the shared split, with the timing ablation of tools/x3_ablate.sh in front of it
+__device__ __forceinline__ void x3_split8(const f32x8 x, u32x4& hi, u32x4& lo) {
+#ifdef X3_ABL_NOSPLIT   // two cheap packs instead of the split, wrong numbers
     const u32x4 a = __builtin_bit_cast(u32x4, f32x4{x[0], x[2], x[4], x[6]}), b = __builtin_bit_cast(u32x4, f32x4{x[1], x[3], x[5], x[7]});
     hi = (a >> 16) | (b & 0xffff0000u);
     lo = (a & 0xffffu) | (b << 16);
     return;
 #endif
-    const bf16x8 h = __builtin_convertvector(x, bf16x8);
-    const f32x8 r = x - __builtin_convertvector(h, f32x8);
-    hi = __builtin_bit_cast(u32x4, h);
-    lo = __builtin_bit_cast(u32x4, __builtin_convertvector(r, bf16x8));
+    split8(x, hi, lo);
 }
-__device__ __forceinline__ f32x8 load8(const float* p) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-    return f32x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p0, const unsigned char* p1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-__device__ __forceinline__ float xhalf_max(float v) {
-    const unsigned u = __float_as_uint(v);
-    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xhalf_sum(float v) {
-    const unsigned u = __float_as_uint(v);
-    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 
 // MODE 0: one launch covers all keys.  MODE 1: statistics pass of one key chunk (GEMM1 + max / sum, nothing else).
 // MODE 2: main pass of one key chunk with the row statistics of ALL chunks taken from P.stats.
@@ -215,7 +169,7 @@ __global__ __launch_bounds__(512, 2) void sparse_attn_x3_kernel(X3Params PA) {
         u32x4 hi, lo;
 #pragma unroll
         for (int i = 0; i < QPT; ++i) {
-            split8(qpre[i], hi, lo);
+            x3_split8(qpre[i], hi, lo);
             lds_qh[tid + 512 * i] = hi;
             lds_ql[tid + 512 * i] = lo;
         }
@@ -223,7 +177,7 @@ __global__ __launch_bounds__(512, 2) void sparse_attn_x3_kernel(X3Params PA) {
             unsigned char* vh = lds_v + vbuf * 2 * V_BYTES;
 #pragma unroll
             for (int i = 0; i < VPT; ++i) {
-                split8(vpre[i], hi, lo);
+                x3_split8(vpre[i], hi, lo);
                 const int p = tid + 512 * i;
                 const int row = p / NCH, ch = p % NCH;
                 const int off = row * VRS + 16 * ((ch + 4 * vrot(row)) & (NCH - 1));
@@ -245,7 +199,7 @@ __global__ __launch_bounds__(512, 2) void sparse_attn_x3_kernel(X3Params PA) {
 #pragma unroll
             for (int kb = 0; kb < NKS; ++kb) {
                 u32x4 hi, lo;
-                split8(raw[kb], hi, lo);
+                x3_split8(raw[kb], hi, lo);
                 if (pad) hi = lo = u32x4{0u, 0u, 0u, 0u};
                 kph[kb] = __builtin_bit_cast(bf16x8, hi);
                 kpl[kb] = __builtin_bit_cast(bf16x8, lo);
@@ -549,9 +503,6 @@ __global__ __launch_bounds__(64) void x3_reduce_kernel(const float* __restrict__
     }
 }
 
-struct X3Plan {
-    int num_wg, tiles_per_head, tiles_per_wg, total_tiles, seg_count, nkb;
-};
 bool x3_plan(int64_t n, int k, int h, int dk, X3Plan* pl, bool packed = false) {
     if (!(dk == 64 || dk == 128) || k < 1 || k > (dk == 128 ? 224 : 256) || n < 1) return false;
     const int need = (k + 31) / 32;
@@ -563,22 +514,9 @@ bool x3_plan(int64_t n, int k, int h, int dk, X3Plan* pl, bool packed = false) {
             break;
         }
     if (!sel) return false;
-    const int64_t tph = (n + TROWS - 1) / TROWS, total = tph * h;
-    if (total > 0x7fffffff) return false;
-    const int cus = snf::cu_count();
-    int64_t num_wg = total < cus ? total : cus;
-    int64_t tpw = (total + num_wg - 1) / num_wg;
-    // a bag inside a packed (varlen) launch: at least 16 tiles (1024 rows) per workgroup -- see make_plan of the bf16 kernel
-    constexpr int64_t SMALL_BAG_TILES = 16;
-    if (packed && total <= cus) tpw = tph < SMALL_BAG_TILES ? tph : SMALL_BAG_TILES;
-    num_wg = (total + tpw - 1) / tpw;
-    pl->num_wg = (int)num_wg;
-    pl->tiles_per_head = (int)tph;
-    pl->tiles_per_wg = (int)tpw;
-    pl->total_tiles = (int)total;
-    pl->seg_count = (int)((tpw + tph - 1) / tph + 1);
     pl->nkb = sel;
-    return true;
+    // a bag inside a packed (varlen) launch: at least 16 tiles (1024 rows) per workgroup
+    return snf_attn::make_tile_plan(n, h, TROWS, /*small_bag_tiles=*/16, packed, pl);
 }
 size_t x3_workspace(const X3Plan& pl, int dk) { return (size_t)pl.num_wg * pl.seg_count * (size_t)(pl.nkb * (dk / 32)) * 1024 * sizeof(float); }
 
@@ -587,18 +525,9 @@ int x3_launch(const X3Params& P, const X3Plan& pl, float* out, hipStream_t s) {
     constexpr int NKS = DK / 16;
     constexpr int q_bytes = (TROWS / 32) * NKS * 1024, p_bytes = TROWS * p_row_bytes(NKB), v_bytes = TROWS * 2 * DK;
     constexpr int lds = 2 * q_bytes + 2 * p_bytes + 4 * v_bytes + 8 * TROWS * 8;   // Q hi|lo, P hi|lo, V 2 x (hi|lo), statistics
-    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    const unsigned long long attr_set_bit = snf::device_bit();
-    const bool attr_set = (attr_set_mask & attr_set_bit) != 0;
     auto kern = sparse_attn_x3_kernel<DK, NKB, AUX, MODE, VL, DROP>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            snf::set_error("sparse_attn_x3: cannot reserve %d bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        attr_set_mask |= attr_set_bit;
-    }
+    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "sparse_attn_x3")) return rc;
     hipLaunchKernelGGL(kern, dim3(pl.num_wg), dim3(512), lds, s, P);
     int rc = snf::check_launch("sparse_attn_x3_kernel");
     if (rc || MODE == 1) return rc;
@@ -628,34 +557,13 @@ int x3_dispatch_varlen(const X3Params& P, const X3Plan& pl, float* out, hipStrea
     snf::set_error("sparse_attn_x3 (varlen): key-block count %d not built", pl.nkb);
     return SNF_EUNSUPPORTED;
 }
-struct X3VarlenPlan {
-    int64_t total_wg, partial_slots;
-    int nkb;
-    bool all_direct;   // every bag has one workgroup per head: no reduction pass
-};
 bool x3_varlen_plan(const int64_t* offsets, int bags, int k, int h, int dk, X3VarlenPlan* vp, int32_t* table, size_t table_ints) {
-    vp->total_wg = 0, vp->partial_slots = 0, vp->nkb = 0, vp->all_direct = true;
-    if (bags < 1 || k > (dk == 128 ? 224 : 256)) return false;   // single key chunk only
-    for (int b = 0; b < bags; ++b) {
-        const int64_t n = offsets[b + 1] - offsets[b];
-        X3Plan pl;
-        if (n < 1 || offsets[b] > 0x7fffffffll || !x3_plan(n, k, h, dk, &pl, true)) return false;
-        const bool direct = pl.tiles_per_wg == pl.tiles_per_head;
-        vp->all_direct = vp->all_direct && direct;
-        if (table) {
-            if ((size_t)(VL_DESC * bags) + (size_t)(vp->total_wg + pl.num_wg) > table_ints) return false;
-            int32_t* d = table + (size_t)VL_DESC * b;
-            d[0] = (int32_t)vp->total_wg, d[1] = (int32_t)offsets[b], d[2] = (int32_t)n, d[3] = b * k;
-            d[4] = pl.tiles_per_head, d[5] = pl.tiles_per_wg, d[6] = pl.total_tiles, d[7] = pl.seg_count;
-            d[8] = (int32_t)vp->partial_slots, d[9] = pl.num_wg, d[10] = direct ? 1 : 0, d[11] = 0;
-            for (int i = 0; i < pl.num_wg; ++i) table[(size_t)VL_DESC * bags + vp->total_wg + i] = b;
-        }
-        vp->total_wg += pl.num_wg;
-        vp->partial_slots += (int64_t)pl.num_wg * pl.seg_count;
-        vp->nkb = pl.nkb;
-        if (vp->total_wg > 0x3fffffff || vp->partial_slots > 0x3fffffff) return false;
+    if (bags < 1 || k > (dk == 128 ? 224 : 256)) {   // single key chunk only
+        vp->total_wg = 0, vp->partial_slots = 0, vp->nkb = 0, vp->all_direct = true;
+        return false;
     }
-    return true;
+    return snf_attn::make_varlen_table(offsets, bags, k, vp, table, table_ints,
+                                       [&](int64_t n, X3Plan* pl) { return x3_plan(n, k, h, dk, pl, true); });
 }
 template <int DK, int NB>
 int x3_modes(const X3Params& P, const X3Plan& pl, float* out, hipStream_t s, int mode) {

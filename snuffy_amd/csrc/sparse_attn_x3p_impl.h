@@ -33,18 +33,13 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "common.h"
+#include "mfma.h"
 
 namespace snf {
 extern unsigned long long* g_attn_trace;   // debug hook of sparse_attn_mfma.hip (snf_debug_attn_trace)
 extern int g_attn_trace_wg;
 
 namespace x3p {
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
 struct X3PParams {
     const unsigned short* q;   // hl image [n, ldq] bf16: head a, true column c at 2 a dk + 64 (c / 32) + c % 32 (hi), + 32 (lo)
     const unsigned short* v;   // hl image [n, ldv]
@@ -88,55 +83,8 @@ namespace {
 using snf::x3p::X3PParams;
 using snf::x3p::X3PPlan;
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) float f32x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
-
 constexpr int TR = 32;       // query rows per tile
 
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-__device__ __forceinline__ f32x8 load8(const float* p) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-    return f32x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-__device__ __forceinline__ void split8(const f32x8 x, u32x4& hi, u32x4& lo) {
-    const bf16x8 h = __builtin_convertvector(x, bf16x8);
-    const f32x8 r = x - __builtin_convertvector(h, f32x8);
-    hi = __builtin_bit_cast(u32x4, h);
-    lo = __builtin_bit_cast(u32x4, __builtin_convertvector(r, bf16x8));
-}
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p0, const unsigned char* p1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-__device__ __forceinline__ float xhalf_max(float v) {
-    const unsigned u = __float_as_uint(v);
-    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xhalf_sum(float v) {
-    const unsigned u = __float_as_uint(v);
-    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 // timing ablations (dev builds, tools/x3p_abl.sh; results wrong): a stage's MFMAs replaced by an opaque use of their operands
 __device__ __forceinline__ f32x16 mfma_off(bf16x8 a, bf16x8 b, f32x16 c) {
     asm volatile("" : "+v"(c) : "v"(a), "v"(b));
@@ -1159,15 +1107,7 @@ int x3p_launch(const X3PParams& P, const X3PPlan& pl, float* out, hipStream_t s)
     static_assert(lds <= 160 * 1024, "sparse_attn_x3p: LDS budget");
     auto kern = sparse_attn_x3p_kernel<DK, NKB, KBW, AUX, MODE>;
     static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    const unsigned long long attr_set_bit = snf::device_bit();
-    if (!(attr_set_mask & attr_set_bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            snf::set_error("sparse_attn_x3p: cannot reserve %d bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        attr_set_mask |= attr_set_bit;
-    }
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "sparse_attn_x3p")) return rc;
     const int nch = P.merged > 1 ? P.merged : 1;
     const int csize = P.merged > 1 ? P.chunk_size : P.k;
     if (P.kp && (MODE != 2 || P.merged <= 1)) {   // (the merged statistics launch has already made the fragments of every chunk;

@@ -104,12 +104,9 @@ extern "C" int snf_tile_preprocess_u8(const void* img_u8, int b, int h, int w, i
     P.cols = reinterpret_cast<unsigned short*>(cols_bf16);
     P.ps = cols_bf16 ? patch : 0;
     auto kern = tile_preprocess_kernel;
-    if (lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            snf::set_error("snf_tile_preprocess_u8: cannot reserve %zu bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
+    if (lds > 64 * 1024) {   // the size depends on the tile: set on every such call, nothing remembered
+        unsigned long long unset = 0;
+        if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &unset, "snf_tile_preprocess_u8")) return rc;
     }
     hipLaunchKernelGGL(kern, dim3(c, b), dim3(256), lds, snf::as_stream(stream), P);
     return snf::check_launch("tile_preprocess_kernel");

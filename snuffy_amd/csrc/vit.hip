@@ -12,29 +12,9 @@
 //   snf_vit_attention_x3_f32 the same program in the fp32-class arithmetic (split-bf16 x3 products), fp32 in / fp32 out
 #include <math.h>
 
-#include <type_traits>
-
-#include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) float f32x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // patchify: cols[(b*gh + gy)*gw + gx][(c*ps + i)*ps + j] = img[b][c][gy*ps + i][gx*ps + j]
@@ -360,10 +340,6 @@ __global__ __launch_bounds__(256) void vit_attention_f32_kernel(const float* __r
 //          one workgroup per CU -- under the 128-register bound of the one-image form the chunked bf16 kernel spilled 85).
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int VIT_ATTN_THREADS = 512;   // 8 waves: one 32-query tile each (T = 197 -> 7 tiles in one round)
-__device__ __forceinline__ void vit_split8(const f32x8 x, bf16x8& hi, bf16x8& lo) {
-    hi = __builtin_convertvector(x, bf16x8);
-    lo = __builtin_convertvector(x - __builtin_convertvector(hi, f32x8), bf16x8);
-}
 template <int NKB, bool CHUNK, bool X3>
 __global__ __launch_bounds__(VIT_ATTN_THREADS, (X3 || CHUNK) ? 2 : 4) void vit_attention_mfma_kernel(const void* __restrict__ qkv_, int B, int T,
                                                                                           int h, float scale, void* __restrict__ out_,
@@ -400,7 +376,7 @@ __global__ __launch_bounds__(VIT_ATTN_THREADS, (X3 || CHUNK) ? 2 : 4) void vit_a
         static_for<0, 4>([&](auto ks) __attribute__((always_inline)) {
             if constexpr (X3) {
                 const f32x4 x0 = *reinterpret_cast<const f32x4*>(qp + 16 * ks), x1 = *reinterpret_cast<const f32x4*>(qp + 16 * ks + 4);
-                vit_split8(f32x8{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]}, qf[ks], ql[ks]);
+                split8(f32x8{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]}, qf[ks], ql[ks]);
             } else {
                 qf[ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qp + 16 * ks));
             }
@@ -432,8 +408,8 @@ __global__ __launch_bounds__(VIT_ATTN_THREADS, (X3 || CHUNK) ? 2 : 4) void vit_a
                 const int key = c >> 3, part = c & 7;
                 if (key < 32 * NKB) {
                     bf16x8 kh, kl, vh, vl;
-                    vit_split8(kst[i], kh, kl);
-                    vit_split8(vst[i], vh, vl);
+                    split8(kst[i], kh, kl);
+                    split8(vst[i], vh, vl);
                     unsigned char* kp = smem + (key * KPITCH + part * 8) * 2;
                     unsigned char* vp = lds_v0 + key * 128 + 16 * ((part + 4 * ((key >> 1) & 1)) & 7);
                     *reinterpret_cast<u32x4*>(kp) = __builtin_bit_cast(u32x4, kh);
@@ -477,11 +453,7 @@ __global__ __launch_bounds__(VIT_ATTN_THREADS, (X3 || CHUNK) ? 2 : 4) void vit_a
         const int r0 = k_base + vkey, r1 = r0 + 8;
         const unsigned char* p0 = lds_v0 + plane * VBYTES + r0 * 128 + 16 * ((vch + 4 * db + 4 * ((r0 >> 1) & 1)) & 7) + vhalf;
         const unsigned char* p1 = lds_v0 + plane * VBYTES + r1 * 128 + 16 * ((vch + 4 * db + 4 * ((r1 >> 1) & 1)) & 7) + vhalf;
-        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
-        const s16x8 vv = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(bf16x8, vv);
+        return tr_frag(p0, p1);
     };
 
     const float c_exp = scale * 1.44269504088896340736f;
@@ -552,7 +524,7 @@ __global__ __launch_bounds__(VIT_ATTN_THREADS, (X3 || CHUNK) ? 2 : 4) void vit_a
             // this lane's 8 keys of the k-step: {16u + 4hf + 0..3} and {16u + 8 + 4hf + 0..3} of block jb
             if constexpr (X3) {
                 bf16x8 ph, pl;
-                vit_split8(pv, ph, pl);
+                split8(pv, ph, pl);
                 static_for<0, 2>([&](auto db_t) __attribute__((always_inline)) {
                     constexpr int db = decltype(db_t)::value;
                     const bf16x8 vh = v_frag(0, 32 * jb + 16 * u, db), vl = v_frag(1, 32 * jb + 16 * u, db);
@@ -640,19 +612,10 @@ template <int NKB, bool CHUNK, bool X3>
 int launch_vit_mfma(const void* qkv, int B, int T, int h, float scale, void* out, hipStream_t s, int out_hl = 0) {
     constexpr size_t lds = (size_t)(X3 ? 2 : 1) * ((size_t)(32 * NKB * (64 + 8)) * sizeof(unsigned short) + (size_t)32 * NKB * 128);
     static_assert(lds <= 160 * 1024, "vit_attention_mfma: LDS budget");
-    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    const unsigned long long attr_set_bit = snf::device_bit();
-    const bool attr_set = (attr_set_mask & attr_set_bit) != 0;
     auto kern = vit_attention_mfma_kernel<NKB, CHUNK, X3>;
-    if (!attr_set && lds > 48 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess) {
-            snf::set_error("vit_attention_mfma: cannot reserve %zu bytes of LDS", lds);
-            (void)hipGetLastError();
-            return SNF_ELAUNCH;
-        }
-        attr_set_mask |= attr_set_bit;
-    }
+    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
+    if (lds > 48 * 1024)
+        if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "vit_attention_mfma")) return rc;
     // chunked keys: a workgroup serves tpw <= 8 query tiles (one per wave); the tiles are spread evenly over the workgroups
     const int ntile = (T + 31) / 32;
     const int nz = CHUNK ? (ntile + 7) / 8 : 1;

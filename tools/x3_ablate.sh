@@ -1,6 +1,6 @@
 #!/bin/bash
 # Timing ablations of sparse_attn_x3_kernel (numerically wrong on purpose; never shipped): what the in-kernel split of Q / V costs.  Builds side copies of the library under /tmp, runs tools/kbench.py x3B against each.
-#   X3_ABL_NOSPLIT  split8 -> two cheap packs (keeps the data dependence and the LDS stores)
+#   X3_ABL_NOSPLIT  x3_split8 -> two cheap packs (keeps the data dependence and the LDS stores)
 set -u
 ROOT=$(pwd)
 for V in ${VARIANTS:-BASE X3_ABL_NOSPLIT}; do
