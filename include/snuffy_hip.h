@@ -458,8 +458,9 @@ int snf_gemm_hl_gated_bf16(const void* a_hl, int64_t lda, const void* w_hl, int6
  *   both -1: one bf16 product.  Tiles of 256 x 256 cut into row parts (one workgroup each), summed in part order (bit-reproducible).
  *   hl != 0: both operands are INTERLEAVED images instead ([hi(32) | lo(32)] per 32 columns; a_hi / b_hi = the image column where the
  *   operand starts, a multiple of 64; a_lo, b_lo ignored; p % 32 == 0, q % 32 == 0) -- full 128-byte lines all the way.
- *   workspace: snf_gemm_tn_ws_bytes(n, p, q) bytes of plain scratch memory.  Domain: n % 32 == 0, p % 8 == 0, q % 8 == 0, plane offsets
- *   % 8 == 0, 16-byte aligned rows. */
+ *   workspace: snf_gemm_tn_ws_bytes(n, p, q) bytes of plain scratch memory.  Domain: n >= 1 (the rows are consumed in steps of 32; a
+ *   last step of n % 32 rows stages only those rows and zeros for the others -- nothing beyond row n - 1 of a or b is read, the
+ *   buffers may end there), p % 8 == 0, q % 8 == 0, plane offsets % 8 == 0, 16-byte aligned rows. */
 size_t snf_gemm_tn_ws_bytes(int64_t n, int p, int q);
 int snf_gemm_tn_f32(const void* a, int64_t lda, int a_hi, int a_lo, const void* b, int64_t ldb, int b_hi, int b_lo, int hl, int64_t n, int p,
                     int q, float* c, int64_t ldc, void* workspace, size_t workspace_bytes, snf_stream_t stream);

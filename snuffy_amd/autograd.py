@@ -493,7 +493,7 @@ def _hl_planes_sum(img):
 def _x3_train_hl_ok(n, d, f):
     """The one-pass chain applies: hl images (32-column groups), every projection fills the chip with 256 x 256 tiles, the three weight
     gradients are in gemm_tn's domain."""
-    return (X3_TRAIN_HL and d % 32 == 0 and f % 32 == 0 and n % 32 == 0 and ops.hl_eligible(n, 2 * d, d) and ops.hl_eligible(n, f, d)
+    return (X3_TRAIN_HL and d % 32 == 0 and f % 32 == 0 and ops.hl_eligible(n, 2 * d, d) and ops.hl_eligible(n, f, d)
             and ops.hl_eligible(n, d, f) and ops.GEMM_TN and n >= 1024 and d * f >= 65536)
 
 

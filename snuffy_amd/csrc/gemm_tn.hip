@@ -26,6 +26,10 @@
 // an operand's step image is 32 rows x 1024 bytes holding both planes as they lie in HBM -- full-line DMA, one row per instruction --
 // and the same swizzle on 64 chunk positions; only the fragment addresses differ (block bi, plane pl -> chunk 8 (bi >> 1) + 4 pl +
 // 2 (bi & 1) + half).  The training chain's images in this layout are 4 bytes per element instead of 6.
+//
+// Row tail: a bag of n rows takes ceil(n / 32) steps.  When n % 32 != 0 the last step of the last row part stages rows 0 .. n % 32 - 1 only
+// and fills the other rows of all its LDS images with zeros (stage_tail below); the caller's images end at row n - 1.  Every other step,
+// and every step of a bag of whole steps, runs as before: same partition, same summation order.
 #include "mfma.h"
 
 namespace {
@@ -40,7 +44,8 @@ struct TnParams {
     int64_t lda, ldb;
     int a_hi, a_lo, b_hi, b_lo;   // column offsets of the planes (elements)
     int p, q;                      // output rows (columns of A's planes), output columns (columns of B's planes)
-    int steps;                     // n / 32
+    int steps;                     // ceil(n / 32)
+    int tail;                      // n % 32: rows of the last step when it is cut short (0: every step is whole)
     int tiles_p, tiles_q, parts;
     float* slab;                   // [parts][tiles][256 x 256] f32 in fragment order
     float* c;                      // reduce: [p, ldc]
@@ -73,6 +78,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_kernel(const TnParams P) {
     const int part = item / ntiles, tile = item - part * ntiles;
     const int tp = tile / P.tiles_q, tq = tile - tp * P.tiles_q;
     const int s_begin = (int)((int64_t)part * P.steps / P.parts), ns = (int)((int64_t)(part + 1) * P.steps / P.parts) - s_begin;
+    // the bag's last step is cut short at row n - 1 (n % 32 != 0): it is the last step of the last row part
+    const int ns_whole = ns - (P.tail != 0 && part == P.parts - 1 ? 1 : 0);
 
     // ---- LDS-DMA sources.  A plane image is 16 pieces of 2 rows x 512 B; wave wid stages pieces 2 wid, 2 wid + 1 (rows 4 wid ..
     // 4 wid + 3) of every image; lane l lands at row 2 piece + (l >> 5), chunk position l & 31 and fetches true chunk
@@ -128,6 +135,45 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_kernel(const TnParams P) {
             }
         }
     };
+    // The cut step: rows 0 .. tail - 1 are staged as above, rows tail .. 31 are neither read (the caller's images end at row n - 1) nor
+    // left as they are (a stale row may hold Inf / NaN bit patterns, and 0 x NaN = NaN): the lanes that would have fetched them write
+    // zeros to their own 16 bytes of the piece instead, in BOTH operands.  HL: an instruction is one row -- the test is wave-uniform.
+    // Planes: an instruction is two rows, lanes 0 .. 31 / 32 .. 63 -- the DMA runs under the lanes' own mask (its LDS side is
+    // base + 16 lane: a masked lane writes nothing) and the other lanes store.  The stores are this wave's own, complete before it
+    // reaches the step's barrier.
+    auto stage_tail = [&](int kstep, int buf) __attribute__((always_inline)) {
+        unsigned char* base = smem + buf * STEP_BYTES;
+        const unsigned short* ap = a_base + (int64_t)kstep * KS * P.lda;
+        const unsigned short* bp = b_base + (int64_t)kstep * KS * P.ldb;
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+        // the lane index again, from the thread index and out of the optimiser's sight: nothing of this path is worth a register
+        // across the steady-state loop, which has none to spare
+        unsigned ln = threadIdx.x;
+        asm volatile("" : "+v"(ln));
+        ln &= 63;
+#pragma unroll
+        for (int j = 0; j < (HL ? 4 : 2); ++j) {
+            const int piece = (HL ? 4 * wid + j : 2 * wid + j) * 1024;
+            const int row = HL ? 4 * wid + j : 2 * (2 * wid + j) + (int)(ln >> 5);
+            if (row < P.tail) {
+                __builtin_amdgcn_global_load_lds((glb_void*)(ap + src_a[j] + P.a_hi), (lds_void*)(base + piece), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((glb_void*)(bp + src_b[j] + P.b_hi), (lds_void*)(base + B_OFF + piece), 16, 0, 0);
+                if constexpr (X3 && !HL) {
+                    __builtin_amdgcn_global_load_lds((glb_void*)(ap + src_a[j] + P.a_lo), (lds_void*)(base + IMG + piece), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((glb_void*)(bp + src_b[j] + P.b_lo), (lds_void*)(base + B_OFF + IMG + piece), 16, 0, 0);
+                }
+            } else {
+                unsigned char* mine = base + piece + 16 * ln;
+                *reinterpret_cast<u32x4*>(mine) = zero;
+                *reinterpret_cast<u32x4*>(mine + B_OFF) = zero;
+                if constexpr (X3 && !HL) {
+                    *reinterpret_cast<u32x4*>(mine + IMG) = zero;
+                    *reinterpret_cast<u32x4*>(mine + B_OFF + IMG) = zero;
+                }
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
 
     // ---- fragment addresses: lane (g = l >> 4, i = l & 15) supplies the 8-byte chunk of row 4 g + (i >> 2), columns 4 (i & 3) .. + 3 of a
     // 16-column block; block index bi (16 wr' + ... in units of 16 columns) sits at chunk position 2 (bi ^ s7) + ((i & 3) >> 1)
@@ -150,7 +196,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_kernel(const TnParams P) {
     f32x4 acc[8][4];
     bf16x8 af[8], bh[4], bl[X3 ? 4 : 1];
 
-    stage(0, 0);
+    if (ns_whole > 0) stage(0, 0);
+    else stage_tail(0, 0);
     int buf = 0;
     for (int s = 0; s < ns; ++s) {
         // this step's images have landed (every wave waits for its own pieces, then all meet); the other buffer is free: its last
@@ -169,7 +216,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_kernel(const TnParams P) {
             for (int ni = 0; ni < 4; ++ni) bl[ni] = tr_frag<PITCH>(b_addr(base, ni) + LO);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (s + 1 < ns) stage(s + 1, buf ^ 1);
+        if (__builtin_expect(s + 1 < ns_whole, 1)) stage(s + 1, buf ^ 1);
+        else if (s + 1 < ns) stage_tail(s + 1, buf ^ 1);      // once per launch, in one row part: out of the loop's line
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         // acc[mi][ni] (lane (i, g)) = C[p = 16 mi' + i][q = 16 ni' + 4 g .. + 3]: B's fragment is the MFMA's first operand
@@ -258,9 +306,9 @@ int launch_tn(const TnParams& P, hipStream_t s) {
 }  // namespace
 
 extern "C" size_t snf_gemm_tn_ws_bytes(int64_t n, int p, int q) {
-    if (n < KS || p < 1 || q < 1) return 0;
+    if (n < 1 || p < 1 || q < 1) return 0;
     const int ntiles = ((p + TM - 1) / TM) * ((q + TN_ - 1) / TN_);
-    return (size_t)tn_parts(n / KS, ntiles) * ntiles * (size_t)(TM * TN_) * sizeof(float);
+    return (size_t)tn_parts((n + KS - 1) / KS, ntiles) * ntiles * (size_t)(TM * TN_) * sizeof(float);
 }
 
 extern "C" int snf_gemm_tn_f32(const void* a, int64_t lda, int a_hi, int a_lo, const void* b, int64_t ldb, int b_hi, int b_lo, int hl,
@@ -272,12 +320,12 @@ extern "C" int snf_gemm_tn_f32(const void* a, int64_t lda, int a_hi, int a_lo, c
     SNF_REQUIRE(!x3 || (a_lo >= 0 && b_lo >= 0), "snf_gemm_tn_f32: both operands carry a lo plane, or neither");
     const int64_t a_w = hl ? (int64_t)a_hi + 2 * (int64_t)p : (int64_t)(a_lo > a_hi ? a_lo : a_hi) + p;
     const int64_t b_w = hl ? (int64_t)b_hi + 2 * (int64_t)q : (int64_t)(b_lo > b_hi ? b_lo : b_hi) + q;
-    if ((hl && (p % 32 || q % 32 || a_hi % 64 || b_hi % 64)) || n % KS || p % 8 || q % 8 || a_hi < 0 || b_hi < 0 || a_hi % 8 || b_hi % 8 || (x3 && (a_lo % 8 || b_lo % 8)) || lda % 8 || ldb % 8 ||
+    if ((hl && (p % 32 || q % 32 || a_hi % 64 || b_hi % 64)) || p % 8 || q % 8 || a_hi < 0 || b_hi < 0 || a_hi % 8 || b_hi % 8 || (x3 && (a_lo % 8 || b_lo % 8)) || lda % 8 || ldb % 8 ||
         lda < a_w || ldb < b_w || ldc < q || ldc % 4 ||
         (reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(workspace)) % 16 ||
         (KS + 1) * lda >= 0x7fffffffll || (KS + 1) * ldb >= 0x7fffffffll) {
         snf::set_error("snf_gemm_tn_f32: shape n=%lld p=%d q=%d (lda %lld ldb %lld ldc %lld, planes %d %d / %d %d) outside the kernel's domain "
-                       "(n %% 32, p %% 8, q %% 8, plane offsets %% 8, 16-byte aligned rows)",
+                       "(p %% 8, q %% 8, plane offsets %% 8, 16-byte aligned rows)",
                        (long long)n, p, q, (long long)lda, (long long)ldb, (long long)ldc, a_hi, a_lo, b_hi, b_lo);
         return SNF_EUNSUPPORTED;
     }
@@ -291,7 +339,7 @@ extern "C" int snf_gemm_tn_f32(const void* a, int64_t lda, int a_hi, int a_lo, c
     P.lda = lda, P.ldb = ldb;
     P.a_hi = a_hi, P.a_lo = a_lo, P.b_hi = b_hi, P.b_lo = b_lo;
     P.p = p, P.q = q;
-    P.steps = (int)(n / KS);
+    P.steps = (int)((n + KS - 1) / KS), P.tail = (int)(n % KS);
     P.tiles_p = (p + TM - 1) / TM, P.tiles_q = (q + TN_ - 1) / TN_;
     P.parts = tn_parts(P.steps, P.tiles_p * P.tiles_q);
     P.slab = reinterpret_cast<float*>(workspace);

@@ -1319,9 +1319,9 @@ GEMM_TN = True          # the weight-gradient contractions of the training step 
 
 
 def gemm_tn_supported(n, p, q, *images):
-    """Shapes / operands snf_gemm_tn_f32 takes: whole 32-row steps, 8-column granules, bf16 images with 16-byte aligned rows, an
-    output large enough to be worth the matrix cores."""
-    if not GEMM_TN or n < 1024 or n % 32 or p % 8 or q % 8 or p * q < 65536:
+    """Shapes / operands snf_gemm_tn_f32 is used for: any bag length from 1024 rows (the kernel cuts the last 32-row step short),
+    8-column granules, bf16 images with 16-byte aligned rows, an output large enough to be worth the matrix cores."""
+    if not GEMM_TN or n < 1024 or p % 8 or q % 8 or p * q < 65536:
         return False
     return all(t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0
                and t.shape[0] == n and 33 * t.stride(0) < 2 ** 31 for t in images)
@@ -1332,7 +1332,8 @@ def gemm_tn(a_img, b_img, p, q, a_planes=(0, -1), b_planes=(0, -1), out=None, hl
     b = the q columns at b_planes[0] of b_img [n, .]; with lo planes (a_planes[1], b_planes[1] >= 0: split images [hi | hi | lo]) the
     product is fp32-class (hi hi + hi lo + lo hi), otherwise one bf16 product.  hl: both images are interleaved ones ([hi(32) | lo(32)]
     per 32 columns; a_planes[0] / b_planes[0] = the IMAGE column where the operand starts, p % 32 == q % 32 == 0).  The contraction runs
-    over the BAG axis: the weight gradients of the training step."""
+    over the BAG axis: the weight gradients of the training step.  n is any length gemm_tn_supported takes; only rows 0 .. n - 1 of
+    either image are read."""
     n = a_img.shape[0]
     if not gemm_tn_supported(n, p, q, a_img, b_img) or (hl and (p % 32 or q % 32 or a_planes[0] % 64 or b_planes[0] % 64)):
         raise ValueError("gemm_tn: shape n=%d p=%d q=%d / operands outside the kernel's domain" % (n, p, q))
