@@ -467,6 +467,24 @@ int snf_gemm_tn_f32(const void* a, int64_t lda, int a_hi, int a_lo, const void* 
 int snf_gemm_hl_ws_bf16(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias, const float* resid,
                         int64_t ldr, int64_t m, int n, int k, int act, void* c, int64_t ldc, int out_dtype, void* workspace,
                         size_t workspace_bytes, snf_stream_t stream);
+/* Encoder dropout of a training step (nn.Dropout(encoder_dropout) of snuffy.py:225 and :110) in the epilogue of the one-pass GEMM:
+ *   C = M o act(A W^T + bias) (+ resid: the residual is NOT masked),  M[i, j] = 0 or 1 / (1 - dropout_p)
+ * M is the Philox keep-mask of snf_dropout_mask_f32(dropout_p, seed, offset, h = 1, n = m, k = n) -- element (i, j) of it whatever the tiling
+ * and whichever workgroup runs the epilogue (split-K included), regenerated in registers and never stored; the product is rounded before
+ * the residual is added, so the result is bit for bit (undropped result) * (mask tensor) (+ resid).  Two forms:
+ *   act = SNF_ACT_RELU, out_dtype = SNF_DT_BF16_HL, resid = NULL   the FFN hidden layer as its hl image (masked before the hi / lo split)
+ *   act = SNF_ACT_NONE, out_dtype = SNF_DT_F32 (resid nullable)    z = x + dropout(W2 hid + b2)
+ * anything else is SNF_EUNSUPPORTED.  dropout_p in [0, 1); 0 = the plain launch.  _ws_: with the split-K workspace of snf_gemm_hl_ws_bf16. */
+int snf_gemm_hl_dropout_bf16(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias, const float* resid,
+                             int64_t ldr, int64_t m, int n, int k, int act, void* c, int64_t ldc, int out_dtype, float dropout_p,
+                             uint64_t seed, uint64_t offset, snf_stream_t stream);
+int snf_gemm_hl_ws_dropout_bf16(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias, const float* resid,
+                                int64_t ldr, int64_t m, int n, int k, int act, void* c, int64_t ldc, int out_dtype, float dropout_p,
+                                uint64_t seed, uint64_t offset, void* workspace, size_t workspace_bytes, snf_stream_t stream);
+/* Its backward: snf_split_hl_colsum_f32 of M o x with the same mask M [m, k] regenerated from (dropout_p, seed, offset) in the same pass --
+ * the hl image of df = M o dz and its column sums, no [m, k] mask tensor. */
+int snf_split_hl_colsum_dropout_f32(const float* x, int64_t ldx, int64_t m, int k, const void* gate_hl, int64_t ldg, float dropout_p,
+                                    uint64_t seed, uint64_t offset, void* out_hl, int64_t ldo, float* partial, snf_stream_t stream);
 int snf_split_hl_f32(const float* x, int64_t ldx, int64_t m, int k, void* out_bf16, snf_stream_t stream);
 int snf_layernorm_rows_hl_f32(const float* x, int64_t n, int d, const int32_t* slot_map, const float* patch_rows,
                               const float* gamma, const float* beta, float eps, void* out_bf16, snf_stream_t stream);

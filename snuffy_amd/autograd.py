@@ -28,6 +28,9 @@ FUSED_X3_TRAINING = True
 X3_TRAIN_HL = True
 # ... and, in that chain, the ReLU mask of the FFN input gradient in the GEMM's epilogue (snf_gemm_hl_gated_bf16); False: gemm_hl + split pass
 X3_TRAIN_GATED_GEMM = True
+# ... and encoder dropout (snuffy.py:108,225,110) inside that chain: Philox masks regenerated in the FFN GEMMs' epilogues and in the dz split
+# pass, a [K, D] mask tensor for the attention output; False: a layer with encoder dropout on takes the generic autograd chain
+FUSED_X3_ENCODER_DROPOUT = True
 
 _ACT = {
     "relu": F.relu,
@@ -585,22 +588,44 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
             mask = ops.dropout_mask(h, n, k, drop[0], drop[1], drop[2], x2.device)         # the same mask as a tensor: the backward reads it
             if not in_kernel:
                 o = torch.bmm((p * mask).transpose(1, 2), v.reshape(n, h, dk).transpose(0, 1)).transpose(0, 1).reshape(k, d)
+        # encoder dropout (hl chain only, fused_layer0_x3_ok): one Philox state per site, drawn in the order A, H, Z after the attention's
+        # own draw; a site with p == 0 draws nothing.  A = after the attention output (snuffy.py:108), H = inside the FFN (:225), Z = after it (:110)
+        p_a, p_h, p_z = _encoder_dropout_ps(layer)
+        drop_a = (p_a,) + draw_dropout_state() if p_a > 0.0 else None
+        drop_h = (p_h,) + draw_dropout_state() if p_h > 0.0 else None
+        drop_z = (p_z,) + draw_dropout_state() if p_z > 0.0 else None
+        if not hl and (drop_a or drop_h or drop_z):
+            raise ops._ffi.SnuffyHipError("EncoderLayer0X3Fn: encoder dropout needs the one-pass (hl) chain; fused_layer0_x3_ok declines this shape")
+        layer.last_dropout_states = {"attn": drop, "A": drop_a, "H": drop_h, "Z": drop_z}
         delta = F.linear(o, wo, bo)
+        mask_a = None
+        if drop_a is not None:
+            mask_a = ops.dropout_mask(1, k, d, drop_a[0], drop_a[1], drop_a[2], x2.device)[0]   # [K, D]: the one mask that is a tensor
+            delta = delta * mask_a
         x_sel = xs + delta                                                             # snuffy.py:108 at the K rows
         xhat0_sel = xn3.index_select(0, sel)
         # LayerNorm_1 sees y = x with the K rows replaced: the image is re-normalised at those rows, every other row is shared
         if hl:
             ops.layernorm_rows_hl_patch_(xn3, sel, x_sel, None, eps=eps)
-            hid3 = ops.gemm_hl(xn3, fw["w1_hl"], fw["b1"], "relu", hl_out=True)        # [N, 2F] image
-            z = ops.gemm_hl(hid3, fw["w2_hl"], bb2.detach().float().contiguous(), resid=x2)
+            b2 = bb2.detach().float().contiguous()
+            if drop_h is not None:                                                     # mask and 1 / (1 - p) behind the ReLU, before the hi / lo split
+                hid3 = ops.gemm_hl_dropout(xn3, fw["w1_hl"], fw["b1"], drop_h, "relu", hl_out=True)
+            else:
+                hid3 = ops.gemm_hl(xn3, fw["w1_hl"], fw["b1"], "relu", hl_out=True)    # [N, 2F] image
+            if drop_z is not None:                                                     # z = x + M_Z o (hid W2^T + b2): the residual is not masked
+                z = ops.gemm_hl_dropout(hid3, fw["w2_hl"], b2, drop_z, resid=x2)
+            else:
+                z = ops.gemm_hl(hid3, fw["w2_hl"], b2, resid=x2)
         else:
             xn3.index_copy_(0, sel, ops.split3_rows(ops.layernorm_rows(x_sel, None, None, eps)))
             hid3 = ops.gemm_x3(xn3, fw["w1_3"], fw["b1"], "relu", split3=True)         # [N, 3F]
             z = ops.gemm_x3(hid3, fw["w2_3"], bb2.detach().float().contiguous(), resid=x2)  # x + f + b2: the residual rides in the epilogue
         z.index_add_(0, sel, delta)                                                    # snuffy.py:110,154-155
-        ctx.save_for_backward(sel, xhat0_sel, qv, kp, p, mask, o, xs, x_sel, hid3, g0, b0, g1, b1, wq, wv, wo, w1)
+        ctx.save_for_backward(sel, xhat0_sel, qv, kp, p, mask, o, xs, x_sel, hid3, g0, b0, g1, b1, wq, wv, wo, w1, mask_a)
         ctx.xn3, ctx.fw = xn3, fw       # xn3: written in place after the Q | V projection read it (outside the version check)
         ctx.h, ctx.eps, ctx.hl = h, eps, hl
+        ctx.scale_h = 1.0 / (1.0 - p_h) if drop_h is not None else None
+        ctx.drop_z = drop_z
         ctx.drop = drop if regen else None
         attn = (p * mask if mask is not None else p) if need_attn else None
         if attn is not None:
@@ -609,7 +634,7 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, _dattn):
-        sel, xhat0_sel, qv, kp, p, mask, o, xs, x_sel, hid3, g0, b0, g1, b1, wq, wv, wo, w1 = ctx.saved_tensors
+        sel, xhat0_sel, qv, kp, p, mask, o, xs, x_sel, hid3, g0, b0, g1, b1, wq, wv, wo, w1, mask_a = ctx.saved_tensors
         xn3, fw = ctx.xn3, ctx.fw
         d = xs.shape[1]
         hl = ctx.hl
@@ -619,7 +644,8 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
         dz = dz.float().contiguous()
         # ---- FFN: z = y + relu(xhat1 W1'^T + b1') W2^T + b2                                                  (snuffy.py:224-225)
         if hl:
-            dz3, db2 = ops.split_hl_colsum(dz)                                         # operand image + bias gradient, one pass
+            # operand image + bias gradient, one pass (encoder dropout: of df = M_Z o dz, the mask regenerated from its Philox state)
+            dz3, db2 = ops.split_hl_colsum(dz, dropout=ctx.drop_z)
             dw2 = ops.gemm_tn(dz3, hid3, d, f, hl=True)                                # [D, F]
             if X3_TRAIN_GATED_GEMM and 2 * f <= 8192:
                 # the ReLU mask (hi values of the output image) in the GEMM's epilogue, which writes the gated gradient as its hl image: no
@@ -650,9 +676,17 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
             del dhid3
             dhid_s, gate_s = dhid.index_select(0, sel), gate.index_select(0, sel)
             del dhid
+        if ctx.scale_h is not None:
+            # FFN dropout: the hi plane of the stored (dropped) hid3 is > 0 exactly where the element was kept behind an open ReLU, so the gate
+            # above selected the right elements; what is left of M_H is the scalar 1 / (1 - p), applied to the three small results
+            dw1f *= ctx.scale_h
+            db1f = db1f * ctx.scale_h
+            dhid_s = dhid_s * ctx.scale_h
         # ---- the K selected rows: y[S] = x_sel = xs + o Wo^T + bo; every other row of y is data               (snuffy.py:108,152-155)
         dyn_s = (dhid_s if gate_s is None else dhid_s * (gate_s > 0)) @ fw["w1f"]     # d loss / d xhat1[S]
         dy_s = ops.layernorm_rows_bwd(x_sel, dyn_s, None, eps, residual=dz.index_select(0, sel), want_param_grads=False)[0]
+        if mask_a is not None:
+            dy_s = dy_s * mask_a            # d loss / d (o Wo^T + bo); the residual path dz[S] went into the LayerNorm backward above, unmasked
         dbo = dy_s.sum(0)
         dwo = dy_s.t() @ o
         do = dy_s @ wo
@@ -696,9 +730,16 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
         return (None, None, None, None, dg0, db0, dg1, db1, dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo, dw1, db1f, dw2, db2)
 
 
+def _encoder_dropout_ps(layer):
+    """(p_A, p_H, p_Z) of a layer's three encoder-dropout sites (snuffy.py:108, 225, 110); all 0 in eval mode."""
+    if not layer.training:
+        return 0.0, 0.0, 0.0
+    return float(layer.sublayer[0].dropout.p), float(layer.feed_forward.dropout.p), float(layer.sublayer[1].dropout.p)
+
+
 def fused_layer0_x3_ok(x2, sel, layer, precision):
-    """EncoderLayer0X3Fn applies: fp32 with FP32_GEMM = "x3", the bag is data, ReLU FFN, no encoder dropout (attention dropout is
-    handled), shapes in the tile GEMM's domain; everything else keeps the generic autograd chain."""
+    """EncoderLayer0X3Fn applies: fp32 with FP32_GEMM = "x3", the bag is data, ReLU FFN, shapes in the tile GEMM's domain; encoder dropout
+    only on the one-pass (hl) branch (attention dropout is handled on both); everything else keeps the generic autograd chain."""
     if (not FUSED_X3_TRAINING or precision != "fp32" or SF.FP32_GEMM != "x3" or x2.requires_grad or sel.numel() == 0
             or torch.is_autocast_enabled() or x2.dtype != torch.float32 or not x2.is_contiguous()):
         return False
@@ -710,8 +751,11 @@ def fused_layer0_x3_ok(x2, sel, layer, precision):
         return False
     if f > 8192 or d > 8192:        # the backward's ops.split3_colsum runs over dhid [N, F] and dz [N, D]: k % 8 == 0, k <= 8192
         return False
-    if layer.training and (layer.sublayer[0].dropout.p > 0 or layer.sublayer[1].dropout.p > 0 or ff.dropout.p > 0):
-        return False
+    if any(p > 0 for p in _encoder_dropout_ps(layer)):
+        # the masks live in the epilogues of the one-pass GEMMs: the concatenated-K branch (and every shape below) declines
+        if not (FUSED_X3_ENCODER_DROPOUT and _x3_train_hl_ok(n, d, f) and ops.encoder_dropout_supported(n, d, f)
+                and all(p < 1 for p in _encoder_dropout_ps(layer))):
+            return False
     if any(t is None for t in (n0.weight, n0.bias, n1.weight, n1.bias, ff.w_1.bias, ff.w_2.bias) + tuple(l.bias for l in mha.linears)):
         return False
     return (ops.gemm_x3_supported(n, 2 * d, d) and ops.gemm_x3_supported(n, f, d) and ops.gemm_x3_supported(n, d, f)

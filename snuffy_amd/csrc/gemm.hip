@@ -28,6 +28,7 @@
 #include <stdlib.h>
 
 #include "mfma.h"
+#include "philox.h"
 
 namespace {
 
@@ -67,6 +68,9 @@ struct GemmParams {
     int64_t ldc2 = 0;
     float* stats_part = nullptr;
     int slots = 0;
+    // gemm_hl_kernel<.., DROP = true> (encoder dropout of a training step, snuffy.py:225,110): the epilogue multiplies act(acc + bias) by the Philox
+    // keep-mask of the [m, n] output (csrc/philox.h with h = 1: a function of (row, column) alone, whatever the tiling), before the residual
+    snf::DropoutState drop = {0u, 0u, 0u, 0u, 0u, 1.f};
 };
 constexpr int HL_SPLIT_MIN_STEPS = 8;   // a K part is at least this many 32-column steps
 constexpr int HL_SPLIT_MAX = 4;
@@ -574,9 +578,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams P) {
 // Register budget: the A-lo fragments are read into the A-hi registers while the second product (hi lo) is still issuing.
 // OUT: 0 bf16, 1 fp32, 3 the hl image of the fp32 result (operand of the next one-pass GEMM).
 // SPLIT (second launch of snf_gemm_hl_ws_bf16): the tiles of the last, partly filled round, one K part per workgroup (see GemmParams).
-template <int ACT, int OUT, bool SPLIT = false, bool GATE = false>
+// DROP (snf_gemm_hl_ws_dropout_bf16): the encoder-dropout mask in the epilogue (GemmParams::drop); with DROP = false the code is what it was
+// before the option existed.
+template <int ACT, int OUT, bool SPLIT = false, bool GATE = false, bool DROP = false>
 __global__ __launch_bounds__(512, 2) void gemm_hl_kernel(GemmParams P) {
     static_assert(!GATE || (OUT == 3 && ACT == SNF_ACT_NONE && !SPLIT), "gemm_hl: the gated form writes an hl image, no activation, no split");
+    static_assert(!DROP || (!GATE && (OUT == 1 || OUT == 3)), "gemm_hl: dropout goes with the fp32 and the hl-image outputs");
     constexpr int NI = 4, BN = 256;
     constexpr int ROWL = 128;                    // LDS row: hi(32) | lo(32) bf16
     constexpr int IMG = BM * ROWL;               // one operand's step image: 32 KiB
@@ -749,6 +756,19 @@ __global__ __launch_bounds__(512, 2) void gemm_hl_kernel(GemmParams P) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = activate<ACT>(acc[mi][2 * h + (e >> 2)][e & 3] + bv4[2 * h + (e >> 2)][e & 3]);
                 const int col = n0 + 32 * h;
+                if constexpr (DROP) {
+                    // mask element (row, col + e): one Philox call per 4 consecutive columns, indexed by the OUTPUT position alone
+                    const snf::philox_f4 m0 = snf::dropout_mask4(P.drop, 0, P.m, row, P.n, col);
+                    const snf::philox_f4 m1 = snf::dropout_mask4(P.drop, 0, P.m, row, P.n, col + 4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        v[e] *= m0[e];
+                        v[4 + e] *= m1[e];
+                    }
+                    // the product is rounded on its own (no fma with the residual below): bit for bit (undropped result) * (mask tensor)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(v[e]));
+                }
 #ifdef X3_NOSTORE
                 const bool ok = v[0] == 123.456f;
 #else
@@ -957,10 +977,13 @@ __global__ __launch_bounds__(512, 2) void gemm_hl_kernel(GemmParams P) {
     }
 }
 
-template <int ACT, int OUT>
+template <int ACT, int OUT, bool DROP = false>
 int launch_hl(const GemmParams& P, hipStream_t s) {
     constexpr int lds = 2 * 2 * BM * 128 + (((OUT == 1 || OUT == 3) && ACT != SNF_ACT_GELU && ACT != SNF_ACT_SELU) ? 8 * 4096 : 0);
-    auto kern = gemm_hl_kernel<ACT, OUT>;
+    auto kern = [] {
+        if constexpr (DROP) return gemm_hl_kernel<ACT, OUT, false, false, true>;
+        else return gemm_hl_kernel<ACT, OUT>;
+    }();
     static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
     if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "gemm_hl")) return rc;
     const int ntiles = P.tiles_m * P.tiles_n;
@@ -976,7 +999,10 @@ int launch_hl(const GemmParams& P, hipStream_t s) {
     int rc = snf::check_launch("gemm_hl_kernel");
     if (rc || P.split_cap < 2) return rc;
     // the last, partly filled round: every remainder tile on 2 .. 4 workgroups, a K range each (same grid: same tile -> XCD map)
-    auto kern2 = gemm_hl_kernel<ACT, OUT, true>;
+    auto kern2 = [] {
+        if constexpr (DROP) return gemm_hl_kernel<ACT, OUT, true, false, true>;
+        else return gemm_hl_kernel<ACT, OUT, true>;
+    }();
     static thread_local unsigned long long attr_set2_mask = 0;   // devices (bit = device id) that have the opt-in
     if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern2), lds, &attr_set2_mask, "gemm_hl")) return rc;
     hipLaunchKernelGGL(kern2, dim3(grid), dim3(512), lds, s, P);
@@ -1416,9 +1442,10 @@ extern "C" int snf_gemm_hl_resid_bf16(const void* a_hl, int64_t lda, const void*
     return snf_gemm_hl_ws_bf16(a_hl, lda, w_hl, ldw, bias, resid, ldr, m, n, k, act, c, ldc, out_dtype, nullptr, 0, stream);
 }
 
-extern "C" int snf_gemm_hl_ws_bf16(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias,
-                                   const float* resid, int64_t ldr, int64_t m, int n, int k, int act, void* c, int64_t ldc,
-                                   int out_dtype, void* workspace, size_t workspace_bytes, snf_stream_t stream) {
+namespace {
+int gemm_hl_ws_impl(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias, const float* resid, int64_t ldr,
+                    int64_t m, int n, int k, int act, void* c, int64_t ldc, int out_dtype, const snf::DropoutState* drop, void* workspace,
+                    size_t workspace_bytes, snf_stream_t stream) {
     SNF_REQUIRE(a_hl && w_hl && c, "snf_gemm_hl_bf16: null pointer");
     SNF_REQUIRE(m >= 1 && n >= 1 && k >= 1, "snf_gemm_hl_bf16: bad shape m=%lld n=%d k=%d", (long long)m, n, k);
     SNF_REQUIRE(act >= SNF_ACT_RELU && act <= SNF_ACT_NONE, "snf_gemm_hl_bf16: bad activation code %d", act);
@@ -1462,8 +1489,39 @@ extern "C" int snf_gemm_hl_ws_bf16(const void* a_hl, int64_t lda, const void* w_
         }
     }
     hipStream_t s = snf::as_stream(stream);
+    if (drop && drop->thresh) {
+        P.drop = *drop;
+        if (hl_out && act == SNF_ACT_RELU && !resid) return launch_hl<SNF_ACT_RELU, 3, true>(P, s);
+        if (out_dtype == SNF_DT_F32 && act == SNF_ACT_NONE) return launch_hl<SNF_ACT_NONE, 1, true>(P, s);
+        snf::set_error("snf_gemm_hl_dropout_bf16: dropout exists for act = relu with an hl-image output and for act = none with an fp32 "
+                       "output (got act %d, out_dtype %d)", act, out_dtype);
+        return SNF_EUNSUPPORTED;
+    }
     if (hl_out) return launch_hl_act<3>(P, s);
     return out_dtype == SNF_DT_F32 ? launch_hl_act<1>(P, s) : launch_hl_act<0>(P, s);
+}
+}  // namespace
+
+extern "C" int snf_gemm_hl_ws_bf16(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias,
+                                   const float* resid, int64_t ldr, int64_t m, int n, int k, int act, void* c, int64_t ldc,
+                                   int out_dtype, void* workspace, size_t workspace_bytes, snf_stream_t stream) {
+    return gemm_hl_ws_impl(a_hl, lda, w_hl, ldw, bias, resid, ldr, m, n, k, act, c, ldc, out_dtype, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int snf_gemm_hl_ws_dropout_bf16(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias,
+                                           const float* resid, int64_t ldr, int64_t m, int n, int k, int act, void* c, int64_t ldc,
+                                           int out_dtype, float dropout_p, uint64_t seed, uint64_t offset, void* workspace,
+                                           size_t workspace_bytes, snf_stream_t stream) {
+    SNF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "snf_gemm_hl_dropout_bf16: dropout_p=%f outside [0, 1)", dropout_p);
+    const snf::DropoutState st = snf::make_dropout(dropout_p, seed, offset);
+    return gemm_hl_ws_impl(a_hl, lda, w_hl, ldw, bias, resid, ldr, m, n, k, act, c, ldc, out_dtype, &st, workspace, workspace_bytes, stream);
+}
+
+extern "C" int snf_gemm_hl_dropout_bf16(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias,
+                                        const float* resid, int64_t ldr, int64_t m, int n, int k, int act, void* c, int64_t ldc,
+                                        int out_dtype, float dropout_p, uint64_t seed, uint64_t offset, snf_stream_t stream) {
+    return snf_gemm_hl_ws_dropout_bf16(a_hl, lda, w_hl, ldw, bias, resid, ldr, m, n, k, act, c, ldc, out_dtype, dropout_p, seed, offset,
+                                       nullptr, 0, stream);
 }
 
 extern "C" int snf_gemm_hl_gated_bf16(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const void* gate_hl, int64_t ldg, int64_t m,

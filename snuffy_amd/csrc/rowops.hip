@@ -665,6 +665,67 @@ __global__ __launch_bounds__(256) void split3_colsum_kernel(const float* __restr
     }
 }
 
+// split3_colsum_kernel<NCH, HL = true> of M o x, M the Philox keep-mask of the [m, k] matrix (philox.h with h = 1, the mask gemm_hl's dropout
+// epilogue applied to z = x + M o f in the forward): the backward's df = M o dz as its hl image plus its column sums, the mask regenerated
+// in registers -- a thread's 8 columns are two Philox groups.  Same row / column ownership, so the sums add up in the same order.
+template <int NCH>
+__global__ __launch_bounds__(256) void split_hl_colsum_dropout_kernel(const float* __restrict__ x, int64_t ldx, int64_t m, int k,
+                                                                      const unsigned short* __restrict__ gate, int64_t ldg,
+                                                                      snf::DropoutState st, unsigned short* __restrict__ out, int64_t ldo,
+                                                                      float* __restrict__ partial, int rows_per_block) {
+    float acc[NCH][8];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+    int64_t r1 = r0 + rows_per_block;
+    if (r1 > m) r1 = m;
+    for (int64_t row = r0; row < r1; ++row) {
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const int c = (j * 256 + threadIdx.x) * 8;
+            if (c < k) {
+                const float4 a = *reinterpret_cast<const float4*>(x + row * ldx + c);
+                const float4 b = *reinterpret_cast<const float4*>(x + row * ldx + c + 4);
+                const snf::philox_f4 m0 = snf::dropout_mask4(st, 0, m, row, k, c), m1 = snf::dropout_mask4(st, 0, m, row, k, c + 4);
+                float v[8] = {a.x * m0[0], a.y * m0[1], a.z * m0[2], a.w * m0[3], b.x * m1[0], b.y * m1[1], b.z * m1[2], b.w * m1[3]};
+                const int ci = 64 * (c >> 5) + (c & 31);   // position of the 8 columns' hi values inside an image row
+                if (gate) {
+                    const uint4 g = *reinterpret_cast<const uint4*>(gate + row * ldg + ci);
+                    const unsigned g4[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (!(__uint_as_float(g4[e] << 16) > 0.f)) v[2 * e] = 0.f;
+                        if (!(__uint_as_float(g4[e] & 0xffff0000u) > 0.f)) v[2 * e + 1] = 0.f;
+                    }
+                }
+                unsigned hi[4], lo[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    hi[e] = pack_bf16x2(v[2 * e], v[2 * e + 1]);
+                    lo[e] = pack_bf16x2(v[2 * e] - __uint_as_float(hi[e] << 16), v[2 * e + 1] - __uint_as_float(hi[e] & 0xffff0000u));
+                }
+                unsigned short* o = out + row * ldo + ci;
+                *reinterpret_cast<uint4*>(o) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+                *reinterpret_cast<uint4*>(o + 32) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[j][e] += v[e];
+            }
+        }
+    }
+    if (!partial) return;
+    float* po = partial + (int64_t)blockIdx.x * k;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c = (j * 256 + threadIdx.x) * 8;
+        if (c < k) {
+            *reinterpret_cast<float4*>(po + c) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+            *reinterpret_cast<float4*>(po + c + 4) = make_float4(acc[j][4], acc[j][5], acc[j][6], acc[j][7]);
+        }
+    }
+}
+
 // x [m, k] f32 (row pitch ldx) -> out [m, 2 k] bf16, interleaved: columns 32 c .. 32 c + 31 as [hi(32) | lo(32)] (k % 32 == 0)
 __global__ __launch_bounds__(256) void split_hl_kernel(const float* __restrict__ x, int64_t ldx, int64_t m, int k,
                                                        unsigned short* __restrict__ out) {
@@ -1612,6 +1673,32 @@ int snf_split_hl_colsum_f32(const float* x, int64_t ldx, int64_t m, int k, const
         default: hipLaunchKernelGGL((split3_colsum_kernel<4, true>), dim3(blocks), dim3(256), 0, s, x, ldx, m, k, g, ldg, o, ldo, (int64_t)0, partial, rpb); break;
     }
     return snf::check_launch("split3_colsum_kernel<hl>");
+}
+
+int snf_split_hl_colsum_dropout_f32(const float* x, int64_t ldx, int64_t m, int k, const void* gate_hl, int64_t ldg, float dropout_p,
+                                    uint64_t seed, uint64_t offset, void* out_hl, int64_t ldo, float* partial, snf_stream_t stream) {
+    SNF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "snf_split_hl_colsum_dropout_f32: dropout_p=%f outside [0, 1)", dropout_p);
+    if (!(dropout_p > 0.f)) return snf_split_hl_colsum_f32(x, ldx, m, k, gate_hl, ldg, out_hl, ldo, partial, stream);
+    SNF_REQUIRE(x && out_hl, "snf_split_hl_colsum_dropout_f32: null pointer");
+    SNF_REQUIRE(m >= 1 && k >= 32 && k % 32 == 0 && k <= 8192 && ldx >= k && ldx % 4 == 0 && ldo >= 2 * (int64_t)k && ldo % 8 == 0 &&
+                    (!gate_hl || (ldg >= 2 * (int64_t)k && ldg % 8 == 0)),
+                "snf_split_hl_colsum_dropout_f32: bad shape m=%lld k=%d ldx=%lld ldg=%lld ldo=%lld (k %% 32 == 0, k <= 8192, images of 2 k columns, 16-byte rows)",
+                (long long)m, k, (long long)ldx, (long long)ldg, (long long)ldo);
+    SNF_REQUIRE(aligned16(x) && aligned16(out_hl) && (!gate_hl || aligned16(gate_hl)) && (!partial || aligned16(partial)),
+                "snf_split_hl_colsum_dropout_f32: buffers must be 16-byte aligned");
+    const int blocks = snf_colsum_blocks(m);
+    const int rpb = (int)((m + blocks - 1) / blocks);
+    const int nch = (k + 2047) / 2048;
+    hipStream_t s = snf::as_stream(stream);
+    const snf::DropoutState st = snf::make_dropout(dropout_p, seed, offset);
+    const unsigned short* g = reinterpret_cast<const unsigned short*>(gate_hl);
+    unsigned short* o = reinterpret_cast<unsigned short*>(out_hl);
+    switch (nch) {
+        case 1: hipLaunchKernelGGL(split_hl_colsum_dropout_kernel<1>, dim3(blocks), dim3(256), 0, s, x, ldx, m, k, g, ldg, st, o, ldo, partial, rpb); break;
+        case 2: hipLaunchKernelGGL(split_hl_colsum_dropout_kernel<2>, dim3(blocks), dim3(256), 0, s, x, ldx, m, k, g, ldg, st, o, ldo, partial, rpb); break;
+        default: hipLaunchKernelGGL(split_hl_colsum_dropout_kernel<4>, dim3(blocks), dim3(256), 0, s, x, ldx, m, k, g, ldg, st, o, ldo, partial, rpb); break;
+    }
+    return snf::check_launch("split_hl_colsum_dropout_kernel");
 }
 
 int snf_fold_blocks(int r) {

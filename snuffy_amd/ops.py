@@ -1454,6 +1454,51 @@ def gemm_hl(a_hl, w_hl, bias=None, act="none", out_dtype=torch.float32, out=None
     return out
 
 
+def encoder_dropout_supported(n, d, f):
+    """Shapes the encoder-dropout kernels take (gemm_hl_dropout for the FFN of a bag [n, d] with f hidden columns, split_hl_colsum with
+    dropout over dz [n, d]): the one-pass GEMM's domain with hl rows on both sides, the column-sum pass's width."""
+    return d % 32 == 0 and f % 32 == 0 and d <= 8192 and hl_eligible(n, f, d) and hl_eligible(n, d, f)
+
+
+def gemm_hl_dropout(a_hl, w_hl, bias, dropout, act="none", hl_out=False, resid=None, out=None):
+    """gemm_hl with encoder dropout in the epilogue (snf_gemm_hl_ws_dropout_bf16): M o act(A W^T + bias) (+ resid, unmasked), M the Philox
+    keep-mask dropout_mask(1, m, n, *dropout) regenerated in registers; dropout = (p, seed, offset).  Two forms: act="relu" with hl_out
+    (the FFN hidden layer's image) and act="none" with an fp32 output (+ resid)."""
+    if a_hl.dtype != torch.bfloat16 or w_hl.dtype != torch.bfloat16:
+        raise TypeError("gemm_hl_dropout: operands must be bfloat16 hl images")
+    if (act, bool(hl_out)) not in (("relu", True), ("none", False)):
+        raise ValueError("gemm_hl_dropout: only relu -> hl image and none -> fp32 (+ resid) exist")
+    a_hl = _rows16(a_hl, "a_hl")
+    w_hl = _rows16(w_hl, "w_hl")
+    m, k2 = a_hl.shape
+    n = w_hl.shape[0]
+    if w_hl.shape[1] != k2 or k2 % 64 or (hl_out and n % 32):
+        raise ValueError("gemm_hl_dropout: images are %s and %s" % (tuple(a_hl.shape), tuple(w_hl.shape)))
+    if bias is not None:
+        bias = _req(bias, torch.float32, "bias", 1)
+    if out is None:
+        out = torch.empty(m, 2 * n, dtype=torch.bfloat16, device=a_hl.device) if hl_out else \
+            torch.empty(m, n, dtype=torch.float32, device=a_hl.device)
+    odt = DT_BF16_HL if hl_out else DT_F32
+    ldr = 0
+    if resid is not None:
+        if hl_out or resid.dtype != torch.float32 or tuple(resid.shape) != (m, n):
+            raise ValueError("gemm_hl_dropout: resid needs an fp32 [m, n] tensor and an fp32 output")
+        resid = _rows16(resid, "resid")
+        ldr = resid.stride(0)
+    p, seed, offset = dropout
+    lib = _ffi.load()
+    ws, ws_bytes = None, 0
+    if GEMM_HL_SPLITK:
+        ws_bytes = int(lib.snf_gemm_hl_ws_bytes(m, n, k2 // 2))
+        if ws_bytes:
+            ws = _hl_workspace(a_hl.device, ws_bytes)
+    check(lib.snf_gemm_hl_ws_dropout_bf16(_p(a_hl), a_hl.stride(0), _p(w_hl), w_hl.stride(0), _p(bias), _p(resid), ldr, m, n, k2 // 2,
+                                          ACT_CODES[act], _p(out), out.stride(0), odt, float(p), int(seed) & (2 ** 64 - 1),
+                                          int(offset) & (2 ** 64 - 1), _p(ws), ws_bytes, _stream()), "snf_gemm_hl_ws_dropout_bf16")
+    return out
+
+
 def gemm_hl_gated(a_hl, w_hl, gate_hl):
     """The hl image [m, 2 n] of (A W^T) o [gate > 0] in one pass (snf_gemm_hl_gated_bf16): the FFN input gradient behind its ReLU; gate_hl
     [m, 2 n] = the activation's own hl image (its hi values decide)."""
@@ -1553,10 +1598,12 @@ def split3_colsum(x, gate=None, out=None, col=0, want_colsum=True):
     return out, (part.sum(0) if part is not None else None)
 
 
-def split_hl_colsum(x, gate_hl=None, out=None, col=0, want_colsum=True):
+def split_hl_colsum(x, gate_hl=None, out=None, col=0, want_colsum=True, dropout=None):
     """split3_colsum writing the INTERLEAVED image ([hi(32) | lo(32)] per 32 columns, [m, 2 k]: operand of gemm_hl and of gemm_tn(hl=True));
     gate_hl [m, 2 k] bf16: the activation's own hl image (its hi values decide).  out / col: write the k columns at TRUE column col of
-    a wider image out [m, 2 w].  Returns (image, colsum [k] or None).  snf_split_hl_colsum_f32."""
+    a wider image out [m, 2 w].  Returns (image, colsum [k] or None).  snf_split_hl_colsum_f32.
+    dropout = (p, seed, offset): image and sums of M o x, M = dropout_mask(1, m, k, p, seed, offset) regenerated in the pass
+    (snf_split_hl_colsum_dropout_f32)."""
     if x.dtype != torch.float32:
         raise TypeError("split_hl_colsum: x must be float32")
     x = _rows16(x, "x")
@@ -1578,6 +1625,11 @@ def split_hl_colsum(x, gate_hl=None, out=None, col=0, want_colsum=True):
     lib = _ffi.load()
     part = torch.empty(lib.snf_colsum_blocks(m), k, dtype=torch.float32, device=x.device) if want_colsum else None
     dst = out if col == 0 else out[:, 2 * col:]
+    if dropout is not None:
+        check(lib.snf_split_hl_colsum_dropout_f32(_p(x), x.stride(0), m, k, _p(gate_hl), ldg, float(dropout[0]), int(dropout[1]) & (2 ** 64 - 1),
+                                                  int(dropout[2]) & (2 ** 64 - 1), _p(dst), out.stride(0), _p(part), _stream()),
+              "snf_split_hl_colsum_dropout_f32")
+        return out, (part.sum(0) if part is not None else None)
     check(lib.snf_split_hl_colsum_f32(_p(x), x.stride(0), m, k, _p(gate_hl), ldg, _p(dst), out.stride(0), _p(part), _stream()),
           "snf_split_hl_colsum_f32")
     return out, (part.sum(0) if part is not None else None)
