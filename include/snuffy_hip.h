@@ -188,6 +188,24 @@ int snf_split3_weight_f32(const float* w, int64_t ldw, int64_t m, int k, const f
 int snf_colsum_blocks(int64_t n);
 int snf_colsum_fused(const void* src, int src_dtype, int64_t n, int d, const float* row_weight, int64_t weight_stride,
                      const void* gate_bf16, void* dst_bf16, float* partial, snf_stream_t stream);
+/* Encoder dropout of the bf16 training chain (snuffy.py:225, 110) outside a GEMM epilogue.  M = the Philox keep-mask of the matrix
+ * (snf_dropout_mask_f32 with h = 1 and the matrix's rows / columns), regenerated in registers, never stored; dropout_p in [0, 1).
+ *   snf_dropout_rows_bf16              x[i, c] = bf16(float(x[i, c]) * M[i, c]) in place, x bf16 [m, n] with row pitch ldx (n % 8 == 0,
+ *                                      16-byte rows): the FFN hidden layer behind a library GEMM.  dropout_p == 0: nothing is launched.
+ *   snf_residual_assemble_dropout_f32  z_out = x + M o (float(add_bf16) + add_bias) (+ delta_rows[slot_map[i]] where slot_map[i] >= 0) in one
+ *                                      launch (x, z_out f32 [n, d], add_bf16 bf16 [n, d], add_bias f32 [d] nullable, slot_map int32 [n]
+ *                                      nullable, d % 4 == 0).  Every step is rounded on its own, in this order: t = add_bf16 + add_bias,
+ *                                      t = t * m, z = x + t, z = z + delta.  dropout_p == 0: z = ((x + add_bf16) + add_bias) + delta, the
+ *                                      order of snf_ln_mean_head_f32's z_out.
+ *   snf_colsum_fused_dropout           snf_colsum_fused of M o src without row weight and gate: dst_bf16 = bf16(src o M) (nullable) and the
+ *                                      partial column sums (of the rounded values when dst is given) -- the backward of the line above:
+ *                                      df = M o dz as the operand of the weight / input gradient GEMMs, and db2.  dropout_p == 0 = snf_colsum_fused. */
+int snf_dropout_rows_bf16(void* x, int64_t ldx, int64_t m, int n, float dropout_p, uint64_t seed, uint64_t offset, snf_stream_t stream);
+int snf_residual_assemble_dropout_f32(const float* x, int64_t n, int d, const void* add_bf16, const float* add_bias,
+                                      const int32_t* slot_map, const float* delta_rows, float dropout_p, uint64_t seed, uint64_t offset,
+                                      float* z_out, snf_stream_t stream);
+int snf_colsum_fused_dropout(const void* src, int src_dtype, int64_t n, int d, float dropout_p, uint64_t seed, uint64_t offset,
+                             void* dst_bf16, float* partial, snf_stream_t stream);
 /* The backward of an fp32-class training step (train.py:259 through snuffy.py:187-190, 224-225) needs each gradient matrix as a split
  * image (operand of the next GEMM and of the weight-gradient contractions) AND its column sums (the bias gradient), the FFN one behind
  * the ReLU mask: one pass.   v = x[i, c] (f32, row pitch ldx) ; v = 0 where gate_bf16[i, c] <= 0 (nullable; row pitch ldg: the hi
@@ -407,6 +425,14 @@ int snf_sparse_attn_dkp_f32(const float* ds, const float* q, int64_t n, int k, i
  * --------------------------------------------------------------------------------------------------------- */
 int snf_gemm_bf16(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, int64_t m, int n, int k,
                   int act, void* c, int64_t ldc, int out_dtype, int tile_n, snf_stream_t stream);
+/* Encoder dropout inside the FFN of a bf16 training step (nn.Dropout(encoder_dropout) of snuffy.py:225) in the epilogue of snf_gemm_bf16:
+ *   C = bf16(M o relu(A W^T + bias)),  M[i, j] = 0 or 1 / (1 - dropout_p)
+ * M is the Philox keep-mask of snf_dropout_mask_f32(dropout_p, seed, offset, h = 1, n = m, k = n), element (i, j) of it whatever the
+ * tiling, regenerated in registers and applied to the fp32 value before the single bf16 rounding.  The one form that exists is
+ * act = SNF_ACT_RELU with out_dtype = SNF_DT_BF16; anything else is SNF_EUNSUPPORTED.  dropout_p in [0, 1); 0 = the plain launch. */
+int snf_gemm_bf16_dropout(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, int64_t m, int n, int k, int act,
+                          void* c, int64_t ldc, int out_dtype, int tile_n, float dropout_p, uint64_t seed, uint64_t offset,
+                          snf_stream_t stream);
 /* fp32 output with a residual in the epilogue: c = act(a w^T + bias) + resid [m, ldr] -- z = x + W2 act(W1 LN(y)) of snuffy.py:110 for
  * bags too small for the one-pass kernel (round 6; snf_gemm_hl_resid_bf16 is the large-bag twin) */
 int snf_gemm_bf16_resid_f32(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, const float* resid, int64_t ldr,

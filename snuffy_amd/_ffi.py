@@ -147,6 +147,12 @@ SIGNATURES = {
     "snf_split_hl_colsum_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "snf_gemm_hl_ws_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
                                     c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p]),
+    "snf_gemm_bf16_dropout": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64,
+                                      c_int, c_int, c_float, c_uint64, c_uint64, c_void_p]),
+    "snf_dropout_rows_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int, c_float, c_uint64, c_uint64, c_void_p]),
+    "snf_residual_assemble_dropout_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_uint64,
+                                                  c_uint64, c_void_p, c_void_p]),
+    "snf_colsum_fused_dropout": (c_int, [c_void_p, c_int, c_int64, c_int, c_float, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "snf_gemm_hl_dropout_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
                                          c_void_p, c_int64, c_int, c_float, c_uint64, c_uint64, c_void_p]),
     "snf_gemm_hl_ws_dropout_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,

@@ -21,6 +21,10 @@ from . import ops
 # bf16 training: the first encoder layer as one hand-ordered forward / backward chain (EncoderLayer0Bf16Fn) instead of the generic
 # autograd graph; False keeps the generic chain everywhere (tests compare the two)
 FUSED_BF16_TRAINING = True
+# ... and encoder dropout (snuffy.py:108,225,110) inside that chain: the same Philox masks as the fp32-class chain below (one seed gives both
+# chains the same masks), regenerated in the FFN-in GEMM's epilogue or in one in-place pass behind the library GEMM, in a one-launch assembly
+# of z and in the backward's dz pass; False: a layer with encoder dropout on takes the generic autograd chain (torch's generator)
+FUSED_BF16_ENCODER_DROPOUT = True
 # fp32 training: the same for the fp32-class arithmetic (EncoderLayer0X3Fn, round 5)
 FUSED_X3_TRAINING = True
 # ... on the one-pass kernels (round 6): activations and gradients as interleaved hl images (4 bytes per element instead of the 6 of
@@ -343,7 +347,12 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
     activation in the GEMM epilogue).  Backward: dz -> FFN weight gradients (three [N, .] GEMMs) -> the K selected rows
     through LayerNorm 1 / the output projection -> MFMA attention backward -> Q|V weight gradients; the folded-weight
     gradients are unfolded into (W, b, gamma, beta) at the end.  Replaces ~150 autograd nodes (casts, adds, reductions:
-    2.6 ms of a 5.4 ms step at config B) by 9 large kernels and a handful of [K, D] / [4D, D] ones."""
+    2.6 ms of a 5.4 ms step at config B) by 9 large kernels and a handful of [K, D] / [4D, D] ones.
+
+    Encoder dropout (fused_layer0_train_ok): one Philox state per site with p > 0, drawn in the order A, H, Z after the attention's own
+    draw, exactly as EncoderLayer0X3Fn does (layer.last_dropout_states).  A: delta [K, D] times a mask tensor.  H: hid = bf16(M_H o relu(.)),
+    the mask in the GEMM's epilogue or in one in-place pass (ops.linear_bf16_dropout).  Z: z = x + M_Z o (zb + b2) (+ delta) in one assembly
+    launch; its backward regenerates M_Z in the dz pass.  A site with p == 0 draws and launches nothing new."""
 
     @staticmethod
     def forward(ctx, x2, sel, layer, need_attn, g0, b0, g1, b1, wq, bq, wk, bk, wv, bv, wo, bo, w1, bb1, w2, bb2):
@@ -364,15 +373,33 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
         p_drop = mha.dropout.p if layer.training else 0.0
         drop = (float(p_drop),) + draw_dropout_state() if p_drop > 0.0 else None
         o, attn, lse = ops.sparse_attn_fwd_mfma(q, v, kp, n, h, need_attn=need_attn, need_lse=True, dropout=drop)
+        # encoder dropout: A = after the attention output (snuffy.py:108), H = inside the FFN (:225), Z = after it (:110)
+        p_a, p_h, p_z = _encoder_dropout_ps(layer)
+        drop_a = (p_a,) + draw_dropout_state() if p_a > 0.0 else None
+        drop_h = (p_h,) + draw_dropout_state() if p_h > 0.0 else None
+        drop_z = (p_z,) + draw_dropout_state() if p_z > 0.0 else None
+        layer.last_dropout_states = {"attn": drop, "A": drop_a, "H": drop_h, "Z": drop_z}
         delta = torch.addmm(bo, o, wo.t())
+        mask_a = None
+        if drop_a is not None:
+            mask_a = ops.dropout_mask(1, sel.numel(), d, drop_a[0], drop_a[1], drop_a[2], x2.device)[0]   # [K, D]: the one mask that is a tensor
+            delta = delta * mask_a
         x_sel = xs + delta
         xhat0_sel = xhat.index_select(0, sel)
         ops.layernorm_rows(x_sel, None, None, eps, out=xhat, out_row_idx=sel)
-        hid = ops.linear_bf16(xhat, fw["w1"], fw["b1"], fw["b1h"], "relu")
+        if drop_h is not None:                                                         # hid = bf16(M_H o relu(xhat W1'^T + b1'))
+            hid = ops.linear_bf16_dropout(xhat, fw["w1"], fw["b1"], fw["b1h"], drop_h)
+        else:
+            hid = ops.linear_bf16(xhat, fw["w1"], fw["b1"], fw["b1h"], "relu")
         zb = ops.linear_bf16(hid, fw["w2"])
-        z = SF.materialize(SF.Parts(x2, add_bf16=zb, add_bias=bb2, slot=slot, delta=delta))
+        if drop_z is not None:                                                         # z = x + M_Z o (zb + b2) (+ delta[slot]): one launch
+            z = ops.residual_assemble_dropout(x2, zb, bb2.detach(), slot, delta, drop_z)
+        else:
+            z = SF.materialize(SF.Parts(x2, add_bf16=zb, add_bias=bb2, slot=slot, delta=delta))
         ctx.save_for_backward(sel, xhat0_sel, qv, kp, lse, o, xs, x_sel, hid, g0, b0, g1, b1, wq, wk, wv, wo, w1,
-                              fw["w1"], fw["w2"])
+                              fw["w1"], fw["w2"], mask_a)
+        ctx.scale_h = 1.0 / (1.0 - p_h) if drop_h is not None else None
+        ctx.drop_z = drop_z
         ctx.xhat = xhat          # read-only in backward; outside save_for_backward because the forward wrote rows S in place after the
         #                          Q|V projection had read it (the version check would reject it)
         ctx.h, ctx.eps, ctx.drop = h, eps, drop
@@ -381,22 +408,38 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, _dattn):
-        (sel, xhat0_sel, qv, kp, lse, o, xs, x_sel, hid, g0, b0, g1, b1, wq, wk, wv, wo, w1, w1f, w2f) = ctx.saved_tensors
+        (sel, xhat0_sel, qv, kp, lse, o, xs, x_sel, hid, g0, b0, g1, b1, wq, wk, wv, wo, w1, w1f, w2f, mask_a) = ctx.saved_tensors
         xhat = ctx.xhat
         n, d = xhat.shape
         h, eps = ctx.h, ctx.eps
         f32 = torch.float32
         dz = dz.float().contiguous()
         # ---- FFN: z = y + act(xhat1 W1'^T + b1') W2^T + b2                                                (snuffy.py:224-225)
-        db2, dz16 = ops.colsum_fused(dz, want_bf16=True)                              # bias gradient + the GEMM operand, one pass
+        # bias gradient + the GEMM operand, one pass (encoder dropout: of df = M_Z o dz, the mask regenerated from its Philox state)
+        db2, dz16 = ops.colsum_fused(dz, want_bf16=True, dropout=ctx.drop_z)
         dw2 = _tn_mm(dz16, hid)                                                        # [D, F]
         dhid = torch.mm(dz16, w2f)                                                   # [N, F] bf16
         db1f, _ = ops.colsum_fused(dhid, gate=hid, inplace=True)                     # ReLU mask from the output + bias gradient
         dw1f = _tn_mm(dhid, xhat)                                                     # [F, D] gradient of the FOLDED weight
         # ---- the K selected rows: y[S] = x_sel = xs + o Wo^T + bo; every other row of y is data             (snuffy.py:108,152-155)
         dyn_s = torch.mm(dhid.index_select(0, sel), w1f, out_dtype=f32)              # d loss / d xhat1[S] (bf16 operands as they are)
+        if ctx.scale_h is not None:
+            # FFN dropout needs no kernel of its own here.  d hid / d pre = M_H o [pre > 0], and M_H is 0 or s = 1 / (1 - p) > 1.  The gate
+            # above is the stored, already dropped hid, and that is > 0 exactly where the element was kept behind an open ReLU:
+            #   dropped or closed: the stored value is 0 * s or s * 0 = 0;
+            #   kept and open: the undropped value u > 0 is a bf16 number (library GEMM + pass) or the fp32 relu(acc + b) (GEMM epilogue).
+            #     u * 1 = u is exact, s > 1 and rounding is monotonic, so fl32(u * s) >= u; rounding to bf16 is monotonic too, so
+            #     bf16(fl32(u * s)) >= bf16(u), which is u itself in the first form and the undropped chain's stored value in the second.
+            #     A positive bf16 value times s therefore never rounds to zero: the gate stays open wherever the undropped chain's is.
+            #     (Nothing flushes denormals on the way: the fp32 product keeps them, the bf16 rounding is integer arithmetic.)
+            # What is left of M_H is the scalar s on the three small results.
+            dw1f *= ctx.scale_h
+            db1f = db1f * ctx.scale_h
+            dyn_s = dyn_s * ctx.scale_h
         # dy[S] = dz[S] + LayerNorm-1 backward of dyn_s at the rows x_sel (affine folded away): one kernel
         dy_s, _, _, _ = ops.layernorm_rows_bwd(x_sel, dyn_s, None, eps, residual=dz.index_select(0, sel), want_param_grads=False)
+        if mask_a is not None:
+            dy_s = dy_s * mask_a            # d loss / d (o Wo^T + bo); the residual path dz[S] went into the LayerNorm backward above, unmasked
         dbo = dy_s.sum(0)
         dwo = dy_s.t() @ o
         do = dy_s @ wo
@@ -432,15 +475,13 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
         return (None, None, None, None, dg0, db0, dg1, db1, dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo, dw1, db1f, dw2, db2)
 
 
-def fused_layer0_shape_ok(layer, n, d, k=None):
-    """Settings / shapes EncoderLayer0Bf16Fn covers (k = number of selected rows; default: the layer's Lambda capped by n)."""
+def _fused_layer0_base_ok(layer, n, d, k=None):
+    """fused_layer0_shape_ok without its word on encoder dropout."""
     if not FUSED_BF16_TRAINING:
         return False
     mha, ff = layer.self_attn, layer.feed_forward
     n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
     if ff.activation_name != "relu" or n0.eps != n1.eps or d % mha.h:
-        return False
-    if layer.training and (layer.sublayer[0].dropout.p > 0 or layer.sublayer[1].dropout.p > 0 or ff.dropout.p > 0):
         return False
     if k is None:
         k = min(int(layer.big_lambda), n)
@@ -449,12 +490,29 @@ def fused_layer0_shape_ok(layer, n, d, k=None):
             and ops.mfma_attn_bwd_supported(k, dk) and all(p.requires_grad for p in layer.parameters()))
 
 
+def fused_layer0_shape_ok(layer, n, d, k=None):
+    """Settings / shapes the dropout-free EncoderLayer0Bf16Fn covers (k = number of selected rows; default: the layer's Lambda capped
+    by n).  A train-mode layer with encoder dropout is declined here; fused_layer0_train_ok is the predicate that admits it."""
+    if layer.training and (layer.sublayer[0].dropout.p > 0 or layer.sublayer[1].dropout.p > 0 or layer.feed_forward.dropout.p > 0):
+        return False
+    return _fused_layer0_base_ok(layer, n, d, k)
+
+
+def fused_layer0_train_ok(layer, n, d, k=None):
+    """EncoderLayer0Bf16Fn takes the layer: the dropout-free chain's settings / shapes, or -- with FUSED_BF16_ENCODER_DROPOUT -- the same
+    with the three encoder-dropout p's anywhere in [0, 1) and shapes the dropout kernels take."""
+    if fused_layer0_shape_ok(layer, n, d, k):
+        return True
+    return (FUSED_BF16_ENCODER_DROPOUT and all(0.0 <= p < 1.0 for p in _encoder_dropout_ps(layer)) and _fused_layer0_base_ok(layer, n, d, k)
+            and ops.bf16_encoder_dropout_supported(n, d, layer.feed_forward.w_1.weight.shape[0]))
+
+
 def fused_layer0_ok(x2, sel, layer, precision):
     """The first-layer chain applies: bf16, the bag is data (no gradient flows into x2), supported shape / settings;
     everything else keeps the generic autograd chain below."""
     if precision != "bf16" or x2.requires_grad or sel.numel() == 0:
         return False
-    return fused_layer0_shape_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
+    return fused_layer0_train_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
 
 
 def _x3_train_weights(layer, hl=False):

@@ -70,6 +70,8 @@ struct GemmParams {
     int slots = 0;
     // gemm_hl_kernel<.., DROP = true> (encoder dropout of a training step, snuffy.py:225,110): the epilogue multiplies act(acc + bias) by the Philox
     // keep-mask of the [m, n] output (csrc/philox.h with h = 1: a function of (row, column) alone, whatever the tiling), before the residual
+    // gemm_bf16_kernel<.., DROP = true> (snf_gemm_bf16_dropout, the bf16 chain's FFN hidden layer): the same mask on relu(acc + bias) in fp32,
+    // before the one bf16 rounding
     snf::DropoutState drop = {0u, 0u, 0u, 0u, 0u, 1.f};
 };
 constexpr int HL_SPLIT_MIN_STEPS = 8;   // a K part is at least this many 32-column steps
@@ -121,8 +123,11 @@ __device__ __forceinline__ float activate(float v) {
 // again) -> 4 x 2 waves of 64 x 64.  A step of the 128 x 32 wave tile reads 8 + 2 KiB of fragments per wave (80 KiB per workgroup), the 64 x 64
 // one 4 + 4 KiB for the same 16 MFMAs: measured -4 % on config A's FFN output projection (85.6 -> 82.5 us), +1.6 % on its bag, level on the
 // ViT shapes -- the 128-wide K loop is not LDS-read bound either; like the 256-wide one it runs at the workgroup's LDS-DMA rate.
-template <int NI, int ACT, int OUT, int EPI = 0, int MI = 8>
+// DROP (snf_gemm_bf16_dropout): the encoder-dropout mask of the FFN hidden layer in the epilogue (GemmParams::drop), ReLU -> bf16 only; with
+// DROP = false the code is what it was.
+template <int NI, int ACT, int OUT, int EPI = 0, int MI = 8, bool DROP = false>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams P) {
+    static_assert(!DROP || (ACT == SNF_ACT_RELU && OUT == 0 && EPI == 0), "gemm_bf16: dropout goes with the ReLU -> bf16 form");
     static_assert(MI == 8 || (MI == 4 && NI == 4 && EPI != 1), "gemm_bf16: wave tiles are 128 x 16 NI or 64 x 64");
     constexpr int WC = MI == 8 ? 4 : 2;        // wave columns (wave rows: 8 / WC)
     constexpr int RW = 16 * MI;                // rows per wave
@@ -346,6 +351,17 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams P) {
                     for (int e = 0; e < 8; ++e) v[e] = activate<ACT>(acc[mi][2 * h + (e >> 2)][e & 3] + bv4[2 * h + (e >> 2)][e & 3]);
                 }
                 const int col = n0 + 32 * h;
+                if constexpr (DROP) {
+                    // mask element (row, col + e), indexed by the OUTPUT position alone (one Philox call per 4 consecutive columns); applied
+                    // to the fp32 value: the result is rounded to bf16 once, below
+                    const snf::philox_f4 m0 = snf::dropout_mask4(P.drop, 0, P.m, row, P.n, col);
+                    const snf::philox_f4 m1 = snf::dropout_mask4(P.drop, 0, P.m, row, P.n, col + 4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        v[e] *= m0[e];
+                        v[4 + e] *= m1[e];
+                    }
+                }
 #ifdef SNF_GEMM_NOSTORE   // timing ablation: no epilogue stores (and, with them, no epilogue arithmetic); results wrong
                 const bool ok = P.k < 0 && row < P.m && col + 8 <= P.n;
 #else
@@ -1034,11 +1050,14 @@ int launch_hl_act(const GemmParams& P, hipStream_t s) {
     }
 }
 
-template <int NI, int ACT, int OUT, int EPI = 0, int MI = 8>
+template <int NI, int ACT, int OUT, int EPI = 0, int MI = 8, bool DROP = false>
 int launch(const GemmParams& P, hipStream_t s) {
     constexpr int lds = NBUF * (A_BYTES + (MI == 8 ? 64 : 32) * NI * ROWB) +
                         ((EPI == 2 || (OUT == 0 && NI == 4 && ACT != SNF_ACT_GELU && ACT != SNF_ACT_SELU)) ? 8 * 4096 : 0);
-    auto kern = gemm_bf16_kernel<NI, ACT, OUT, EPI, MI>;
+    auto kern = [] {
+        if constexpr (DROP) return gemm_bf16_kernel<NI, ACT, OUT, EPI, MI, true>;
+        else return gemm_bf16_kernel<NI, ACT, OUT, EPI, MI>;
+    }();
     static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
     if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "gemm_bf16")) return rc;
     const int ntiles = P.tiles_m * P.tiles_n;
@@ -1054,12 +1073,12 @@ int launch(const GemmParams& P, hipStream_t s) {
 #define SNF_GEMM_128_MI4 1   // 128-wide tiles: 1 = 4 x 2 waves of 64 x 64 (round 6), 0 = 2 x 4 waves of 128 x 32 (dev builds, A / B)
 #endif
 // NI == 2 names the 128-wide tile at the call sites; the instantiation behind it is the 64 x 64 wave layout
-template <int NI, int ACT, int OUT, int EPI = 0>
+template <int NI, int ACT, int OUT, int EPI = 0, bool DROP = false>
 int launch_tile(const GemmParams& P, hipStream_t s) {
     if constexpr (NI == 2 && SNF_GEMM_128_MI4)
-        return launch<4, ACT, OUT, EPI, 4>(P, s);
+        return launch<4, ACT, OUT, EPI, 4, DROP>(P, s);
     else
-        return launch<NI, ACT, OUT, EPI>(P, s);
+        return launch<NI, ACT, OUT, EPI, 8, DROP>(P, s);
 }
 
 template <int NI, int OUT>
@@ -1264,7 +1283,8 @@ int snf::skinny_linear_x3_kpfrag(const float* x, int64_t ldx, const float* w, in
 }
 
 static int gemm_bf16_impl(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, const float* resid, int64_t ldr,
-                          int64_t m, int n, int k, int act, void* c, int64_t ldc, int out_dtype, int tile_n, snf_stream_t stream);
+                          int64_t m, int n, int k, int act, void* c, int64_t ldc, int out_dtype, int tile_n, snf_stream_t stream,
+                          const snf::DropoutState* drop = nullptr);
 extern "C" int snf_gemm_bf16(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, int64_t m, int n,
                              int k, int act, void* c, int64_t ldc, int out_dtype, int tile_n, snf_stream_t stream) {
     return gemm_bf16_impl(a, lda, w, ldw, bias, nullptr, 0, m, n, k, act, c, ldc, out_dtype, tile_n, stream);
@@ -1275,8 +1295,23 @@ extern "C" int snf_gemm_bf16_resid_f32(const void* a, int64_t lda, const void* w
     SNF_REQUIRE(resid && ldr >= n && ldr % 4 == 0 && reinterpret_cast<uintptr_t>(resid) % 16 == 0, "snf_gemm_bf16_resid_f32: resid [m, ldr] f32, 16-byte aligned rows");
     return gemm_bf16_impl(a, lda, w, ldw, bias, resid, ldr, m, n, k, act, c, ldc, SNF_DT_F32, tile_n, stream);
 }
+// Encoder dropout inside the FFN of a bf16 training step (snuffy.py:225): C = bf16(M o relu(A W^T + bias)), M the Philox keep-mask of the
+// [m, n] output regenerated in the epilogue.  The one form that exists is ReLU -> bf16; dropout_p == 0 is the plain launch.
+extern "C" int snf_gemm_bf16_dropout(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, int64_t m, int n, int k,
+                                     int act, void* c, int64_t ldc, int out_dtype, int tile_n, float dropout_p, uint64_t seed,
+                                     uint64_t offset, snf_stream_t stream) {
+    SNF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "snf_gemm_bf16_dropout: dropout_p=%f outside [0, 1)", dropout_p);
+    if (act != SNF_ACT_RELU || out_dtype != SNF_DT_BF16) {
+        snf::set_error("snf_gemm_bf16_dropout: only act = relu with a bf16 output exists (act %d, out_dtype %d)", act, out_dtype);
+        return SNF_EUNSUPPORTED;
+    }
+    if (!(dropout_p > 0.f)) return gemm_bf16_impl(a, lda, w, ldw, bias, nullptr, 0, m, n, k, act, c, ldc, out_dtype, tile_n, stream);
+    const snf::DropoutState st = snf::make_dropout(dropout_p, seed, offset);
+    return gemm_bf16_impl(a, lda, w, ldw, bias, nullptr, 0, m, n, k, act, c, ldc, out_dtype, tile_n, stream, &st);
+}
 static int gemm_bf16_impl(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, const float* resid, int64_t ldr,
-                          int64_t m, int n, int k, int act, void* c, int64_t ldc, int out_dtype, int tile_n, snf_stream_t stream) {
+                          int64_t m, int n, int k, int act, void* c, int64_t ldc, int out_dtype, int tile_n, snf_stream_t stream,
+                          const snf::DropoutState* drop) {
     SNF_REQUIRE(a && w && c, "snf_gemm_bf16: null pointer");
     SNF_REQUIRE(m >= 1 && n >= 1 && k >= 1, "snf_gemm_bf16: bad shape m=%lld n=%d k=%d", (long long)m, n, k);
     SNF_REQUIRE(act >= SNF_ACT_RELU && act <= SNF_ACT_NONE, "snf_gemm_bf16: bad activation code %d", act);
@@ -1314,6 +1349,10 @@ static int gemm_bf16_impl(const void* a, int64_t lda, const void* w, int64_t ldw
     if (const char* e = getenv("SNF_GEMM_TRACE_PTR")) P.trace = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0));
 #endif
     hipStream_t s = snf::as_stream(stream);
+    if (drop) {   // snf_gemm_bf16_dropout has checked the form: ReLU -> bf16
+        P.drop = *drop;
+        return tile_n == 256 ? launch_tile<4, SNF_ACT_RELU, 0, 0, true>(P, s) : launch_tile<2, SNF_ACT_RELU, 0, 0, true>(P, s);
+    }
     if (out_dtype == SNF_DT_BF16_SPLIT3) return tile_n == 256 ? launch_act<4, 2>(P, s) : launch_act<2, 2>(P, s);
     if (out_dtype == SNF_DT_BF16_HL) return tile_n == 256 ? launch_act<4, 3>(P, s) : launch_act<2, 3>(P, s);
     if (tile_n == 256) return out_dtype == SNF_DT_F32 ? launch_act<4, 1>(P, s) : launch_act<4, 0>(P, s);

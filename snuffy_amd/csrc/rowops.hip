@@ -726,6 +726,146 @@ __global__ __launch_bounds__(256) void split_hl_colsum_dropout_kernel(const floa
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Encoder dropout of the bf16 training chain (autograd.EncoderLayer0Bf16Fn; reference snuffy.py:225, 110).  M is the Philox keep-mask of
+// the matrix (philox.h with h = 1, element (row, column): a function of the position alone), regenerated in registers, never stored.
+// ---------------------------------------------------------------------------------------------------------------
+// x[i, c] = bf16(float(x[i, c]) * M[i, c]) in place over a bf16 [m, n] matrix with row pitch ldx: the FFN hidden layer behind a library
+// GEMM.  A lane moves 8 bf16 (16 bytes) = two Philox groups; no LDS, no barriers.
+__global__ __launch_bounds__(256) void dropout_rows_bf16_kernel(unsigned short* __restrict__ x, int64_t ldx, int64_t m, int n,
+                                                                snf::DropoutState st) {
+    const int gpr = n >> 3;                                  // 8-column groups per row
+    const int64_t total = m * gpr;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / gpr;
+        const int c = (int)(i - row * gpr) * 8;
+        unsigned short* px = x + row * ldx + c;
+        const uint4 u = *reinterpret_cast<const uint4*>(px);
+        const snf::philox_f4 m0 = snf::dropout_mask4(st, 0, m, row, n, c), m1 = snf::dropout_mask4(st, 0, m, row, n, c + 4);
+        const unsigned w4[4] = {u.x, u.y, u.z, u.w};
+        const float mk[8] = {m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+        unsigned o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            o[e] = pack_bf16x2(__uint_as_float(w4[e] << 16) * mk[2 * e], __uint_as_float(w4[e] & 0xffff0000u) * mk[2 * e + 1]);
+        *reinterpret_cast<uint4*>(px) = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// z = x + M o (float(zb) + b2) (+ delta[slot] at the selected rows) in one launch: the residual stream behind the FFN with its dropout
+// (snuffy.py:110).  The order is fixed, every step rounded on its own (no fma contraction of the product with the residual):
+//   t = zb + b2;  t = t * m;  z = x + t;  z = z + delta[slot].   DROP = false (dropout_p == 0): the order of ln_colsum_kernel's assembly,
+//   z = ((x + zb) + b2) + delta[slot], which is what functional.materialize returns.
+// A lane owns 4 consecutive columns = one Philox group.
+template <bool DROP>
+__global__ __launch_bounds__(256) void residual_assemble_dropout_kernel(const float* __restrict__ x, int64_t n, int d,
+                                                                        const unsigned short* __restrict__ add_bf16,
+                                                                        const float* __restrict__ add_bias,
+                                                                        const int32_t* __restrict__ slot_map,
+                                                                        const float* __restrict__ delta_rows, snf::DropoutState st,
+                                                                        float* __restrict__ z_out) {
+    const int gpr = d >> 2;
+    const int64_t total = n * gpr;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / gpr;
+        const int c = (int)(i - row * gpr) * 4;
+        const float4 xv = *reinterpret_cast<const float4*>(x + row * d + c);
+        const uint2 zb = *reinterpret_cast<const uint2*>(add_bf16 + row * d + c);
+        const float4 bv = add_bias ? *reinterpret_cast<const float4*>(add_bias + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const int sl = slot_map ? slot_map[row] : -1;
+        const float xr[4] = {xv.x, xv.y, xv.z, xv.w}, br[4] = {bv.x, bv.y, bv.z, bv.w};
+        const float fr[4] = {__uint_as_float(zb.x << 16), __uint_as_float(zb.x & 0xffff0000u), __uint_as_float(zb.y << 16),
+                             __uint_as_float(zb.y & 0xffff0000u)};
+        float z[4];
+        if constexpr (DROP) {
+            const snf::philox_f4 mk = snf::dropout_mask4(st, 0, n, row, d, c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float t = (fr[e] + br[e]) * mk[e];
+                asm volatile("" : "+v"(t));      // the product is rounded on its own: no fma contraction with the residual below
+                z[e] = xr[e] + t;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) z[e] = add_bias ? (xr[e] + fr[e]) + br[e] : xr[e] + fr[e];
+        }
+        if (sl >= 0) {
+            const float4 dv = *reinterpret_cast<const float4*>(delta_rows + (int64_t)sl * d + c);
+            z[0] += dv.x, z[1] += dv.y, z[2] += dv.z, z[3] += dv.w;
+        }
+        *reinterpret_cast<float4*>(z_out + row * d + c) = make_float4(z[0], z[1], z[2], z[3]);
+    }
+}
+
+// colsum_fused_kernel of M o src with a bf16 copy: dst = bf16(src o M) (the operand of the two FFN-out gradient GEMMs, df = M_Z o dz) and
+// the column sums of the ROUNDED values (db2), M regenerated from the forward's Philox state -- no row weight, no gate.  Same row / column
+// ownership as colsum_fused_kernel, so the sums add up in the same order.
+template <bool SRC_BF16, int NCH>
+__global__ __launch_bounds__(256) void colsum_fused_dropout_kernel(const void* __restrict__ src, int64_t n, int d, snf::DropoutState st,
+                                                                   unsigned short* __restrict__ dst, float* __restrict__ partial,
+                                                                   int rows_per_block) {
+    float acc[NCH][8];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+    int64_t r1 = r0 + rows_per_block;
+    if (r1 > n) r1 = n;
+    for (int64_t row = r0; row < r1; ++row) {
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const int c = (j * 256 + threadIdx.x) * 8;
+            if (c < d) {
+                float v[8];
+                if constexpr (SRC_BF16) {
+                    const uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(src) + row * d + c);
+                    const unsigned w4[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        v[2 * e] = __uint_as_float(w4[e] << 16);
+                        v[2 * e + 1] = __uint_as_float(w4[e] & 0xffff0000u);
+                    }
+                } else {
+                    const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(src) + row * d + c);
+                    const float4 b = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(src) + row * d + c + 4);
+                    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+                }
+                const snf::philox_f4 m0 = snf::dropout_mask4(st, 0, n, row, d, c), m1 = snf::dropout_mask4(st, 0, n, row, d, c + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] *= m0[e];
+                    v[4 + e] *= m1[e];
+                }
+                if (dst) {
+                    uint4 o;
+                    o.x = pack_bf16x2(v[0], v[1]), o.y = pack_bf16x2(v[2], v[3]);
+                    o.z = pack_bf16x2(v[4], v[5]), o.w = pack_bf16x2(v[6], v[7]);
+                    *reinterpret_cast<uint4*>(dst + row * d + c) = o;
+                    // the sums are taken over the ROUNDED values that the following GEMMs consume
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const unsigned w = e == 0 ? o.x : e == 1 ? o.y : e == 2 ? o.z : o.w;
+                        v[2 * e] = __uint_as_float(w << 16);
+                        v[2 * e + 1] = __uint_as_float(w & 0xffff0000u);
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[j][e] += v[e];
+            }
+        }
+    }
+    float* out = partial + (int64_t)blockIdx.x * d;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c = (j * 256 + threadIdx.x) * 8;
+        if (c < d) {
+            *reinterpret_cast<float4*>(out + c) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+            *reinterpret_cast<float4*>(out + c + 4) = make_float4(acc[j][4], acc[j][5], acc[j][6], acc[j][7]);
+        }
+    }
+}
+
 // x [m, k] f32 (row pitch ldx) -> out [m, 2 k] bf16, interleaved: columns 32 c .. 32 c + 31 as [hi(32) | lo(32)] (k % 32 == 0)
 __global__ __launch_bounds__(256) void split_hl_kernel(const float* __restrict__ x, int64_t ldx, int64_t m, int k,
                                                        unsigned short* __restrict__ out) {
@@ -1552,6 +1692,85 @@ int snf_colsum_fused(const void* src, int src_dtype, int64_t n, int d, const flo
     }
 #undef SNF_COLSUM
     return snf::check_launch("colsum_fused_kernel");
+}
+
+namespace {
+// grid of the flat elementwise passes: enough workgroups to fill the chip a few times over, never more than the work
+int flat_grid(int64_t groups) {
+    int64_t b = (groups + 255) / 256;
+    const int64_t cap = (int64_t)snf::cu_count() * 8;
+    if (b > cap) b = cap;
+    return (int)(b < 1 ? 1 : b);
+}
+}  // namespace
+
+int snf_dropout_rows_bf16(void* x, int64_t ldx, int64_t m, int n, float dropout_p, uint64_t seed, uint64_t offset, snf_stream_t stream) {
+    SNF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "snf_dropout_rows_bf16: dropout_p=%f outside [0, 1)", dropout_p);
+    SNF_REQUIRE(x, "snf_dropout_rows_bf16: null pointer");
+    SNF_REQUIRE(m >= 1 && n >= 8 && n % 8 == 0 && ldx >= n && ldx % 8 == 0,
+                "snf_dropout_rows_bf16: bad shape m=%lld n=%d ldx=%lld (n %% 8 == 0, 16-byte rows)", (long long)m, n, (long long)ldx);
+    SNF_REQUIRE(aligned16(x), "snf_dropout_rows_bf16: x must be 16-byte aligned");
+    if (!(dropout_p > 0.f)) return SNF_OK;     // the mask is all ones
+    const snf::DropoutState st = snf::make_dropout(dropout_p, seed, offset);
+    hipLaunchKernelGGL(dropout_rows_bf16_kernel, dim3(flat_grid(m * (n >> 3))), dim3(256), 0, snf::as_stream(stream),
+                       reinterpret_cast<unsigned short*>(x), ldx, m, n, st);
+    return snf::check_launch("dropout_rows_bf16_kernel");
+}
+
+int snf_residual_assemble_dropout_f32(const float* x, int64_t n, int d, const void* add_bf16, const float* add_bias,
+                                      const int32_t* slot_map, const float* delta_rows, float dropout_p, uint64_t seed, uint64_t offset,
+                                      float* z_out, snf_stream_t stream) {
+    SNF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "snf_residual_assemble_dropout_f32: dropout_p=%f outside [0, 1)", dropout_p);
+    SNF_REQUIRE(x && add_bf16 && z_out, "snf_residual_assemble_dropout_f32: null pointer");
+    SNF_REQUIRE(!slot_map || delta_rows, "snf_residual_assemble_dropout_f32: slot_map without delta_rows");
+    SNF_REQUIRE(n >= 1 && d >= 4 && d % 4 == 0, "snf_residual_assemble_dropout_f32: bad shape n=%lld d=%d (d %% 4 == 0)", (long long)n, d);
+    SNF_REQUIRE(aligned16(x) && aligned16(z_out) && reinterpret_cast<uintptr_t>(add_bf16) % 8 == 0 && (!add_bias || aligned16(add_bias)) &&
+                    (!delta_rows || aligned16(delta_rows)),
+                "snf_residual_assemble_dropout_f32: buffers must be 16-byte aligned (the bf16 addend 8-byte)");
+    const snf::DropoutState st = snf::make_dropout(dropout_p, seed, offset);
+    hipStream_t s = snf::as_stream(stream);
+    const unsigned short* zb = reinterpret_cast<const unsigned short*>(add_bf16);
+    const int grid = flat_grid(n * (d >> 2));
+    if (dropout_p > 0.f)
+        hipLaunchKernelGGL(residual_assemble_dropout_kernel<true>, dim3(grid), dim3(256), 0, s, x, n, d, zb, add_bias, slot_map, delta_rows, st, z_out);
+    else
+        hipLaunchKernelGGL(residual_assemble_dropout_kernel<false>, dim3(grid), dim3(256), 0, s, x, n, d, zb, add_bias, slot_map, delta_rows, st, z_out);
+    return snf::check_launch("residual_assemble_dropout_kernel");
+}
+
+int snf_colsum_fused_dropout(const void* src, int src_dtype, int64_t n, int d, float dropout_p, uint64_t seed, uint64_t offset,
+                             void* dst_bf16, float* partial, snf_stream_t stream) {
+    SNF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "snf_colsum_fused_dropout: dropout_p=%f outside [0, 1)", dropout_p);
+    if (!(dropout_p > 0.f)) return snf_colsum_fused(src, src_dtype, n, d, nullptr, 0, nullptr, dst_bf16, partial, stream);
+    SNF_REQUIRE(src && partial, "snf_colsum_fused_dropout: null pointer");
+    SNF_REQUIRE(n >= 1 && d >= 8 && d % 8 == 0 && d <= 8192, "snf_colsum_fused_dropout: bad shape n=%lld d=%d (d %% 8 == 0, d <= 8192)",
+                (long long)n, d);
+    SNF_REQUIRE(src_dtype == SNF_DT_F32 || src_dtype == SNF_DT_BF16, "snf_colsum_fused_dropout: bad dtype %d", src_dtype);
+    SNF_REQUIRE(aligned16(src) && aligned16(partial) && (!dst_bf16 || aligned16(dst_bf16)),
+                "snf_colsum_fused_dropout: buffers must be 16-byte aligned");
+    const int blocks = snf_colsum_blocks(n);
+    const int rpb = (int)((n + blocks - 1) / blocks);
+    const int nch = (d + 2047) / 2048;
+    hipStream_t s = snf::as_stream(stream);
+    const snf::DropoutState st = snf::make_dropout(dropout_p, seed, offset);
+    unsigned short* o = reinterpret_cast<unsigned short*>(dst_bf16);
+#define SNF_COLSUM_DROP(BF, NC) \
+    hipLaunchKernelGGL((colsum_fused_dropout_kernel<BF, NC>), dim3(blocks), dim3(256), 0, s, src, n, d, st, o, partial, rpb)
+    if (src_dtype == SNF_DT_BF16) {
+        switch (nch) {
+            case 1: SNF_COLSUM_DROP(true, 1); break;
+            case 2: SNF_COLSUM_DROP(true, 2); break;
+            default: SNF_COLSUM_DROP(true, 4); break;
+        }
+    } else {
+        switch (nch) {
+            case 1: SNF_COLSUM_DROP(false, 1); break;
+            case 2: SNF_COLSUM_DROP(false, 2); break;
+            default: SNF_COLSUM_DROP(false, 4); break;
+        }
+    }
+#undef SNF_COLSUM_DROP
+    return snf::check_launch("colsum_fused_dropout_kernel");
 }
 
 int snf_layernorm_rows_hl_f32(const float* x, int64_t n, int d, const int32_t* slot_map, const float* patch_rows,

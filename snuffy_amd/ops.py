@@ -399,10 +399,12 @@ def layernorm_rows_bwd(x, dy, gamma=None, eps=1e-5, residual=None, want_dx=True,
     return dx, dxb, sums[0], sums[1]
 
 
-def colsum_fused(src, row_weight=None, gate=None, want_bf16=False, inplace=False):
+def colsum_fused(src, row_weight=None, gate=None, want_bf16=False, inplace=False, dropout=None):
     """Column sums of src [n, d] (f32 or bf16) fused with an optional row weight [n] (f32, any stride), an optional ReLU gate
     (bf16 [n, d]: elements whose gate is <= 0 are zeroed) and an optional bf16 copy of the result (inplace: written over a
-    bf16 src).  Returns (colsum [d] f32, bf16 copy or None).  See snf_colsum_fused."""
+    bf16 src).  Returns (colsum [d] f32, bf16 copy or None).  See snf_colsum_fused.
+    dropout = (p, seed, offset): sums and copy of M o src, M = dropout_mask(1, n, d, p, seed, offset) regenerated in the pass
+    (snf_colsum_fused_dropout; no row weight, no gate)."""
     if src.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError("colsum_fused: src must be float32 or bfloat16")
     src = _req(src, src.dtype, "src", 2)
@@ -427,6 +429,13 @@ def colsum_fused(src, row_weight=None, gate=None, want_bf16=False, inplace=False
         dst = torch.empty(n, d, dtype=torch.bfloat16, device=src.device)
     lib = _ffi.load()
     part = torch.empty(lib.snf_colsum_blocks(n), d, dtype=torch.float32, device=src.device)
+    if dropout is not None:
+        if row_weight is not None or gate is not None:
+            raise ValueError("colsum_fused: the dropout form takes no row weight and no gate")
+        check(lib.snf_colsum_fused_dropout(_p(src), DT_F32 if src.dtype == torch.float32 else DT_BF16, n, d, float(dropout[0]),
+                                           int(dropout[1]) & (2 ** 64 - 1), int(dropout[2]) & (2 ** 64 - 1), _p(dst), _p(part), _stream()),
+              "snf_colsum_fused_dropout")
+        return part.sum(0), dst
     check(lib.snf_colsum_fused(_p(src), DT_F32 if src.dtype == torch.float32 else DT_BF16, n, d, _p(row_weight), ws, _p(gate),
                                _p(dst), _p(part), _stream()), "snf_colsum_fused")
     return part.sum(0), dst
@@ -1175,6 +1184,106 @@ def linear_bf16(a, w, bias_f32=None, bias_bf16=None, act="none", prefer_native=N
     out = torch.mm(a, w.t())
     bias_act_(out, bias_f32 if bias_f32 is not None else (bias_bf16.float() if bias_bf16 is not None else None), act)
     return out
+
+
+def bf16_encoder_dropout_supported(n, d, f):
+    """Shapes the bf16 chain's encoder-dropout kernels take for a bag [n, d] with f hidden columns: dropout_rows_bf16_ / the DROP
+    epilogue over hid [n, f], residual_assemble_dropout over z [n, d], colsum_fused with dropout over dz [n, d]."""
+    return n >= 1 and d >= 8 and d % 8 == 0 and d <= 8192 and f >= 8 and f % 8 == 0
+
+
+def dropout_gemm_prefers_native(m, n, k):
+    """Which form linear_bf16_dropout takes, measured on MI355X at the FFN-in shapes of config B (32 768 x 3072 x 768) and of a ViT-S bag
+    (16 384 x 1536 x 384) with tools/encoder_dropout_bf16_time.py --gemm (profiles/encoder_dropout_bf16_train.txt): the mask in the
+    hand-written GEMM's epilogue is the faster form in both shape classes (0.207 against 0.243 ms, 0.048 against 0.061 ms) -- also at
+    config B, where without dropout the library GEMM is 7 % ahead of the hand-written one: the in-place pass behind it costs 0.093 ms,
+    the Philox calls in the epilogue 0.062 ms.  The library GEMM plus the pass is left with the shapes outside the kernel's domain."""
+    return gemm_supported(m, n, k)
+
+
+def dropout_rows_bf16_(x, dropout):
+    """x = bf16(float(x) * M) in place, M = dropout_mask(1, m, n, p, seed, offset)[0] regenerated in registers; x bf16 [m, n], a
+    row-pitched view of a wider buffer included (columns beyond n are not touched).  dropout = (p, seed, offset).  snf_dropout_rows_bf16."""
+    x = _req_nc(x, "x")
+    if x.dtype != torch.bfloat16:
+        raise TypeError("dropout_rows_bf16_: x must be bfloat16")
+    m, n = x.shape
+    if x.stride(1) != 1 or x.stride(0) < n or x.stride(0) % 8 or x.data_ptr() % 16 or n % 8:
+        raise ValueError("dropout_rows_bf16_: x needs unit-stride, 16-byte aligned rows of a multiple of 8 columns (shape %s, strides %s)"
+                         % (tuple(x.shape), tuple(x.stride())))
+    p, seed, offset = dropout
+    check(_ffi.load().snf_dropout_rows_bf16(_p(x), x.stride(0), m, n, float(p), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                            _stream()), "snf_dropout_rows_bf16")
+    return x
+
+
+def gemm_bf16_dropout(a, w, bias, dropout, act="relu", out_dtype=torch.bfloat16, tile_n=0):
+    """bf16(M o relu(a @ w.T + bias)) on the hand-written MFMA kernel, the Philox keep-mask M = dropout_mask(1, m, n, *dropout)[0]
+    applied to the fp32 value in the epilogue (snf_gemm_bf16_dropout).  ReLU with a bf16 output is the one form that exists."""
+    if a.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise TypeError("gemm_bf16_dropout: a and w must be bfloat16")
+    if act != "relu" or out_dtype != torch.bfloat16:
+        raise ValueError("gemm_bf16_dropout: only relu -> bfloat16 exists (act=%r, out_dtype=%s)" % (act, out_dtype))
+    a = _rows16(a, "a")
+    w = _rows16(w, "w")
+    m, k = a.shape
+    n = w.shape[0]
+    if w.shape[1] != k:
+        raise ValueError("gemm_bf16_dropout: a is %s but w is %s" % (tuple(a.shape), tuple(w.shape)))
+    if bias is not None:
+        bias = _req(bias, torch.float32, "bias", 1)
+        if bias.shape[0] != n:
+            raise ValueError("gemm_bf16_dropout: bias has %d entries for %d columns" % (bias.shape[0], n))
+    out = torch.empty(m, n, dtype=torch.bfloat16, device=a.device)
+    p, seed, offset = dropout
+    check(_ffi.load().snf_gemm_bf16_dropout(_p(a), a.stride(0), _p(w), w.stride(0), _p(bias), m, n, k, ACT_CODES[act], _p(out),
+                                            out.stride(0), DT_BF16, int(tile_n), float(p), int(seed) & (2 ** 64 - 1),
+                                            int(offset) & (2 ** 64 - 1), _stream()), "snf_gemm_bf16_dropout")
+    return out
+
+
+def linear_bf16_dropout(a, w, bias_f32, bias_bf16, dropout, prefer_native=None):
+    """bf16(M o relu(a @ w.T + bias)): the FFN hidden layer of a bf16 training step with encoder dropout (snuffy.py:225), in one of two
+    forms by the measured shape policy above -- the mask in the hand-written GEMM's epilogue (one rounding, of the masked fp32 value), or
+    linear_bf16's library GEMM followed by one in-place pass (dropout_rows_bf16_: the kept elements are rounded a second time after the
+    1 / (1 - p) scale).  dropout = (p, seed, offset); either way the mask is dropout_mask(1, m, n, p, seed, offset)[0]."""
+    m, k = a.shape
+    n = w.shape[0]
+    native = dropout_gemm_prefers_native(m, n, k) if prefer_native is None else (prefer_native and gemm_supported(m, n, k))
+    if native:
+        if bias_f32 is None and bias_bf16 is not None:
+            bias_f32 = bias_bf16.float()
+        return gemm_bf16_dropout(a, w, bias_f32, dropout)
+    return dropout_rows_bf16_(linear_bf16(a, w, bias_f32, bias_bf16, "relu", prefer_native=False), dropout)
+
+
+def residual_assemble_dropout(x, add_bf16, add_bias, slot, delta_rows, dropout):
+    """z = x + M o (float(add_bf16) + add_bias) (+ delta_rows[slot] at the rows with slot >= 0) in one launch, M = dropout_mask(1, n, d,
+    *dropout)[0]: the residual stream behind the FFN with its dropout (snuffy.py:110).  Each step is rounded on its own, in that order
+    (snf_residual_assemble_dropout_f32); p = 0 gives what functional.materialize gives."""
+    x = _req(x, torch.float32, "x", 2)
+    n, d = x.shape
+    add_bf16 = _req(add_bf16, torch.bfloat16, "add_bf16", 2)
+    if tuple(add_bf16.shape) != (n, d) or d % 4:
+        raise ValueError("residual_assemble_dropout: x is %s, add_bf16 %s (d %% 4 == 0)" % (tuple(x.shape), tuple(add_bf16.shape)))
+    if add_bias is not None:
+        add_bias = _req(add_bias, torch.float32, "add_bias", 1)
+        if add_bias.shape[0] != d:
+            raise ValueError("residual_assemble_dropout: add_bias has %d entries for %d columns" % (add_bias.shape[0], d))
+    if slot is not None:
+        slot = _req(slot, torch.int32, "slot", 1)
+        delta_rows = _req(delta_rows, torch.float32, "delta_rows", 2)
+        if slot.shape[0] != n or delta_rows.shape[1] != d:
+            raise ValueError("residual_assemble_dropout: slot %s / delta_rows %s do not match x %s"
+                             % (tuple(slot.shape), tuple(delta_rows.shape), tuple(x.shape)))
+    else:
+        delta_rows = None
+    z = torch.empty_like(x)
+    p, seed, offset = dropout
+    check(_ffi.load().snf_residual_assemble_dropout_f32(_p(x), n, d, _p(add_bf16), _p(add_bias), _p(slot), _p(delta_rows), float(p),
+                                                        int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), _p(z), _stream()),
+          "snf_residual_assemble_dropout_f32")
+    return z
 
 
 def gemm_bf16(a, w, bias=None, act="none", out_dtype=torch.bfloat16, out=None, tile_n=0, split3=False, hl_out=False):
