@@ -302,6 +302,9 @@ int snf_sparse_attn_fwd_mfma(const void* q, int64_t ldq, const void* v, int64_t 
  *   forward : the normalised probabilities are multiplied by the mask (0 or 1 / (1 - p)) before they are pooled; `out` and the
  *             returned `attn` are those of the dropped P, as in the reference.  Needs lse (or attn) requested.
  *   backward: pass mask == NULL and the forward's (dropout_p, seed, offset).
+ * More keys than one launch holds (key chunks, see snf_sparse_attn_fwd_mfma): with dropout the main passes' chunks start on multiples
+ * of 4 keys (one Philox call covers 4 consecutive keys), the main pass of a chunk regenerates the mask with the key index among ALL
+ * keys, and the cross-chunk statistics, lse and the undropped P are, bit for bit, those of the launch without dropout.
  * snf_dropout_mask_f32 writes the same mask as a tensor [h, n, k] (exact-fp32 training path, tests). */
 int snf_sparse_attn_fwd_mfma_dropout(const void* q, int64_t ldq, const void* v, int64_t ldv, int qv_dtype, const void* kp,
                                      int kp_dtype, int64_t n, int k, int h, int dk, float scale, float* out, float* attn,
@@ -404,6 +407,20 @@ int snf_sparse_attn_bwd_mfma_ex(const void* q, int64_t ldq, const void* v, int64
                                 const float* dout, const float* lse, const float* mask, float dropout_p, uint64_t seed,
                                 uint64_t offset, int64_t n, int k, int h, int dk, float scale, void* dq, void* dv, int64_t ldd,
                                 int dqv_dtype, void* ds, int ds_dtype, snf_stream_t stream);
+/* The same backward for MORE keys than one launch holds: dk == 128 with k <= 8 x 224 or dk == 64 with k <= 8 x 256 (the key chunks of
+ * snf_sparse_attn_fwd_mfma's domain; chunk starts are multiples of 32).  The forward's lse is global, so P of a chunk is recomputed on
+ * its own.  Series A, one launch per chunk: dV summed in fp32 over the chunks, then D = V . dV per head and row (= rowsum(P o dP), with
+ * or without a mask).  Series B, one launch per chunk: dS = P o (dP - D) * scale at the chunk's columns of the full-width ds
+ * [h, n, k], dQ summed the same way.  A wave owns its rows in every launch and the chunks are added in launch order: no atomics,
+ * bit-reproducible.  The dropout mask -- tensor or (dropout_p, seed, offset) -- is keyed on the key index among ALL keys, as
+ * snf_dropout_mask_f32 writes it.  Arguments as snf_sparse_attn_bwd_mfma_ex, plus the workspace (D, and the fp32 sums when dq / dv
+ * leave as bf16; fp32 dq / dv are summed in place).  One chunk: forwards to snf_sparse_attn_bwd_mfma_ex (workspace may be NULL). */
+size_t snf_sparse_attn_bwd_mfma_chunked_workspace_bytes(int64_t n, int k, int h, int dk, int dqv_dtype);
+int snf_sparse_attn_bwd_mfma_chunked(const void* q, int64_t ldq, const void* v, int64_t ldv, int qv_dtype, const float* kp,
+                                     const float* dout, const float* lse, const float* mask, float dropout_p, uint64_t seed,
+                                     uint64_t offset, int64_t n, int k, int h, int dk, float scale, void* dq, void* dv, int64_t ldd,
+                                     int dqv_dtype, void* ds, int ds_dtype, void* workspace, size_t workspace_bytes,
+                                     snf_stream_t stream);
 /* dKp [k, d] = dS^T Q per head (deterministic slice reduction); ds [h, n, k], q [n, d] f32.
  * workspace: snf_sparse_attn_bwd_workspace_bytes. */
 int snf_sparse_attn_dkp_f32(const float* ds, const float* q, int64_t n, int k, int h, int dk, float* dkp, void* workspace,

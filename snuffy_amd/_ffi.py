@@ -117,6 +117,10 @@ SIGNATURES = {
     "snf_sparse_attn_bwd_mfma_ex": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_float, c_uint64, c_uint64, c_int64, c_int, c_int, c_int, c_float, c_void_p,
                                             c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p]),
+    "snf_sparse_attn_bwd_mfma_chunked_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
+    "snf_sparse_attn_bwd_mfma_chunked": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_float, c_uint64, c_uint64, c_int64, c_int, c_int, c_int, c_float, c_void_p,
+                                                 c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "snf_dropout_mask_f32": (c_int, [c_float, c_uint64, c_uint64, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "snf_tile_preprocess_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                        c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

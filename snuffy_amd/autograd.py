@@ -25,6 +25,10 @@ FUSED_BF16_TRAINING = True
 # chains the same masks), regenerated in the FFN-in GEMM's epilogue or in one in-place pass behind the library GEMM, in a one-launch assembly
 # of z and in the backward's dz pass; False: a layer with encoder dropout on takes the generic autograd chain (torch's generator)
 FUSED_BF16_ENCODER_DROPOUT = True
+# ... and that chain above one key chunk of the MFMA attention (Lambda > 224 at dk = 128, > 256 at dk = 64: up to 8 chunks, forward with
+# in-kernel dropout and backward over chunks) and at head widths that ride zero-padded to 64 / 128 (functional.head_pad: the README
+# recipes' dk = 96); False: such layers take the generic autograd chain, as before (fused_layer0_chunked_ok)
+FUSED_BF16_KEY_CHUNKS = True
 # fp32 training: the same for the fp32-class arithmetic (EncoderLayer0X3Fn, round 5)
 FUSED_X3_TRAINING = True
 # ... on the one-pass kernels (round 6): activations and gradients as interleaved hl images (4 bytes per element instead of the 6 of
@@ -352,7 +356,12 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
     Encoder dropout (fused_layer0_train_ok): one Philox state per site with p > 0, drawn in the order A, H, Z after the attention's own
     draw, exactly as EncoderLayer0X3Fn does (layer.last_dropout_states).  A: delta [K, D] times a mask tensor.  H: hid = bf16(M_H o relu(.)),
     the mask in the GEMM's epilogue or in one in-place pass (ops.linear_bf16_dropout).  Z: z = x + M_Z o (zb + b2) (+ delta) in one assembly
-    launch; its backward regenerates M_Z in the dz pass.  A site with p == 0 draws and launches nothing new."""
+    launch; its backward regenerates M_Z in the dz pass.  A site with p == 0 draws and launches nothing new.
+
+    Padded heads (fused_layer0_chunked_ok; dk = 96 -> 128): Q | V, Kp and O carry dkp = functional.head_pad(dk) columns per head, the
+    padding being zero rows of the folded Q | V weights and of Wk / bk and zero columns of Wo (functional._folded(layer, dkp),
+    _padded_heads) -- exact zeros in the forward, so the scores, P and the true columns of O are those of the true width (scale =
+    1 / sqrt(dk)).  The backward cuts the gradients of the padded operands back to the parameters' own rows / columns."""
 
     @staticmethod
     def forward(ctx, x2, sel, layer, need_attn, g0, b0, g1, b1, wq, bq, wk, bk, wv, bv, wo, bo, w1, bb1, w2, bb2):
@@ -361,25 +370,35 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
         mha = layer.self_attn
         h = mha.h
         eps = layer.sublayer[0].norm.eps
-        fw = SF._folded(layer)
+        dk = d // h
+        dkp = SF.head_pad(dk) or dk                                                    # head width of Q | V, Kp and O
+        dp = h * dkp
+        fw = SF._folded(layer, dkp)
         xhat = SF._take_xhat(layer, x2, eps)                                           # left by the critic pass, if any
         if xhat is None:
             xhat = torch.empty(n, d, dtype=torch.bfloat16, device=x2.device)
             ops.layernorm_rows(x2, None, None, eps, out=xhat)
         qv = ops.linear_bf16(xhat, fw["wqv"], fw["bqv_f"], fw["bqv"])
-        q, v = qv[:, :d], qv[:, d:]
+        q, v = qv[:, :dp], qv[:, dp:]
         xs, slot, xs16 = ops.gather_slot_map(x2, sel, bf16_copy=True)
-        kp = torch.addmm(fw["bk"], xs16, fw["wk"].t()).float()
+        wo_p = None
+        if dkp != dk:
+            fp = SF._padded_heads(layer, dkp)
+            wo_p = fp["wo"]                                                            # [D, h dkp]: zero columns at the padding
+            kp = torch.addmm(fp["bk"].to(torch.bfloat16), xs16, fp["wk"].to(torch.bfloat16).t()).float()
+        else:
+            kp = torch.addmm(fw["bk"], xs16, fw["wk"].t()).float()
         p_drop = mha.dropout.p if layer.training else 0.0
         drop = (float(p_drop),) + draw_dropout_state() if p_drop > 0.0 else None
-        o, attn, lse = ops.sparse_attn_fwd_mfma(q, v, kp, n, h, need_attn=need_attn, need_lse=True, dropout=drop)
+        o, attn, lse = ops.sparse_attn_fwd_mfma(q, v, kp, n, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn, need_lse=True,
+                                                dropout=drop)
         # encoder dropout: A = after the attention output (snuffy.py:108), H = inside the FFN (:225), Z = after it (:110)
         p_a, p_h, p_z = _encoder_dropout_ps(layer)
         drop_a = (p_a,) + draw_dropout_state() if p_a > 0.0 else None
         drop_h = (p_h,) + draw_dropout_state() if p_h > 0.0 else None
         drop_z = (p_z,) + draw_dropout_state() if p_z > 0.0 else None
         layer.last_dropout_states = {"attn": drop, "A": drop_a, "H": drop_h, "Z": drop_z}
-        delta = torch.addmm(bo, o, wo.t())
+        delta = torch.addmm(bo, o, (wo if wo_p is None else wo_p).t())
         mask_a = None
         if drop_a is not None:
             mask_a = ops.dropout_mask(1, sel.numel(), d, drop_a[0], drop_a[1], drop_a[2], x2.device)[0]   # [K, D]: the one mask that is a tensor
@@ -397,7 +416,8 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
         else:
             z = SF.materialize(SF.Parts(x2, add_bf16=zb, add_bias=bb2, slot=slot, delta=delta))
         ctx.save_for_backward(sel, xhat0_sel, qv, kp, lse, o, xs, x_sel, hid, g0, b0, g1, b1, wq, wk, wv, wo, w1,
-                              fw["w1"], fw["w2"], mask_a)
+                              fw["w1"], fw["w2"], mask_a, wo_p)
+        ctx.dk, ctx.dkp = dk, dkp
         ctx.scale_h = 1.0 / (1.0 - p_h) if drop_h is not None else None
         ctx.drop_z = drop_z
         ctx.xhat = xhat          # read-only in backward; outside save_for_backward because the forward wrote rows S in place after the
@@ -408,10 +428,16 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, _dattn):
-        (sel, xhat0_sel, qv, kp, lse, o, xs, x_sel, hid, g0, b0, g1, b1, wq, wk, wv, wo, w1, w1f, w2f, mask_a) = ctx.saved_tensors
+        (sel, xhat0_sel, qv, kp, lse, o, xs, x_sel, hid, g0, b0, g1, b1, wq, wk, wv, wo, w1, w1f, w2f, mask_a, wo_p) = ctx.saved_tensors
         xhat = ctx.xhat
         n, d = xhat.shape
         h, eps = ctx.h, ctx.eps
+        dk, dkp = ctx.dk, ctx.dkp
+        dp = h * dkp
+        padded = dkp != dk
+
+        def true_rows(t):            # [h dkp, ...] -> the true head rows [h dk, ...]
+            return t.view((h, dkp) + tuple(t.shape[1:]))[:, :dk].reshape((h * dk,) + tuple(t.shape[1:]))
         f32 = torch.float32
         dz = dz.float().contiguous()
         # ---- FFN: z = y + act(xhat1 W1'^T + b1') W2^T + b2                                                (snuffy.py:224-225)
@@ -442,10 +468,13 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
             dy_s = dy_s * mask_a            # d loss / d (o Wo^T + bo); the residual path dz[S] went into the LayerNorm backward above, unmasked
         dbo = dy_s.sum(0)
         dwo = dy_s.t() @ o
-        do = dy_s @ wo
+        do = dy_s @ (wo_p if padded else wo)                                          # [K, h dkp]: zero at the padded columns
+        if padded:
+            dwo = dwo.view(d, h, dkp)[:, :, :dk].reshape(d, d)
         # ---- attention                                                                                     (snuffy.py:160-168)
-        q, v = qv[:, :d], qv[:, d:]
-        dq, dkp, dv = ops.sparse_attn_bwd_mfma(q, v, kp, do.contiguous(), lse, h, dropout=ctx.drop, fused_bf16_grads=True)
+        q, v = qv[:, :dp], qv[:, dp:]
+        dq, dkp_, dv = ops.sparse_attn_bwd_mfma(q, v, kp, do.contiguous(), lse, h, scale=1.0 / math.sqrt(dk), dropout=ctx.drop,
+                                                fused_bf16_grads=True)
         dqv = dq._base                                                                # [N, 2D] bf16 = [dQ | dV]
         del dq, dv
         # xhat holds LayerNorm 1's rows at S since the forward re-normalised them in place; the Q|V projection saw LayerNorm 0's.
@@ -454,8 +483,12 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
         corr = (xhat0_sel.float() - xhat.index_select(0, sel).float())               # [K, D]
         dwqvf += dqv.index_select(0, sel).float().t() @ corr
         dbqvf, _ = ops.colsum_fused(dqv)
-        dwk = dkp.t() @ xs
-        dbk = dkp.sum(0)
+        if padded:                   # back to the parameters' own shapes: per head, the true rows of the folded Q | V gradients and of dKp^T
+            dwqvf = torch.cat([true_rows(dwqvf[:dp]), true_rows(dwqvf[dp:])])
+            dbqvf = torch.cat([true_rows(dbqvf[:dp]), true_rows(dbqvf[dp:])])
+            dkp_ = dkp_.view(-1, h, dkp)[:, :, :dk].reshape(-1, d)
+        dwk = dkp_.t() @ xs
+        dbk = dkp_.sum(0)
         # ---- unfold  W' = W * gamma,  b' = W beta + b  (one kernel per projection: dW, and the partial sums of dgamma / dbeta)
         dbq, dbv = dbqvf[:d].contiguous(), dbqvf[d:].contiguous()
         if d <= 2048:
@@ -507,12 +540,40 @@ def fused_layer0_train_ok(layer, n, d, k=None):
             and ops.bf16_encoder_dropout_supported(n, d, layer.feed_forward.w_1.weight.shape[0]))
 
 
+def fused_layer0_chunked_ok(layer, n, d, k=None):
+    """EncoderLayer0Bf16Fn takes the layer beyond fused_layer0_train_ok (FUSED_BF16_KEY_CHUNKS): the same settings (ReLU FFN, one eps, all
+    parameters trainable, encoder dropout as fused_layer0_train_ok admits it) with up to 8 key chunks of the MFMA attention instead of one
+    and with a head width that is 64 or 128 after functional.head_pad.  dk = 192 (the README's MAE recipe) has no padded form."""
+    if not (FUSED_BF16_TRAINING and FUSED_BF16_KEY_CHUNKS):
+        return False
+    mha, ff = layer.self_attn, layer.feed_forward
+    n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
+    if ff.activation_name != "relu" or n0.eps != n1.eps or d % mha.h:
+        return False
+    if k is None:
+        k = min(int(layer.big_lambda), n)
+    dk = d // mha.h
+    dkp = SF.head_pad(dk)
+    if dkp is None:
+        return False
+    dp = mha.h * dkp
+    if not (k >= 1 and ops.mfma_attn_supported(k, dkp, n, 2 * dp) and ops.mfma_attn_train_chunks_supported(k, dkp)
+            and all(p.requires_grad for p in layer.parameters())):
+        return False
+    ps = _encoder_dropout_ps(layer)
+    if any(p != 0.0 for p in ps):
+        return (FUSED_BF16_ENCODER_DROPOUT and all(0.0 <= p < 1.0 for p in ps)
+                and ops.bf16_encoder_dropout_supported(n, d, ff.w_1.weight.shape[0]))
+    return True
+
+
 def fused_layer0_ok(x2, sel, layer, precision):
     """The first-layer chain applies: bf16, the bag is data (no gradient flows into x2), supported shape / settings;
     everything else keeps the generic autograd chain below."""
     if precision != "bf16" or x2.requires_grad or sel.numel() == 0:
         return False
-    return fused_layer0_train_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
+    return (fused_layer0_train_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
+            or fused_layer0_chunked_ok(layer, x2.shape[0], x2.shape[1], sel.numel()))
 
 
 def _x3_train_weights(layer, hl=False):

@@ -400,6 +400,291 @@ int launch_bwd_nkb(const BwdParams& P, const BwdPlan& pl, hipStream_t s) {
     }
 }
 
+
+// ---- more keys than one pair of LDS images holds: the backward over key chunks ------------------------------------------------------
+// The forward's lse is GLOBAL (all keys), so P of any chunk is recomputed on its own; what needs all keys is D = rowsum(P o dP) and
+// the sums dV, dQ.  Two series of launches, one launch per chunk each (the forward's "statistics pass, then main pass"):
+//   series A   S -> P -> Pd = P o M -> dV += dO^T Pd^T                      the last launch also takes D = V . dV per head and row:
+//                                                                           D = sum_j Pd_j (V . dO_j) = V . sum_j Pd_j dO_j, mask or not
+//   series B   S, dP = (V dO^T) o M, dS = P o (dP - D) * scale -> column k0 of the full-width dS, dQ += Kp^T dS^T
+// The running sums live in fp32 between the launches (the caller's dq / dv when those are fp32, else the workspace): a wave owns
+// its rows in every launch and the chunks are added in launch order -- no atomics, one summation order.  Nothing is kept per key
+// block across blocks (P or dS of a block goes straight into its MFMAs), so the block loop is a run-time loop and one kernel
+// serves every chunk length; 8 waves per workgroup (two per SIMD) overlap one wave's exponentials with the other's MFMAs.
+// The mask is keyed on the GLOBAL key index and the total key count, in registers (Philox) or from the [h, n, k] tensor; each
+// series uses it once, so the single-chunk kernel's sign-bit memory has nothing to save here.
+constexpr int CH_WAVES = 8, CH_ROWS = 32 * CH_WAVES;
+
+struct ChunkParams {
+    BwdParams b;        // kp / dout point at the chunk's first key, b.k = keys of THIS chunk; mask / ds at column 0 of the full rows
+    int k0, k_total;    // first key of the chunk, keys of all chunks
+    int nkb;            // key blocks of this chunk
+    int first, last;    // first / last launch of the series
+    float* acc;         // [n, ldacc] f32 running sum of the series (dV in A, dQ in B)
+    int64_t ldacc;
+    float* dsum;        // [h, n] D: written by the last launch of series A, read by series B
+};
+
+__device__ __forceinline__ void load4_bf16(const float* p, float (&o)[4]) {   // rounded as the MFMA operand is (load_frag)
+    const f32x4 x = *reinterpret_cast<const f32x4*>(p);
+    const unsigned a = pack2(x[0], x[1]), b = pack2(x[2], x[3]);
+    o[0] = lo_f(a), o[1] = hi_f(a), o[2] = lo_f(b), o[3] = hi_f(b);
+}
+__device__ __forceinline__ void load4_bf16(const unsigned short* p, float (&o)[4]) {
+    const uint2 x = *reinterpret_cast<const uint2*>(p);
+    o[0] = lo_f(x.x), o[1] = hi_f(x.x), o[2] = lo_f(x.y), o[3] = hi_f(x.y);
+}
+
+// SERIES 0 = A, 1 = B.  FAST (series B, the training path's shape): bf16 dS, K % 4 == 0, no mask tensor.
+template <int DK, typename QT, int SERIES, bool FAST>
+__global__ __launch_bounds__(64 * CH_WAVES, 1) void sparse_attn_bwd_chunk_kernel(ChunkParams C) {
+    const BwdParams& P = C.b;
+    constexpr int NKS = DK / 16, NCB = DK / 32, RP = 2 * DK, NCH = DK / 8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* img_kp = smem;
+    unsigned char* img_do = smem + 32 * C.nkb * RP;
+    // A operand of the second product: dO^T (series A, dV) or Kp^T (series B, dQ)
+    const unsigned char* img_t = SERIES == 0 ? img_do : img_kp;
+
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int j = lane & 31, hf = lane >> 5;
+    const QT* __restrict__ q = reinterpret_cast<const QT*>(P.q);
+    const QT* __restrict__ vg = reinterpret_cast<const QT*>(P.v);
+    const float c_exp = P.scale * 1.44269504088896340736f;
+    const int n32 = (int)P.n;
+    const int prow = 32 * w + j;
+
+    int ra[NKS];   // see sparse_attn_bwd_mfma_kernel: the same images, the same fragment addresses
+#pragma unroll
+    for (int kb = 0; kb < NKS; ++kb) ra[kb] = j * RP + 16 * img_pos<DK>(j, 2 * kb + hf);
+    const int tg = lane >> 4, ti = lane & 15;
+    int rt0[NCB], rt1[NCB];
+#pragma unroll
+    for (int db = 0; db < NCB; ++db) {
+        const int r0 = 4 * (tg >> 1) + (ti >> 2), r1 = r0 + 8;
+        const int c = 4 * db + 2 * (tg & 1) + ((ti & 3) >> 1);
+        rt0[db] = r0 * RP + 16 * img_pos<DK>(r0, c) + 8 * (ti & 1);
+        rt1[db] = r1 * RP + 16 * img_pos<DK>(r1, c) + 8 * (ti & 1);
+    }
+
+    const int f_begin = blockIdx.x * P.tiles_per_wg;
+    int f_end = f_begin + P.tiles_per_wg;
+    if (f_end > P.total_tiles) f_end = P.total_tiles;
+    int a = f_begin / P.tiles_per_head, t = f_begin - a * P.tiles_per_head;
+    int cur_head = -1;
+
+    for (int f = f_begin; f < f_end; ++f) {
+        if (a != cur_head) {
+            __syncthreads();
+            for (int ci = threadIdx.x; ci < 32 * C.nkb * NCH; ci += 64 * CH_WAVES) {
+                const int row = ci / NCH, c = ci % NCH;
+                u32x4 vk = {0u, 0u, 0u, 0u}, vo = {0u, 0u, 0u, 0u};
+                if (row < P.k) {
+                    vk = __builtin_bit_cast(u32x4, load_frag(P.kp + (int64_t)row * P.d + a * DK + 8 * c));
+                    vo = __builtin_bit_cast(u32x4, load_frag(P.dout + (int64_t)row * P.d + a * DK + 8 * c));
+                }
+                const int off = row * RP + 16 * img_pos<DK>(row, c);
+                *reinterpret_cast<u32x4*>(img_kp + off) = vk;
+                *reinterpret_cast<u32x4*>(img_do + off) = vo;
+            }
+            __syncthreads();
+            cur_head = a;
+        }
+        const int row = t * CH_ROWS + prow;
+        const bool rvalid = row < n32;
+        const int lrow = rvalid ? row : n32 - 1;
+        bf16x8 qf[NKS], vf[SERIES == 1 ? NKS : 1];
+        {
+            const QT* qp = q + (int64_t)lrow * P.ldq + a * DK + 8 * hf;
+            const QT* vp = vg + (int64_t)lrow * P.ldv + a * DK + 8 * hf;
+            static_for<0, NKS>([&](auto kb) __attribute__((always_inline)) {
+                qf[kb] = load_frag(qp + 16 * kb);
+                if constexpr (SERIES == 1) vf[kb] = load_frag(vp + 16 * kb);
+            });
+        }
+        const float lse2 = rvalid ? P.lse[(int64_t)a * P.n + row] * 1.44269504088896340736f : INFINITY;   // rows past the end: P = 0
+        const float* mrow = P.mask ? P.mask + ((int64_t)a * P.n + lrow) * C.k_total + C.k0 : nullptr;
+        float dtot = 0.f;
+        if constexpr (SERIES == 1) dtot = C.dsum[(int64_t)a * P.n + lrow];
+        float* dsrow = reinterpret_cast<float*>(P.ds) + ((int64_t)a * P.n + lrow) * C.k_total + C.k0;
+        unsigned short* dsrow16 = reinterpret_cast<unsigned short*>(P.ds) + ((int64_t)a * P.n + lrow) * C.k_total + C.k0;
+        const bool vec_ok = (C.k_total & 3) == 0;   // chunk starts are multiples of 32
+
+        // the running sum of the chunks before this one; C layout of X^T[col, row]: lane = row, registers = columns
+        // 32 db + (r & 3) + 8 (r >> 2) + 4 hf
+        f32x16 acc[NCB];
+        float* accp = C.acc + (int64_t)lrow * C.ldacc + a * DK + 4 * hf;
+#pragma unroll
+        for (int db = 0; db < NCB; ++db)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 x = {0.f, 0.f, 0.f, 0.f};
+                if (!C.first && rvalid) x = *reinterpret_cast<const f32x4*>(accp + 32 * db + 8 * g);
+                acc[db][4 * g] = x[0], acc[db][4 * g + 1] = x[1], acc[db][4 * g + 2] = x[2], acc[db][4 * g + 3] = x[3];
+            }
+
+#pragma unroll 1
+        for (int jb = 0; jb < C.nkb; ++jb) {
+            const int jo = jb * 32 * RP;
+            const bool tail = jb == C.nkb - 1;   // only the last block holds padded keys: P = 0 there
+            f32x16 s, dp;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                s[r] = (tail && 32 * jb + (r & 3) + 8 * (r >> 2) + 4 * hf >= P.k) ? -INFINITY : 0.f;
+                dp[r] = 0.f;
+            }
+            static_for<0, NKS>([&](auto kb_t) __attribute__((always_inline)) {
+                constexpr int kb = decltype(kb_t)::value;
+                const bf16x8 ak = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img_kp + ra[kb] + jo));
+                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ak, qf[kb], s, 0, 0, 0);
+                if constexpr (SERIES == 1) {
+                    const bf16x8 ao = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(img_do + ra[kb] + jo));
+                    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, vf[kb], dp, 0, 0, 0);
+                }
+            });
+            unsigned bk[8];   // B operand of the second product: Pd (A) or dS (B) of this block as bf16 pairs
+#pragma unroll
+            for (int c4 = 0; c4 < 4; ++c4) {
+                const int key0 = 32 * jb + 8 * c4 + 4 * hf;   // inside the chunk; C.k0 + key0 of all keys
+                f32x4 mk = {1.f, 1.f, 1.f, 1.f};
+                if (!FAST && mrow) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) mk[e] = (key0 + e < P.k) ? mrow[key0 + e] : 0.f;
+                } else if (P.drop.thresh) {
+                    const snf::philox_f4 m4 = snf::dropout_mask4(P.drop, a, P.n, lrow, C.k_total, C.k0 + key0);
+                    mk = f32x4{m4[0], m4[1], m4[2], m4[3]};
+                }
+                f32x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float pv = __builtin_amdgcn_exp2f(fmaf(s[4 * c4 + e], c_exp, -lse2));
+                    if constexpr (SERIES == 0)
+                        o[e] = pv * mk[e];                                       // Pd = P o M
+                    else
+                        o[e] = pv * (dp[4 * c4 + e] * mk[e] - dtot) * P.scale;   // dS = P o (dP - D) * scale, dP = dPd o M
+                }
+                const unsigned o01 = pack2(o[0], o[1]), o23 = pack2(o[2], o[3]);
+                bk[2 * c4] = o01;
+                bk[2 * c4 + 1] = o23;
+                if constexpr (SERIES == 1) {
+                    if (rvalid) {
+                        if constexpr (FAST) {
+                            if (!tail || key0 < P.k) *reinterpret_cast<uint2*>(dsrow16 + key0) = uint2{o01, o23};
+                        } else if (P.ds_bf16) {
+                            if (vec_ok) {
+                                if (key0 < P.k) *reinterpret_cast<uint2*>(dsrow16 + key0) = uint2{o01, o23};
+                            } else {
+                                const unsigned short hv[4] = {(unsigned short)(o01 & 0xffffu), (unsigned short)(o01 >> 16),
+                                                              (unsigned short)(o23 & 0xffffu), (unsigned short)(o23 >> 16)};
+#pragma unroll
+                                for (int e = 0; e < 4; ++e)
+                                    if (key0 + e < P.k) dsrow16[key0 + e] = hv[e];
+                            }
+                        } else if (vec_ok) {
+                            if (key0 < P.k) *reinterpret_cast<f32x4*>(dsrow + key0) = o;
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                if (key0 + e < P.k) dsrow[key0 + e] = o[e];
+                        }
+                    }
+                }
+            }
+            // X^T[col, row] += T^T B^T: k-step = 16 keys (registers 4u .. 4u + 3 of the block)
+            static_for<0, 2>([&](auto u_t) __attribute__((always_inline)) {
+                constexpr int u = decltype(u_t)::value;
+                const u32x4 bb = {bk[4 * u], bk[4 * u + 1], bk[4 * u + 2], bk[4 * u + 3]};
+                const int koff = jo + 16 * u * RP;
+                static_for<0, NCB>([&](auto db_t) __attribute__((always_inline)) {
+                    constexpr int db = decltype(db_t)::value;
+                    const bf16x8 at = tr_frag(img_t + rt0[db] + koff, img_t + rt1[db] + koff);
+                    acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at, __builtin_bit_cast(bf16x8, bb), acc[db], 0, 0, 0);
+                });
+            });
+            // keep the key blocks apart, as in the single-chunk kernel
+            __builtin_amdgcn_sched_barrier(0);
+        }
+
+        if constexpr (SERIES == 0) {
+            if (C.last) {   // D = V . dV per head: the lane's V row in the accumulators' column layout, one cross-half exchange
+                float dpart = 0.f;
+                const QT* vp = vg + (int64_t)lrow * P.ldv + a * DK + 4 * hf;
+#pragma unroll
+                for (int db = 0; db < NCB; ++db)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        float vv[4];
+                        load4_bf16(vp + 32 * db + 8 * g, vv);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) dpart = fmaf(vv[e], acc[db][4 * g + e], dpart);
+                    }
+                const float dall = xhalf_sum(dpart);
+                if (rvalid && hf == 0) C.dsum[(int64_t)a * P.n + row] = dall;
+            }
+        }
+        if (rvalid) {
+            if (C.last && P.dqv_bf16) {   // the sums leave once, in the caller's dtype and pitch
+                unsigned short* op = reinterpret_cast<unsigned short*>(SERIES == 0 ? P.dv : P.dq) + (int64_t)row * P.ldd + a * DK + 4 * hf;
+#pragma unroll
+                for (int db = 0; db < NCB; ++db)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        uint2 pk;
+                        pk.x = pack_bf16x2(acc[db][4 * g], acc[db][4 * g + 1]);
+                        pk.y = pack_bf16x2(acc[db][4 * g + 2], acc[db][4 * g + 3]);
+                        *reinterpret_cast<uint2*>(op + 32 * db + 8 * g) = pk;
+                    }
+            } else {
+#pragma unroll
+                for (int db = 0; db < NCB; ++db)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        *reinterpret_cast<f32x4*>(accp + 32 * db + 8 * g) =
+                            f32x4{acc[db][4 * g], acc[db][4 * g + 1], acc[db][4 * g + 2], acc[db][4 * g + 3]};
+            }
+        }
+        if (++t == P.tiles_per_head) {
+            t = 0;
+            ++a;
+        }
+    }
+}
+
+// keys per chunk: as few chunks as the forward's make_chunks takes (224 keys at dk = 128, 256 at dk = 64, at most 8 chunks),
+// near-equal, every chunk start a multiple of 32
+constexpr int CH_MAX_CHUNKS = 8;
+inline bool make_bwd_chunks(int k, int dk, int* n_chunks, int* chunk_k) {
+    if (!(dk == 64 || dk == 128) || k < 1) return false;
+    const int kmax = dk == 128 ? 224 : 256;
+    const int nc = (k + kmax - 1) / kmax;
+    if (nc > CH_MAX_CHUNKS) return false;
+    const int ck = ((k + nc - 1) / nc + 31) / 32 * 32;
+    *chunk_k = ck;
+    *n_chunks = (k + ck - 1) / ck;
+    return true;
+}
+inline size_t chunked_acc_bytes(int64_t n, int h, int dk) { return ((size_t)n * h * dk * sizeof(float) + 255) / 256 * 256; }
+
+template <int DK, typename QT, int SERIES, bool FAST>
+int launch_chunk(const ChunkParams& C, int num_wg, hipStream_t s) {
+    constexpr size_t lds_max = (size_t)2 * 32 * (DK == 128 ? 7 : 8) * 2 * DK;
+    const size_t lds = (size_t)2 * 32 * C.nkb * 2 * DK;
+    auto kern = sparse_attn_bwd_chunk_kernel<DK, QT, SERIES, FAST>;
+    static thread_local unsigned long long attr_set_mask = 0;
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds_max, &attr_set_mask, "sparse_attn_bwd_mfma_chunked")) return rc;
+    hipLaunchKernelGGL(kern, dim3(num_wg), dim3(64 * CH_WAVES), lds, s, C);
+    return snf::check_launch("sparse_attn_bwd_chunk_kernel");
+}
+template <int DK, typename QT>
+int launch_chunk_series(const ChunkParams& C, int series, int num_wg, hipStream_t s) {
+    if (series == 0) return launch_chunk<DK, QT, 0, false>(C, num_wg, s);
+    if constexpr (std::is_same<QT, unsigned short>::value) {   // the training path: bf16 operands, bf16 dS, K % 4 == 0
+        if (C.b.ds_bf16 && !C.b.mask && (C.k_total & 3) == 0) return launch_chunk<DK, QT, 1, true>(C, num_wg, s);
+    }
+    return launch_chunk<DK, QT, 1, false>(C, num_wg, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -473,6 +758,101 @@ int snf_sparse_attn_bwd_mfma_ex(const void* q, int64_t ldq, const void* v, int64
     if (dk == 128)
         return qv_dtype == SNF_DT_F32 ? launch_bwd_nkb<128, float>(P, pl, s) : launch_bwd_nkb<128, unsigned short>(P, pl, s);
     return qv_dtype == SNF_DT_F32 ? launch_bwd_nkb<64, float>(P, pl, s) : launch_bwd_nkb<64, unsigned short>(P, pl, s);
+}
+
+size_t snf_sparse_attn_bwd_mfma_chunked_workspace_bytes(int64_t n, int k, int h, int dk, int dqv_dtype) {
+    int nc, ck;
+    if (n < 1 || h < 1 || !make_bwd_chunks(k, dk, &nc, &ck) || nc == 1) return 0;
+    const size_t dsum = ((size_t)h * n * sizeof(float) + 255) / 256 * 256;
+    return dsum + (dqv_dtype == SNF_DT_BF16 ? 2 * chunked_acc_bytes(n, h, dk) : 0);   // D | fp32 dV | fp32 dQ
+}
+
+int snf_sparse_attn_bwd_mfma_chunked(const void* q, int64_t ldq, const void* v, int64_t ldv, int qv_dtype, const float* kp,
+                                     const float* dout, const float* lse, const float* mask, float dropout_p, uint64_t seed,
+                                     uint64_t offset, int64_t n, int k, int h, int dk, float scale, void* dq, void* dv, int64_t ldd,
+                                     int dqv_dtype, void* ds, int ds_dtype, void* workspace, size_t workspace_bytes,
+                                     snf_stream_t stream) {
+    int nc = 0, ck = 0;
+    if (!make_bwd_chunks(k, dk, &nc, &ck)) {
+        snf::set_error("snf_sparse_attn_bwd_mfma_chunked: unsupported shape k=%d dk=%d (need dk == 128 with k <= %d or dk == 64 with "
+                       "k <= %d)", k, dk, CH_MAX_CHUNKS * 224, CH_MAX_CHUNKS * 256);
+        return SNF_EUNSUPPORTED;
+    }
+    if (nc == 1)   // one chunk: the single-launch kernel, bit for bit
+        return snf_sparse_attn_bwd_mfma_ex(q, ldq, v, ldv, qv_dtype, kp, dout, lse, mask, dropout_p, seed, offset, n, k, h, dk, scale, dq,
+                                           dv, ldd, dqv_dtype, ds, ds_dtype, stream);
+    SNF_REQUIRE(q && v && kp && dout && lse && dq && dv && ds, "snf_sparse_attn_bwd_mfma_chunked: null pointer");
+    SNF_REQUIRE(h >= 1 && n >= 1 && n <= 0x7fffff00ll, "snf_sparse_attn_bwd_mfma_chunked: bad shape n=%lld h=%d", (long long)n, h);
+    SNF_REQUIRE(dqv_dtype == SNF_DT_F32 || dqv_dtype == SNF_DT_BF16, "snf_sparse_attn_bwd_mfma_chunked: bad dq / dv dtype %d", dqv_dtype);
+    SNF_REQUIRE(ldd >= (int64_t)h * dk && ldd % (dqv_dtype == SNF_DT_BF16 ? 8 : 4) == 0,
+                "snf_sparse_attn_bwd_mfma_chunked: ldd=%lld must be >= h*dk and keep rows 16-byte aligned", (long long)ldd);
+    SNF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "snf_sparse_attn_bwd_mfma_chunked: dropout_p=%f outside [0, 1)", dropout_p);
+    SNF_REQUIRE(!(mask && dropout_p > 0.f), "snf_sparse_attn_bwd_mfma_chunked: pass a mask tensor OR (dropout_p, seed, offset), not both");
+    SNF_REQUIRE(qv_dtype == SNF_DT_F32 || qv_dtype == SNF_DT_BF16, "snf_sparse_attn_bwd_mfma_chunked: bad dtype %d", qv_dtype);
+    SNF_REQUIRE(ds_dtype == SNF_DT_F32 || ds_dtype == SNF_DT_BF16, "snf_sparse_attn_bwd_mfma_chunked: bad ds dtype %d", ds_dtype);
+    const int64_t d = (int64_t)h * dk;
+    const int align = qv_dtype == SNF_DT_BF16 ? 8 : 4;
+    SNF_REQUIRE(ldq >= d && ldv >= d && (ldq % align) == 0 && (ldv % align) == 0,
+                "snf_sparse_attn_bwd_mfma_chunked: ldq=%lld / ldv=%lld must be >= h*dk and keep rows 16-byte aligned", (long long)ldq,
+                (long long)ldv);
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    SNF_REQUIRE(al16(q) && al16(v) && al16(kp) && al16(dout) && al16(dq) && al16(dv) && al16(ds) && al16(workspace),
+                "snf_sparse_attn_bwd_mfma_chunked: buffers must be 16-byte aligned");
+    const size_t need = snf_sparse_attn_bwd_mfma_chunked_workspace_bytes(n, k, h, dk, dqv_dtype);
+    if (!workspace || workspace_bytes < need) {
+        snf::set_error("snf_sparse_attn_bwd_mfma_chunked: workspace %zu < %zu", workspace_bytes, need);
+        return SNF_EWORKSPACE;
+    }
+    const int64_t tph = (n + CH_ROWS - 1) / CH_ROWS, total = tph * h;
+    if (total > 0x7fffffff) {
+        snf::set_error("snf_sparse_attn_bwd_mfma_chunked: too many row tiles (n=%lld h=%d)", (long long)n, h);
+        return SNF_EUNSUPPORTED;
+    }
+    const int cus = snf::cu_count();
+    int64_t num_wg = total < cus ? total : cus;
+    const int64_t tpw = (total + num_wg - 1) / num_wg;
+    num_wg = (total + tpw - 1) / tpw;
+
+    unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
+    const size_t dsum_bytes = ((size_t)h * n * sizeof(float) + 255) / 256 * 256;
+    ChunkParams C;
+    BwdParams& P = C.b;
+    P.q = q, P.v = v, P.lse = lse, P.mask = mask;
+    P.drop = snf::make_dropout(dropout_p, seed, offset);
+    P.n = n, P.ldq = ldq, P.ldv = ldv, P.d = d, P.h = h, P.scale = scale;
+    P.dq = dq, P.dv = dv, P.ldd = ldd, P.dqv_bf16 = dqv_dtype == SNF_DT_BF16;
+    P.ds = ds, P.ds_bf16 = ds_dtype == SNF_DT_BF16;
+    P.tiles_per_head = (int)tph, P.tiles_per_wg = (int)tpw, P.total_tiles = (int)total;
+    C.k_total = k;
+    C.dsum = reinterpret_cast<float*>(wsb);
+    hipStream_t s = snf::as_stream(stream);
+    for (int series = 0; series < 2; ++series) {
+        // fp32 outputs are their own running sums; bf16 outputs are written once, by the last launch, from the workspace's
+        if (P.dqv_bf16) {
+            C.acc = reinterpret_cast<float*>(wsb + dsum_bytes + (series ? chunked_acc_bytes(n, h, dk) : 0));
+            C.ldacc = d;
+        } else {
+            C.acc = reinterpret_cast<float*>(series ? dq : dv);
+            C.ldacc = ldd;
+        }
+        for (int c = 0; c < nc; ++c) {
+            C.k0 = c * ck;
+            P.k = k - C.k0 < ck ? k - C.k0 : ck;
+            P.kp = kp + (int64_t)C.k0 * d;
+            P.dout = dout + (int64_t)C.k0 * d;
+            C.nkb = (P.k + 31) / 32;
+            C.first = c == 0, C.last = c == nc - 1;
+            int rc;
+            if (dk == 128)
+                rc = qv_dtype == SNF_DT_F32 ? launch_chunk_series<128, float>(C, series, (int)num_wg, s)
+                                            : launch_chunk_series<128, unsigned short>(C, series, (int)num_wg, s);
+            else
+                rc = qv_dtype == SNF_DT_F32 ? launch_chunk_series<64, float>(C, series, (int)num_wg, s)
+                                            : launch_chunk_series<64, unsigned short>(C, series, (int)num_wg, s);
+            if (rc) return rc;
+        }
+    }
+    return SNF_OK;
 }
 
 }  // extern "C"

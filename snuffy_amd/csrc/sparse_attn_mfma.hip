@@ -57,13 +57,12 @@ int snf_sparse_attn_fwd_mfma_dropout(const void* q, int64_t ldq, const void* v, 
                        MAX_CHUNKS * (dk == 128 ? 224 : 256));
         return SNF_EUNSUPPORTED;
     }
-    if (dropout_p > 0.f && cp.n_chunks > 1) {
-        // the in-register mask is keyed on the launch's own key index and the chunks' main passes differ in their outputs:
-        // the training shapes (k <= 224 / 256) are one chunk; more keys with dropout take the exact kernels + snf_dropout_mask_f32
-        snf::set_error("snf_sparse_attn_fwd_mfma: dropout is supported for one key chunk only (k <= %d at dk = %d), got k=%d",
-                       dk == 128 ? 224 : 256, dk, k);
-        return SNF_EUNSUPPORTED;
-    }
+    // one Philox call covers 4 consecutive keys of a row: with dropout the MAIN passes' chunks start on multiples of 4.  Rounding the
+    // chunk length up changes neither the chunk count nor the key blocks of a chunk (the workspace), and every chunk keeps a built
+    // key-block count (the last one holds more than chunk_k - 4 n_chunks keys).  The statistics passes keep the chunks they always
+    // had, and a main pass only sees the statistics combined over ALL chunks: lse and the normalised P are, bit for bit, those of
+    // the launch without dropout.
+    const int main_chunk_k = (dropout_p > 0.f && cp.n_chunks > 1) ? (cp.chunk_k + 3) & ~3 : cp.chunk_k;
     const int64_t d = (int64_t)h * dk;
     if (ldq >= (1 << 24) || ldv >= (1 << 24) || n * (ldq > ldv ? ldq : ldv) >= 0x7fffffffll) {
         snf::set_error("snf_sparse_attn_fwd_mfma: n * row pitch = %lld elements exceeds the 32-bit offsets of the kernel",
@@ -117,12 +116,13 @@ int snf_sparse_attn_fwd_mfma_dropout(const void* q, int64_t ldq, const void* v, 
         if (rc) return rc;
         kp16 = stage;
     }
-    auto plan_chunk = [&](int c, Plan* pl) -> int {   // keys of chunk c; fills the launch geometry
-        const int k0 = c * cp.chunk_k;
-        const int kc = (k - k0 < cp.chunk_k) ? k - k0 : cp.chunk_k;
+    auto plan_chunk = [&](int c, int chunk_k, Plan* pl) -> int {   // keys of chunk c; fills the launch geometry
+        const int k0 = c * chunk_k;
+        const int kc = (k - k0 < chunk_k) ? k - k0 : chunk_k;
         make_plan(n, kc, h, dk, pl);
         P.kp = kp16 + (int64_t)k0 * d;
         P.k = kc;
+        P.key0 = k0;
         P.tiles_per_head = pl->tiles_per_head;
         P.tiles_per_wg = pl->tiles_per_wg;
         P.total_tiles = pl->total_tiles;
@@ -135,7 +135,7 @@ int snf_sparse_attn_fwd_mfma_dropout(const void* q, int64_t ldq, const void* v, 
         P.lse = nullptr;
         P.stats = nullptr;
         for (int c = 0; c < cp.n_chunks; ++c) {
-            plan_chunk(c, &pl);
+            plan_chunk(c, cp.chunk_k, &pl);
             P.stats_out = stats + (size_t)c * h * n * 2;
             int rc = dk == 128 ? snf::attn_launch_dk128(qv_dtype, true, P, pl, nullptr, s)
                                : snf::attn_launch_dk64(qv_dtype, true, P, pl, nullptr, s);
@@ -145,7 +145,7 @@ int snf_sparse_attn_fwd_mfma_dropout(const void* q, int64_t ldq, const void* v, 
     P.stats = stats;
     P.stats_out = nullptr;
     for (int c = 0; c < cp.n_chunks; ++c) {
-        const int k0 = plan_chunk(c, &pl);
+        const int k0 = plan_chunk(c, main_chunk_k, &pl);
         P.attn = attn ? attn + k0 : nullptr;
         P.lse = c == 0 ? lse : nullptr;
         float* out_c = out + (int64_t)k0 * d;
@@ -233,6 +233,7 @@ int snf_sparse_attn_fwd_mfma_varlen(const void* q, int64_t ldq, const void* v, i
     P.tiles_per_head = P.tiles_per_wg = P.total_tiles = P.seg_count = 0;   // per bag, from the table
     P.trace = nullptr, P.trace_wg = 0;
     P.drop = snf::make_dropout(0.f, 0, 0);
+    P.key0 = 0;
     P.n_stride = total;
     P.vl = table_dev, P.vl_bags = bags;
     P.out_direct = out;

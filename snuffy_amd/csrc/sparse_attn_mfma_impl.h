@@ -63,6 +63,7 @@ struct AttnParams {
     // registers (philox.h) and applied to the normalised probabilities before they are published -- O and the returned A
     // are those of the dropped P, as in the reference.  thresh == 0: off.  Only the AUX variants look at it.
     snf::DropoutState drop;
+    int key0;          // first key of this launch among all keys (key-chunked launches; the dropout mask is keyed on it), else 0
     int64_t n_stride;  // rows per head of attn / lse (= n for one bag; the packed row count of a varlen launch)
     // varlen launch (many bags in one grid, VL kernels): table of VL_DESC ints per bag, then the bag of every workgroup
     const int* vl;
@@ -442,7 +443,7 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
                     f32x2 p23 = f32x2{s_acc[jb][4 * c4 + 2], s_acc[jb][4 * c4 + 3]} * inv2;
                     if constexpr (AUX) {
                         if (P.drop.thresh) {   // training: drop probabilities (wave-uniform branch, never taken in inference)
-                            const snf::philox_f4 mk = snf::dropout_mask4(P.drop, a, P.n, row, (int)P.attn_ld, 32 * jb + 8 * c4 + 4 * hf);
+                            const snf::philox_f4 mk = snf::dropout_mask4(P.drop, a, P.n, row, (int)P.attn_ld, P.key0 + 32 * jb + 8 * c4 + 4 * hf);
                             p01 *= f32x2{mk[0], mk[1]};
                             p23 *= f32x2{mk[2], mk[3]};
                         }
@@ -888,7 +889,8 @@ inline bool make_varlen_plan(const int64_t* offsets, int bags, int k, int h, int
         break;
 template <int DK, typename QT>
 int launch_nkb(const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
-    const bool aux = P.attn != nullptr || P.lse != nullptr;
+    // dropout lives in the AUX variants: the chunks behind the first have no lse to write and still drop their probabilities
+    const bool aux = P.attn != nullptr || P.lse != nullptr || P.drop.thresh != 0;
     if (P.stats) {   // key-chunked launch: chunk sizes are in (kmax/2, kmax] -> 4, 6, 7 or 8 key blocks
         switch (pl.nkb) {
 #ifndef SNF_ATTN_DEV

@@ -567,10 +567,18 @@ def mfma_attn_bwd_supported(k, dk):
     return (dk == 128 and 1 <= k <= 224) or (dk == 64 and 1 <= k <= 256)
 
 
+def mfma_attn_train_chunks_supported(k, dk):
+    """Key counts the MFMA attention trains at with in-kernel Philox dropout, forward and backward: the forward's up to 8 key chunks
+    (snf_sparse_attn_fwd_mfma_dropout over chunks, snf_sparse_attn_bwd_mfma_chunked).  One chunk is what mfma_attn_dropout_supported
+    and mfma_attn_bwd_supported describe."""
+    return (dk == 128 and 1 <= k <= 8 * 224) or (dk == 64 and 1 <= k <= 8 * 256)
+
+
 def sparse_attn_bwd_mfma(q, v, kp, dout, lse, h, mask=None, scale=None, dropout=None, fused_bf16_grads=False):
     """MFMA backward (bf16 operands): (dq [n,d] f32, dkp [k,d] f32, dv [n,d] f32) from q, v (f32 or bf16, row-strided views
     allowed), kp [k,d] f32, dout [k,d] f32 and the forward's lse [h,n].  mask: dropout keep-mask / (1 - p) or None.
-    fused_bf16_grads: dq and dv are the two column halves of ONE bf16 buffer [n, 2 d] (returned as views of it)."""
+    fused_bf16_grads: dq and dv are the two column halves of ONE bf16 buffer [n, 2 d] (returned as views of it).
+    More keys than one launch holds (mfma_attn_bwd_supported) run over key chunks, snf_sparse_attn_bwd_mfma_chunked."""
     if q.dtype not in (torch.float32, torch.bfloat16) or v.dtype != q.dtype:
         raise TypeError("sparse_attn_bwd_mfma: q and v must both be float32 or both bfloat16")
     q = _rows16(q, "q")
@@ -598,10 +606,18 @@ def sparse_attn_bwd_mfma(q, v, kp, dout, lse, h, mask=None, scale=None, dropout=
     ds = torch.empty(h, n, k, dtype=torch.bfloat16 if bf16 else torch.float32, device=q.device)
     dt = DT_F32 if q.dtype == torch.float32 else DT_BF16
     pdrop, seed, offset = dropout if dropout is not None else (0.0, 0, 0)
-    check(lib.snf_sparse_attn_bwd_mfma_ex(_p(q), q.stride(0), _p(v), v.stride(0), dt, _p(kp), _p(dout), _p(lse), _p(mask),
-                                          float(pdrop), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), n, k, h, dk,
-                                          float(scale), _p(dq), _p(dv), ldd, gdt, _p(ds), DT_BF16 if bf16 else DT_F32, _stream()),
-          "snf_sparse_attn_bwd_mfma")
+    if mfma_attn_bwd_supported(k, dk) or not mfma_attn_train_chunks_supported(k, dk):   # one chunk (or the library's own refusal)
+        check(lib.snf_sparse_attn_bwd_mfma_ex(_p(q), q.stride(0), _p(v), v.stride(0), dt, _p(kp), _p(dout), _p(lse), _p(mask),
+                                              float(pdrop), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), n, k, h, dk,
+                                              float(scale), _p(dq), _p(dv), ldd, gdt, _p(ds), DT_BF16 if bf16 else DT_F32, _stream()),
+              "snf_sparse_attn_bwd_mfma")
+    else:
+        cwsb = lib.snf_sparse_attn_bwd_mfma_chunked_workspace_bytes(n, k, h, dk, gdt)
+        cws = _ws(cwsb, q.device)
+        check(lib.snf_sparse_attn_bwd_mfma_chunked(_p(q), q.stride(0), _p(v), v.stride(0), dt, _p(kp), _p(dout), _p(lse), _p(mask),
+                                                   float(pdrop), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), n, k, h, dk,
+                                                   float(scale), _p(dq), _p(dv), ldd, gdt, _p(ds), DT_BF16 if bf16 else DT_F32,
+                                                   _p(cws), cwsb, _stream()), "snf_sparse_attn_bwd_mfma_chunked")
     if bf16:
         # dKp = dS^T Q per head: a [k, dk] output over a contraction of n rows -- split over 16 row chunks (one batched GEMM,
         # partials summed in fp32) so that the library has 16 h tiles to spread instead of h (121 -> 85 us at config B)
@@ -634,8 +650,8 @@ def mfma_attn_supported(k, dk, n=None, ld=None):
 
 
 def mfma_attn_dropout_supported(k, dk):
-    """In-kernel Philox dropout (forward and the MFMA backward) covers ONE key chunk; more keys use the exact kernels with
-    the mask tensor of dropout_mask()."""
+    """One key chunk of the in-kernel Philox dropout (forward and the single-launch MFMA backward); more keys, up to 8 chunks:
+    mfma_attn_train_chunks_supported."""
     return (dk == 64 and 1 <= k <= 256) or (dk == 128 and 1 <= k <= 224)
 
 
@@ -1136,9 +1152,9 @@ def sparse_attn_fwd_mfma(q, v, kp, n, h, scale=None, need_attn=False, need_lse=F
     dt = DT_F32 if q.dtype == torch.float32 else DT_BF16
     kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
     pdrop, seed, offset = dropout if dropout is not None else (0.0, 0, 0)
-    if pdrop > 0 and not mfma_attn_dropout_supported(k, dk):
-        raise ValueError("sparse_attn_fwd_mfma: in-kernel dropout needs a single key chunk (k <= %d at dk = %d), got k = %d"
-                         % (224 if dk == 128 else 256, dk, k))
+    if pdrop > 0 and not mfma_attn_train_chunks_supported(k, dk):
+        raise ValueError("sparse_attn_fwd_mfma: in-kernel dropout needs at most 8 key chunks (k <= %d at dk = %d), got k = %d"
+                         % (8 * (224 if dk == 128 else 256), dk, k))
     check(lib.snf_sparse_attn_fwd_mfma_dropout(_p(q), q.stride(0), _p(v), v.stride(0), dt, _p(kp), kdt, n, k, h, dk, float(scale),
                                                _p(out), _p(attn), _p(lse), float(pdrop), int(seed) & (2 ** 64 - 1),
                                                int(offset) & (2 ** 64 - 1), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_mfma")
