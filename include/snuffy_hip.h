@@ -273,8 +273,8 @@ int snf_ln_mean_head_f32(const float* z, int64_t n, int d, const void* add_bf16,
  *       (ldq, ldv >= d in elements, rows 16-byte aligned: q and v may be the two column halves of ONE fused
  *       projection output [n, 2d]), both of dtype qv_dtype (f32 converted in registers, or bf16); kp [k, d] of
  *       dtype kp_dtype: bf16 is read as it is, f32 is rounded to bf16 into the workspace first (one small launch).
- *       One launch holds 256 (dk == 64) / 224 (dk == 128) keys (Kp + P + V images share the 160 KiB LDS); more keys --
- *       up to 8 such chunks, k <= 2048 / 1792 -- run as key chunks: a statistics launch per chunk (row max / sum) and a
+ *       One launch holds 256 (dk == 64) / 224 (dk == 128) / 128 (dk == 192) keys (Kp + P + V images share the 160 KiB LDS); more
+ *       keys -- up to 8 such chunks, k <= 2048 / 1792 / 1024 -- run as key chunks: a statistics launch per chunk (row max / sum) and a
  *       full launch per chunk normalising with the statistics of all chunks, so the softmax stays exact.
  *       Other dk / larger k: SNF_EUNSUPPORTED, the caller picks snf_sparse_attn_fwd_f32.
  *   workspace: deterministic cross-workgroup reduction of the [h, k, dk] accumulators.
@@ -414,7 +414,10 @@ int snf_sparse_attn_bwd_mfma_ex(const void* q, int64_t ldq, const void* v, int64
  * [h, n, k], dQ summed the same way.  A wave owns its rows in every launch and the chunks are added in launch order: no atomics,
  * bit-reproducible.  The dropout mask -- tensor or (dropout_p, seed, offset) -- is keyed on the key index among ALL keys, as
  * snf_dropout_mask_f32 writes it.  Arguments as snf_sparse_attn_bwd_mfma_ex, plus the workspace (D, and the fp32 sums when dq / dv
- * leave as bf16; fp32 dq / dv are summed in place).  One chunk: forwards to snf_sparse_attn_bwd_mfma_ex (workspace may be NULL). */
+ * leave as bf16; fp32 dq / dv are summed in place).  One chunk: forwards to snf_sparse_attn_bwd_mfma_ex (workspace may be NULL).
+ * dk == 192 with k <= 8 x 128 (the forward's domain there) exists in this form only: chunks of up to 192 keys (two images of 144 KiB),
+ * one launch per series even for a single chunk (the workspace is always needed); snf_sparse_attn_bwd_mfma[_ex] refuse dk == 192.
+ * There dS = (bf16(P o M) o dPd - P D) * scale, the rounded factor being the one D was summed with: rows of dS sum to 0 in fp32. */
 size_t snf_sparse_attn_bwd_mfma_chunked_workspace_bytes(int64_t n, int k, int h, int dk, int dqv_dtype);
 int snf_sparse_attn_bwd_mfma_chunked(const void* q, int64_t ldq, const void* v, int64_t ldv, int qv_dtype, const float* kp,
                                      const float* dout, const float* lse, const float* mask, float dropout_p, uint64_t seed,

@@ -29,6 +29,10 @@ FUSED_BF16_ENCODER_DROPOUT = True
 # in-kernel dropout and backward over chunks) and at head widths that ride zero-padded to 64 / 128 (functional.head_pad: the README
 # recipes' dk = 96); False: such layers take the generic autograd chain, as before (fused_layer0_chunked_ok)
 FUSED_BF16_KEY_CHUNKS = True
+# the fused first-layer bf16 chain at head width 192 (D = 768 with h = 4, the README's MAE recipe: the MFMA attention's dk = 192 kernels,
+# no padding); False: such layers take the generic autograd chain, as before (fused_layer0_dk192_ok).  Ships off, like
+# functional.MFMA_ATTN_DK192: not timed against the generic chain yet (tools/attn_dk192_time.py)
+FUSED_BF16_DK192 = False
 # fp32 training: the same for the fp32-class arithmetic (EncoderLayer0X3Fn, round 5)
 FUSED_X3_TRAINING = True
 # ... on the one-pass kernels (round 6): activations and gradients as interleaved hl images (4 bytes per element instead of the 6 of
@@ -543,7 +547,8 @@ def fused_layer0_train_ok(layer, n, d, k=None):
 def fused_layer0_chunked_ok(layer, n, d, k=None):
     """EncoderLayer0Bf16Fn takes the layer beyond fused_layer0_train_ok (FUSED_BF16_KEY_CHUNKS): the same settings (ReLU FFN, one eps, all
     parameters trainable, encoder dropout as fused_layer0_train_ok admits it) with up to 8 key chunks of the MFMA attention instead of one
-    and with a head width that is 64 or 128 after functional.head_pad.  dk = 192 (the README's MAE recipe) has no padded form."""
+    and with a head width that is 64 or 128 after functional.head_pad.  dk = 192 (the README's MAE recipe) has no padded form and is
+    declined here: it runs unpadded on kernel variants of its own, which fused_layer0_dk192_ok admits."""
     if not (FUSED_BF16_TRAINING and FUSED_BF16_KEY_CHUNKS):
         return False
     mha, ff = layer.self_attn, layer.feed_forward
@@ -567,13 +572,35 @@ def fused_layer0_chunked_ok(layer, n, d, k=None):
     return True
 
 
+def fused_layer0_dk192_ok(layer, n, d, k=None):
+    """EncoderLayer0Bf16Fn takes the layer at head width 192, unpadded (FUSED_BF16_DK192): the settings of fused_layer0_chunked_ok (ReLU
+    FFN, one eps, all parameters trainable, encoder dropout as admitted there) with the key counts of ops.mfma_attn_dk192_supported --
+    the forward over up to 8 chunks of 128 keys, the backward on the chunked kernel at any key count."""
+    if not (FUSED_BF16_TRAINING and FUSED_BF16_DK192):
+        return False
+    mha, ff = layer.self_attn, layer.feed_forward
+    n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
+    if ff.activation_name != "relu" or n0.eps != n1.eps or d % mha.h or d // mha.h != 192:
+        return False
+    if k is None:
+        k = min(int(layer.big_lambda), n)
+    if not (ops.mfma_attn_dk192_supported(k, n, 2 * d) and all(p.requires_grad for p in layer.parameters())):
+        return False
+    ps = _encoder_dropout_ps(layer)
+    if any(p != 0.0 for p in ps):
+        return (FUSED_BF16_ENCODER_DROPOUT and all(0.0 <= p < 1.0 for p in ps)
+                and ops.bf16_encoder_dropout_supported(n, d, ff.w_1.weight.shape[0]))
+    return True
+
+
 def fused_layer0_ok(x2, sel, layer, precision):
     """The first-layer chain applies: bf16, the bag is data (no gradient flows into x2), supported shape / settings;
     everything else keeps the generic autograd chain below."""
     if precision != "bf16" or x2.requires_grad or sel.numel() == 0:
         return False
     return (fused_layer0_train_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
-            or fused_layer0_chunked_ok(layer, x2.shape[0], x2.shape[1], sel.numel()))
+            or fused_layer0_chunked_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
+            or fused_layer0_dk192_ok(layer, x2.shape[0], x2.shape[1], sel.numel()))
 
 
 def _x3_train_weights(layer, hl=False):

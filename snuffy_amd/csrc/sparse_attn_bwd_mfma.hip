@@ -58,8 +58,16 @@ __device__ __forceinline__ float hi_f(unsigned u) { return __uint_as_float(u & 0
 // rotated by the row (so the 4 consecutive rows x 64 bytes of a transpose-read group fall into 4 different 64-byte bank
 // quarters: r & 3 for 256-byte rows, (r >> 1) & 1 for 128-byte rows, whose rows already alternate halves), the chunk inside
 // the block is XOR-ed with (r >> 2) & 3 (so the 16 rows of a ds_read_b128 service group hit 16 different bank quads).
+// 384-byte rows (DK = 192, the chunked kernel only) are one and a half bank rows: row r starts at bank 32 r mod 64, so the 64-byte
+// block at block position b covers the bank quarter (2 r + b) mod 4.  Block cb goes to position cb ^ ((r >> 1) & 1) (an XOR of the low
+// bit stays inside the row's 6 blocks): rows r0 .. r0 + 3 of a transpose-read group then use the quarters cb, cb + 2, cb ^ 1,
+// (cb ^ 1) + 2 (mod 4) -- four different ones, each bank once.  For a ds_read_b128 service group the 16-byte slot (of 16 per bank row)
+// is 4 * quarter + ((c & 3) ^ ((r >> 2) & 3)): the quarter is a bijection of r & 3, and the rows of a group that agree in r & 3
+// ({0, 12, 20, 24}, {4, 8, 16, 28}, ...) have four different (r >> 2) & 3 -- 16 rows, 16 slots.  Everything is periodic in 16 rows
+// (16 * 384 bytes = 24 bank rows), which the fragment addresses below rely on.
 template <int DK>
 __device__ __forceinline__ int img_pos(int row, int c) {
+    if constexpr (DK == 192) return 4 * ((c >> 2) ^ ((row >> 1) & 1)) + ((c & 3) ^ ((row >> 2) & 3));
     const int rot = DK == 128 ? (row & 3) : ((row >> 1) & 1);
     return 4 * (((c >> 2) + rot) & (DK / 32 - 1)) + ((c & 3) ^ ((row >> 2) & 3));
 }
@@ -413,7 +421,9 @@ int launch_bwd_nkb(const BwdParams& P, const BwdPlan& pl, hipStream_t s) {
 // serves every chunk length; 8 waves per workgroup (two per SIMD) overlap one wave's exponentials with the other's MFMAs.
 // The mask is keyed on the GLOBAL key index and the total key count, in registers (Philox) or from the [h, n, k] tensor; each
 // series uses it once, so the single-chunk kernel's sign-bit memory has nothing to save here.
-constexpr int CH_WAVES = 8, CH_ROWS = 32 * CH_WAVES;
+// dk = 192: 4 waves (one per SIMD, 512 registers each).  A row's 6 accumulators (96 registers) next to the Q and V fragments (48 + 48 in
+// series B) and s / dp (32) do not fit the 256 registers of two waves per SIMD: series B spilled 63 - 119 registers that way.
+constexpr int ch_waves(int dk) { return dk == 192 ? 4 : 8; }
 
 struct ChunkParams {
     BwdParams b;        // kp / dout point at the chunk's first key, b.k = keys of THIS chunk; mask / ds at column 0 of the full rows
@@ -437,7 +447,8 @@ __device__ __forceinline__ void load4_bf16(const unsigned short* p, float (&o)[4
 
 // SERIES 0 = A, 1 = B.  FAST (series B, the training path's shape): bf16 dS, K % 4 == 0, no mask tensor.
 template <int DK, typename QT, int SERIES, bool FAST>
-__global__ __launch_bounds__(64 * CH_WAVES, 1) void sparse_attn_bwd_chunk_kernel(ChunkParams C) {
+__global__ __launch_bounds__(64 * ch_waves(DK), 1) void sparse_attn_bwd_chunk_kernel(ChunkParams C) {
+    constexpr int CH_WAVES = ch_waves(DK), CH_ROWS = 32 * CH_WAVES;
     const BwdParams& P = C.b;
     constexpr int NKS = DK / 16, NCB = DK / 32, RP = 2 * DK, NCH = DK / 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -556,13 +567,27 @@ __global__ __launch_bounds__(64 * CH_WAVES, 1) void sparse_attn_bwd_chunk_kernel
                     mk = f32x4{m4[0], m4[1], m4[2], m4[3]};
                 }
                 f32x4 o;
+                float pvv[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float pv = __builtin_amdgcn_exp2f(fmaf(s[4 * c4 + e], c_exp, -lse2));
-                    if constexpr (SERIES == 0)
-                        o[e] = pv * mk[e];                                       // Pd = P o M
-                    else
-                        o[e] = pv * (dp[4 * c4 + e] * mk[e] - dtot) * P.scale;   // dS = P o (dP - D) * scale, dP = dPd o M
+                for (int e = 0; e < 4; ++e) pvv[e] = __builtin_amdgcn_exp2f(fmaf(s[4 * c4 + e], c_exp, -lse2));
+                if constexpr (SERIES == 1 && DK == 192) {
+                    // dS_j = (bf16(P_j M_j) dPd_j - P_j D) * scale.  D came out of series A as sum_j bf16(P_j M_j) dPd_j (bf16(P o M) is the
+                    // MFMA operand of dV), so the first term carries the SAME rounded factor: sum_j dS_j = D - D sum_j P_j = 0 to fp32
+                    // accuracy, and a row whose gradient cancels exactly (one key: P = 1, dS = 0) gives 0 instead of
+                    // (M - bf16(M)) dPd -- 2^-9 of a term that the true gradient does not contain.
+                    const unsigned r01 = pack2(pvv[0] * mk[0], pvv[1] * mk[1]), r23 = pack2(pvv[2] * mk[2], pvv[3] * mk[3]);
+                    const float pd[4] = {lo_f(r01), hi_f(r01), lo_f(r23), hi_f(r23)};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] = (pd[e] * dp[4 * c4 + e] - pvv[e] * dtot) * P.scale;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float pv = pvv[e];
+                        if constexpr (SERIES == 0)
+                            o[e] = pv * mk[e];                                       // Pd = P o M
+                        else
+                            o[e] = pv * (dp[4 * c4 + e] * mk[e] - dtot) * P.scale;   // dS = P o (dP - D) * scale, dP = dPd o M
+                    }
                 }
                 const unsigned o01 = pack2(o[0], o[1]), o23 = pack2(o[2], o[3]);
                 bk[2 * c4] = o01;
@@ -652,11 +677,14 @@ __global__ __launch_bounds__(64 * CH_WAVES, 1) void sparse_attn_bwd_chunk_kernel
 }
 
 // keys per chunk: as few chunks as the forward's make_chunks takes (224 keys at dk = 128, 256 at dk = 64, at most 8 chunks),
-// near-equal, every chunk start a multiple of 32
+// near-equal, every chunk start a multiple of 32.  dk = 192: two images of 32 nkb rows x 384 bytes fit 160 KiB up to nkb = 6
+// (144 KiB) = 192 keys per chunk -- fewer chunks than the forward's 128-key ones; the key range stays the forward's, k <= 8 * 128.
 constexpr int CH_MAX_CHUNKS = 8;
+constexpr int bwd_chunk_kmax(int dk) { return dk == 64 ? 256 : dk == 128 ? 224 : dk == 192 ? 192 : 0; }
+constexpr int bwd_chunk_klimit(int dk) { return dk == 192 ? 8 * 128 : CH_MAX_CHUNKS * bwd_chunk_kmax(dk); }
 inline bool make_bwd_chunks(int k, int dk, int* n_chunks, int* chunk_k) {
-    if (!(dk == 64 || dk == 128) || k < 1) return false;
-    const int kmax = dk == 128 ? 224 : 256;
+    const int kmax = bwd_chunk_kmax(dk);
+    if (!kmax || k < 1 || k > bwd_chunk_klimit(dk)) return false;
     const int nc = (k + kmax - 1) / kmax;
     if (nc > CH_MAX_CHUNKS) return false;
     const int ck = ((k + nc - 1) / nc + 31) / 32 * 32;
@@ -668,12 +696,12 @@ inline size_t chunked_acc_bytes(int64_t n, int h, int dk) { return ((size_t)n * 
 
 template <int DK, typename QT, int SERIES, bool FAST>
 int launch_chunk(const ChunkParams& C, int num_wg, hipStream_t s) {
-    constexpr size_t lds_max = (size_t)2 * 32 * (DK == 128 ? 7 : 8) * 2 * DK;
+    constexpr size_t lds_max = (size_t)2 * (bwd_chunk_kmax(DK)) * 2 * DK;
     const size_t lds = (size_t)2 * 32 * C.nkb * 2 * DK;
     auto kern = sparse_attn_bwd_chunk_kernel<DK, QT, SERIES, FAST>;
     static thread_local unsigned long long attr_set_mask = 0;
     if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds_max, &attr_set_mask, "sparse_attn_bwd_mfma_chunked")) return rc;
-    hipLaunchKernelGGL(kern, dim3(num_wg), dim3(64 * CH_WAVES), lds, s, C);
+    hipLaunchKernelGGL(kern, dim3(num_wg), dim3(64 * ch_waves(DK)), lds, s, C);
     return snf::check_launch("sparse_attn_bwd_chunk_kernel");
 }
 template <int DK, typename QT>
@@ -762,7 +790,8 @@ int snf_sparse_attn_bwd_mfma_ex(const void* q, int64_t ldq, const void* v, int64
 
 size_t snf_sparse_attn_bwd_mfma_chunked_workspace_bytes(int64_t n, int k, int h, int dk, int dqv_dtype) {
     int nc, ck;
-    if (n < 1 || h < 1 || !make_bwd_chunks(k, dk, &nc, &ck) || nc == 1) return 0;
+    // one chunk is the single-launch kernel's (no workspace) -- except at dk = 192, which only the chunked kernel is built for
+    if (n < 1 || h < 1 || !make_bwd_chunks(k, dk, &nc, &ck) || (nc == 1 && dk != 192)) return 0;
     const size_t dsum = ((size_t)h * n * sizeof(float) + 255) / 256 * 256;
     return dsum + (dqv_dtype == SNF_DT_BF16 ? 2 * chunked_acc_bytes(n, h, dk) : 0);   // D | fp32 dV | fp32 dQ
 }
@@ -774,11 +803,11 @@ int snf_sparse_attn_bwd_mfma_chunked(const void* q, int64_t ldq, const void* v, 
                                      snf_stream_t stream) {
     int nc = 0, ck = 0;
     if (!make_bwd_chunks(k, dk, &nc, &ck)) {
-        snf::set_error("snf_sparse_attn_bwd_mfma_chunked: unsupported shape k=%d dk=%d (need dk == 128 with k <= %d or dk == 64 with "
-                       "k <= %d)", k, dk, CH_MAX_CHUNKS * 224, CH_MAX_CHUNKS * 256);
+        snf::set_error("snf_sparse_attn_bwd_mfma_chunked: unsupported shape k=%d dk=%d (need dk == 128 with k <= %d, dk == 64 with "
+                       "k <= %d or dk == 192 with k <= %d)", k, dk, bwd_chunk_klimit(128), bwd_chunk_klimit(64), bwd_chunk_klimit(192));
         return SNF_EUNSUPPORTED;
     }
-    if (nc == 1)   // one chunk: the single-launch kernel, bit for bit
+    if (nc == 1 && dk != 192)   // one chunk: the single-launch kernel, bit for bit (dk = 192 has none: one launch per series below)
         return snf_sparse_attn_bwd_mfma_ex(q, ldq, v, ldv, qv_dtype, kp, dout, lse, mask, dropout_p, seed, offset, n, k, h, dk, scale, dq,
                                            dv, ldd, dqv_dtype, ds, ds_dtype, stream);
     SNF_REQUIRE(q && v && kp && dout && lse && dq && dv && ds, "snf_sparse_attn_bwd_mfma_chunked: null pointer");
@@ -803,7 +832,8 @@ int snf_sparse_attn_bwd_mfma_chunked(const void* q, int64_t ldq, const void* v, 
         snf::set_error("snf_sparse_attn_bwd_mfma_chunked: workspace %zu < %zu", workspace_bytes, need);
         return SNF_EWORKSPACE;
     }
-    const int64_t tph = (n + CH_ROWS - 1) / CH_ROWS, total = tph * h;
+    const int ch_rows = 32 * ch_waves(dk);   // query rows per workgroup step
+    const int64_t tph = (n + ch_rows - 1) / ch_rows, total = tph * h;
     if (total > 0x7fffffff) {
         snf::set_error("snf_sparse_attn_bwd_mfma_chunked: too many row tiles (n=%lld h=%d)", (long long)n, h);
         return SNF_EUNSUPPORTED;
@@ -846,6 +876,9 @@ int snf_sparse_attn_bwd_mfma_chunked(const void* q, int64_t ldq, const void* v, 
             if (dk == 128)
                 rc = qv_dtype == SNF_DT_F32 ? launch_chunk_series<128, float>(C, series, (int)num_wg, s)
                                             : launch_chunk_series<128, unsigned short>(C, series, (int)num_wg, s);
+            else if (dk == 192)
+                rc = qv_dtype == SNF_DT_F32 ? launch_chunk_series<192, float>(C, series, (int)num_wg, s)
+                                            : launch_chunk_series<192, unsigned short>(C, series, (int)num_wg, s);
             else
                 rc = qv_dtype == SNF_DT_F32 ? launch_chunk_series<64, float>(C, series, (int)num_wg, s)
                                             : launch_chunk_series<64, unsigned short>(C, series, (int)num_wg, s);

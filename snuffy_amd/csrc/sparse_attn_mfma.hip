@@ -16,6 +16,13 @@ int attn_launch_dk128(int qv_dtype, bool stats_pass, const AttnParams& P, const 
 }
 }  // namespace snf
 
+// the translation unit of the head width (make_chunks admitted dk: 64, 128 or 192)
+static int attn_launch(int dk, int qv_dtype, bool stats_pass, const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
+    if (dk == 128) return snf::attn_launch_dk128(qv_dtype, stats_pass, P, pl, out, s);
+    if (dk == 192) return snf::attn_launch_dk192(qv_dtype, stats_pass, P, pl, out, s);
+    return snf::attn_launch_dk64(qv_dtype, stats_pass, P, pl, out, s);
+}
+
 extern "C" {
 
 // debug only (not part of the public header): device buffer of >= 64*8*4 u64 receiving s_memtime stamps of workgroup 0
@@ -53,8 +60,8 @@ int snf_sparse_attn_fwd_mfma_dropout(const void* q, int64_t ldq, const void* v, 
     ChunkPlan cp;
     size_t partial_bytes = 0, stats_bytes = 0;
     if (!make_chunks(k, dk, &cp) || !chunked_workspace(n, k, h, dk, &partial_bytes, &stats_bytes)) {
-        snf::set_error("snf_sparse_attn_fwd_mfma: unsupported shape k=%d dk=%d (need dk in {64, 128} and k <= %d)", k, dk,
-                       MAX_CHUNKS * (dk == 128 ? 224 : 256));
+        snf::set_error("snf_sparse_attn_fwd_mfma: unsupported shape k=%d dk=%d (need dk in {64, 128, 192} and k <= %d keys "
+                       "= %d chunks of %d)", k, dk, MAX_CHUNKS * attn_kmax(dk), MAX_CHUNKS, attn_kmax(dk));
         return SNF_EUNSUPPORTED;
     }
     // one Philox call covers 4 consecutive keys of a row: with dropout the MAIN passes' chunks start on multiples of 4.  Rounding the
@@ -137,8 +144,7 @@ int snf_sparse_attn_fwd_mfma_dropout(const void* q, int64_t ldq, const void* v, 
         for (int c = 0; c < cp.n_chunks; ++c) {
             plan_chunk(c, cp.chunk_k, &pl);
             P.stats_out = stats + (size_t)c * h * n * 2;
-            int rc = dk == 128 ? snf::attn_launch_dk128(qv_dtype, true, P, pl, nullptr, s)
-                               : snf::attn_launch_dk64(qv_dtype, true, P, pl, nullptr, s);
+            int rc = attn_launch(dk, qv_dtype, true, P, pl, nullptr, s);
             if (rc) return rc;
         }
     }
@@ -149,8 +155,7 @@ int snf_sparse_attn_fwd_mfma_dropout(const void* q, int64_t ldq, const void* v, 
         P.attn = attn ? attn + k0 : nullptr;
         P.lse = c == 0 ? lse : nullptr;
         float* out_c = out + (int64_t)k0 * d;
-        int rc = dk == 128 ? snf::attn_launch_dk128(qv_dtype, false, P, pl, out_c, s)
-                           : snf::attn_launch_dk64(qv_dtype, false, P, pl, out_c, s);
+        int rc = attn_launch(dk, qv_dtype, false, P, pl, out_c, s);
         if (rc) return rc;
     }
     return SNF_OK;

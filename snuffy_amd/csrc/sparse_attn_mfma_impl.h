@@ -1,7 +1,7 @@
 #pragma once
 // K7 (fast form): Snuffy's sparse attention on the CDNA4 matrix cores.
-// (implementation header: compiled once per head width by sparse_attn_mfma.hip (dk = 128 + the C entry points) and
-// sparse_attn_mfma_dk64.hip, so the two halves of the ~80 kernel variants build in parallel)
+// (implementation header: compiled once per head width by sparse_attn_mfma.hip (dk = 128 + the C entry points),
+// sparse_attn_mfma_dk64.hip and sparse_attn_mfma_dk192.hip, so the kernel variants of the three widths build in parallel)
 //
 //   per head a:   P_a = softmax_j(Q_a Kp_a^T * scale)  [n, k]      O_a = P_a^T V_a  [k, dk]        (snuffy.py:160-168)
 //
@@ -84,6 +84,10 @@ using snf_attn::VarlenPlan;
 using snf_attn::p_row_bytes;
 
 constexpr int TILE_ROWS = 128;  // query rows per workgroup step (4 waves x 32)
+
+// keys ONE launch holds: the Kp + P + V images in the 160 KiB LDS of a CU (0: head width not built).  dk = 192: 4 key blocks,
+// Kp 4 * 12 * 1024 = 48 KiB + P 128 * p_row_bytes(4) = 40 KiB + V 128 * 384 = 48 KiB = 136 KiB (6 blocks would need 200 KiB)
+constexpr int attn_kmax(int dk) { return dk == 64 ? 256 : dk == 128 ? 224 : dk == 192 ? 128 : 0; }
 
 __device__ __forceinline__ bf16x8 zero_frag() {
     u32x4 z = {0u, 0u, 0u, 0u};
@@ -476,15 +480,34 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
     } else {
         // =========================================== pooling waves ===========================================
         const QT* __restrict__ vg = reinterpret_cast<const QT*>(P.v);
+        // DK = 192 (6 column blocks: not a power of two) has its own tile ownership: wave w works on ONE key block, kb = w % NKB,
+        // and on the column blocks cb = w / NKB + (4 / NKB) ti of it (all six with NKB = 4) -- one P^T fragment per 16-row
+        // k-step feeds all of the wave's MFMAs of that step, the V fragment changes per MFMA.  The partial tiles keep the order
+        // t_idx = kb * NCB + cb that flush / reduce_partials_kernel use.
+        constexpr bool D192 = DK == 192;
         const int cb = (NCB == 4) ? w : (w & (NCB - 1));
+        auto tile_of = [&](int ti) __attribute__((always_inline)) -> int {
+            if constexpr (D192)
+                return (w % NKB) * NCB + w / NKB + (4 / NKB) * ti;
+            else
+                return w + 4 * ti;
+        };
+        auto tile_ok = [&](int ti) __attribute__((always_inline)) -> bool {
+            if constexpr (D192)
+                return w / NKB + (4 / NKB) * ti < NCB;
+            else
+                return w + 4 * ti < NKB * NCB;
+        };
         // reader of the P image (GEMM2 A operand): lane = group g (16 lanes) x i; rows 8*(g>>1) + 4*s + (i>>2), chunk
         // 4*(g&1) + (i&3)
         const int rg = lane >> 4, ri = lane & 15;
         const int rr0 = 8 * (rg >> 1) + (ri >> 2), rr1 = rr0 + 4;
         const int rch = 4 * (rg & 1) + (ri & 3);
         // key block of output tile ti of this wave = ti * (4 / NCB) + w / NCB: the wave-dependent part goes into the base
-        const unsigned char* rbase0 = lds_p + rr0 * RS + 8 * (rch ^ ((rr0 >> 1) & 7)) + 64 * (w / NCB);
-        const unsigned char* rbase1 = lds_p + rr1 * RS + 8 * (rch ^ ((rr1 >> 1) & 7)) + 64 * (w / NCB);
+        // (DK = 192: w % NKB for every tile of the wave)
+        const int pkb = D192 ? (w % NKB) : (w / NCB);
+        const unsigned char* rbase0 = lds_p + rr0 * RS + 8 * (rch ^ ((rr0 >> 1) & 7)) + 64 * pkb;
+        const unsigned char* rbase1 = lds_p + rr1 * RS + 8 * (rch ^ ((rr1 >> 1) & 7)) + 64 * pkb;
 
         // ---- V image.  V arrives ROW-major (it comes out of the same GEMM as Q): each pooling wave fetches 32 rows of the
         // tile with fully coalesced 16-byte loads (one row = DK/8 chunks of 8 columns), parks them in registers until the
@@ -493,25 +516,58 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
         // padding: chunk c of row r sits at chunk position (c + 4 rot(r)) mod NCH, which spreads the 4 rows x 64 bytes of a
         // transpose-read group over all 64 banks (rot = r & 3 for DK = 128, (r >> 1) & 1 for DK = 64: rows of 128 bytes
         // already alternate halves).
+        // DK = 192: a row is 384 bytes = 96 banks = one and a half bank rows, so row r starts at bank 32 r mod 64 and the 64-byte
+        // block at block position b of the row covers banks 16 ((2 r + b) mod 4) .. + 15.  Block cb of row r is stored at block
+        // position cb ^ ((r >> 1) & 1) (an XOR of the low bit stays inside the row's 6 blocks; in chunks: c ^ 4 ((r >> 1) & 1)).
+        // The 4 rows r0 .. r0 + 3 (r0 a multiple of 4) of a transpose-read group then use the bank quarters
+        //   cb, cb + 2, cb ^ 1, (cb ^ 1) + 2   (mod 4)
+        // -- cb and cb ^ 1 differ in bit 0, the + 2 flips bit 1: four different quarters, each bank once.  Rows 8 or 16 further on
+        // sit a whole number of bank rows away (8 * 384 = 12 * 256) with the same XOR, so the pattern holds for every group.  The
+        // 16-byte stores (8 lanes per group, 32 banks) write 8 consecutive chunks 8 m .. 8 m + 7 of ONE row (24 = 3 * 8 chunks per
+        // row): the XOR permutes them inside their 128 bytes, every bank once.
         constexpr int VRS = 2 * DK, NCH = DK / 8;     // row pitch (bytes), 16-byte chunks per row
-        constexpr int RPI = 64 / NCH, NVI = 32 / RPI; // rows per load instruction, load instructions per wave and tile
+        // loader: NLS load instructions cover RPI whole rows (DK = 192: 3 instructions = 192 chunks = 8 rows of 24)
+        constexpr int NLS = D192 ? 3 : 1;
+        constexpr int RPI = NLS * 64 / NCH, NVI = 32 / RPI * NLS;   // rows per instruction group, load instructions per wave and tile
         auto vrot = [](int r) __attribute__((always_inline)) -> int { return DK == 128 ? (r & 3) : ((r >> 1) & 1); };
-        const int vl_row = lane / NCH, vl_ch = lane % NCH;          // loader: row inside the instruction, chunk
-        const int vwaddr = (32 * w + vl_row) * VRS + 16 * ((vl_ch + 4 * vrot(vl_row)) & (NCH - 1));   // + i * RPI * VRS
+        auto vpos = [&](int r, int c) __attribute__((always_inline)) -> int {   // chunk position of chunk c in row r
+            if constexpr (D192)
+                return c ^ (4 * ((r >> 1) & 1));
+            else
+                return (c + 4 * vrot(r)) & (NCH - 1);
+        };
+        int vl_row[NLS], vl_ch[NLS], vwaddr[NLS];   // loader: row inside the instruction group, chunk, store offset (+ group * RPI * VRS)
+#pragma unroll
+        for (int s = 0; s < NLS; ++s) {
+            vl_row[s] = (64 * s + lane) / NCH;
+            vl_ch[s] = (64 * s + lane) % NCH;
+            vwaddr[s] = (32 * w + vl_row[s]) * VRS + 16 * vpos(vl_row[s], vl_ch[s]);
+        }
         const int vr0 = 8 * (rg >> 1) + (ri >> 2), vr1 = vr0 + 4;   // reader: rows of the two transpose-reads
         const int vrc = 4 * cb + 2 * (rg & 1) + ((ri & 3) >> 1);     // chunk of this lane's 4 columns, + 8 * (ri & 1) bytes
-        const unsigned char* vbase0 = lds_v + vr0 * VRS + 16 * ((vrc + 4 * vrot(vr0)) & (NCH - 1)) + 8 * (ri & 1);
-        const unsigned char* vbase1 = lds_v + vr1 * VRS + 16 * ((vrc + 4 * vrot(vr1)) & (NCH - 1)) + 8 * (ri & 1);
+        const unsigned char* vbase0 = lds_v + vr0 * VRS + 16 * vpos(vr0, D192 ? 0 : vrc) + 8 * (ri & 1);
+        const unsigned char* vbase1 = lds_v + vr1 * VRS + 16 * vpos(vr1, D192 ? 0 : vrc) + 8 * (ri & 1);
+        // DK = 192: one address per output tile of the wave (column block cb = w / NKB + (4 / NKB) ti, clamped for the tiles that
+        // do not exist); the second transpose-read is 4 rows = 4 * VRS bytes further on (vpos(r + 4, c) == vpos(r, c))
+        int vaddr[D192 ? NT : 1];
+        if constexpr (D192) {
+#pragma unroll
+            for (int ti = 0; ti < NT; ++ti) {
+                int cbt = w / NKB + (4 / NKB) * ti;
+                if (cbt > NCB - 1) cbt = NCB - 1;
+                vaddr[ti] = vr0 * VRS + 16 * vpos(vr0, 4 * cbt + 2 * (rg & 1) + ((ri & 3) >> 1)) + 8 * (ri & 1);
+            }
+        }
         const int ldv32 = (int)P.ldv;
         auto v_off = [&](int a_, int t_, int i) __attribute__((always_inline)) -> unsigned {
-            int vrow = t_ * TILE_ROWS + 32 * w + RPI * i + vl_row;
+            int vrow = t_ * TILE_ROWS + 32 * w + RPI * (i / NLS) + vl_row[i % NLS];
             if (vrow > n32 - 1) vrow = n32 - 1;
-            return __umul24((unsigned)vrow, (unsigned)ldv32) + (a_ * DK + 8 * vl_ch);
+            return __umul24((unsigned)vrow, (unsigned)ldv32) + (a_ * DK + 8 * vl_ch[i % NLS]);
         };
 
         f32x16 acc_o[NT];
         bf16x8 vld[NVI];  // this wave's 32 rows of V(f), in flight / parked until the images are free
-        bf16x8 vfr[2];    // B fragments of the current and the next GEMM2 k-step (read one k-step ahead)
+        bf16x8 vfr[D192 ? 4 : 2];   // B fragments of the current and the next GEMM2 k-step (read one k-step ahead; DK = 192: ring, below)
         // GEMM2 of the pending tile, MFMA m = sk * NT + ti  (sk = 16-row k-step of the tile, ti = output tile of the wave):
         // A = P^T fragment (key on the lane, 8 rows in registers), B = V fragment, both by transpose-read.  The P fragment of
         // MFMA m + 3 is requested before MFMA m issues (4-slot ring), the V fragment one whole k-step ahead.
@@ -528,6 +584,30 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
             constexpr int m = decltype(m_tag)::value;
             constexpr int sk = m / NT, ti = m % NT;
             const int t_idx = w + 4 * ti;  // tile = kb * NCB + cb ; cb == t_idx % NCB is constant per wave
+            if constexpr (D192) {
+                // the roles of the two rings are exchanged: the P fragment (key block fixed) is read one k-step ahead into
+                // pfr[sk & 1], the V fragment of MFMA m + 3 is requested before MFMA m issues (vfr = 4-slot ring)
+                auto v_read = [&](auto mm_tag) __attribute__((always_inline)) {
+                    constexpr int mm = decltype(mm_tag)::value;
+                    if constexpr (mm < M2) {
+                        constexpr int off = (mm / NT) * 16 * VRS;
+                        const unsigned char* vp = lds_v + vaddr[mm % NT];
+                        vfr[mm % 4] = tr_frag(vp + off, vp + off + 4 * VRS);
+                    }
+                };
+                if constexpr (m == 0) {
+                    pfr[0] = tr_frag(rbase0, rbase1);
+                    v_read(std::integral_constant<int, 0>{});
+                    v_read(std::integral_constant<int, 1>{});
+                    v_read(std::integral_constant<int, 2>{});
+                }
+                v_read(std::integral_constant<int, m + 3>{});
+                if constexpr (ti == 0 && sk + 1 < 8)
+                    pfr[(sk + 1) & 1] = tr_frag(rbase0 + (sk + 1) * 16 * RS, rbase1 + (sk + 1) * 16 * RS);
+                if (NT * 4 == NKB * NCB || tile_ok(ti))
+                    acc_o[ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pfr[sk & 1], vfr[m % 4], acc_o[ti], 0, 0, 0);
+                return;
+            }
             if constexpr (m == 0) {
                 vfr[0] = tr_frag(vbase0, vbase1);
                 p_read(std::integral_constant<int, 0>{});
@@ -552,7 +632,7 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
                     const int64_t ld = (int64_t)P.h * DK;
 #pragma unroll
                     for (int ti = 0; ti < NT; ++ti) {
-                        const int t_idx = w + 4 * ti;
+                        const int t_idx = w + 4 * ti;   // (varlen launches are built for DK = 64 / 128 only)
                         if (t_idx < NKB * NCB) {
                             const int kb_ = t_idx / NCB, cb_ = t_idx - kb_ * NCB;
                             float* dcol = P.out_direct + head * DK + 32 * cb_ + j;
@@ -570,8 +650,8 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
             float* dst = P.partial + ((int64_t)bid * P.seg_count + seg) * (int64_t)(NKB * NCB) * 1024;
 #pragma unroll
             for (int ti = 0; ti < NT; ++ti) {
-                const int t_idx = w + 4 * ti;
-                if (t_idx < NKB * NCB) {
+                const int t_idx = tile_of(ti);
+                if (tile_ok(ti)) {
                     const int key0 = 32 * (t_idx / NCB);
 #pragma unroll
                     for (int q4 = 0; q4 < 4; ++q4) {
@@ -635,7 +715,7 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
             stamp(7);
             static_for<0, NVI>([&](auto i_t) __attribute__((always_inline)) {
                 constexpr int i = decltype(i_t)::value;
-                *reinterpret_cast<u32x4*>(lds_v + vwaddr + i * RPI * VRS) = __builtin_bit_cast(u32x4, vld[i]);
+                *reinterpret_cast<u32x4*>(lds_v + vwaddr[i % NLS] + (i / NLS) * RPI * VRS) = __builtin_bit_cast(u32x4, vld[i]);
             });
             published = true;
             ++trace_it;
@@ -806,7 +886,8 @@ __global__ __launch_bounds__(64) void reduce_partials_kernel(const float* __rest
 
 
 inline bool make_plan(int64_t n, int k, int h, int dk, Plan* pl, bool packed = false) {
-    if (!(dk == 64 || dk == 128) || k < 1 || k > (dk == 128 ? 224 : 256)) return false;   // LDS: Kp + P + V images
+    if (k < 1 || k > attn_kmax(dk)) return false;   // LDS: Kp + P + V images
+    if (packed && dk == 192) return false;          // the varlen kernels are built for dk = 64 / 128 only
     int nkb = (k + 31) / 32;
     // instantiated key-block counts
     const int opts[] = {1, 2, 4, 6, 7, 8};
@@ -891,6 +972,26 @@ template <int DK, typename QT>
 int launch_nkb(const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
     // dropout lives in the AUX variants: the chunks behind the first have no lse to write and still drop their probabilities
     const bool aux = P.attn != nullptr || P.lse != nullptr || P.drop.thresh != 0;
+    if constexpr (DK == 192) {
+        // 128 keys per launch: key blocks 1, 2, 4.  The chunks of a key-chunked launch hold 61 .. 128 keys (61: the second of
+        // two chunks after the first was rounded up to a multiple of 4 for dropout) -> 2 or 4 blocks
+        if (P.stats) {
+            switch (pl.nkb) {
+                SNF_ATTN_CASE(2, true)
+                SNF_ATTN_CASE(4, true)
+                default: break;
+            }
+        } else {
+            switch (pl.nkb) {
+                SNF_ATTN_CASE(1, false)
+                SNF_ATTN_CASE(2, false)
+                SNF_ATTN_CASE(4, false)
+                default: break;
+            }
+        }
+        snf::set_error("sparse_attn_mfma: key-block count %d not built for dk = 192", pl.nkb);
+        return SNF_EUNSUPPORTED;
+    } else {
     if (P.stats) {   // key-chunked launch: chunk sizes are in (kmax/2, kmax] -> 4, 6, 7 or 8 key blocks
         switch (pl.nkb) {
 #ifndef SNF_ATTN_DEV
@@ -920,6 +1021,7 @@ int launch_nkb(const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
     }
     snf::set_error("sparse_attn_mfma: key-block count %d not built", pl.nkb);
     return SNF_EUNSUPPORTED;
+    }
 }
 #undef SNF_ATTN_CASE
 #undef SNF_ATTN_CASE8
@@ -936,16 +1038,24 @@ int launch_stats_variant(const AttnParams& P, const Plan& pl, hipStream_t s) {
 }
 template <int DK, typename QT>
 int launch_stats(const AttnParams& P, const Plan& pl, hipStream_t s) {
-    switch (pl.nkb) {
+    if constexpr (DK == 192) {   // chunks of 64 .. 128 keys
+        switch (pl.nkb) {
+            case 2: return launch_stats_variant<DK, 2, QT>(P, pl, s);
+            case 4: return launch_stats_variant<DK, 4, QT>(P, pl, s);
+            default: break;
+        }
+    } else {
+        switch (pl.nkb) {
 #ifndef SNF_ATTN_DEV
-        case 4: return launch_stats_variant<DK, 4, QT>(P, pl, s);
-        case 6: return launch_stats_variant<DK, 6, QT>(P, pl, s);
-        case 8:
-            if constexpr (DK == 64) return launch_stats_variant<DK, 8, QT>(P, pl, s);
-            break;
+            case 4: return launch_stats_variant<DK, 4, QT>(P, pl, s);
+            case 6: return launch_stats_variant<DK, 6, QT>(P, pl, s);
+            case 8:
+                if constexpr (DK == 64) return launch_stats_variant<DK, 8, QT>(P, pl, s);
+                break;
 #endif
-        case 7: return launch_stats_variant<DK, 7, QT>(P, pl, s);
-        default: break;
+            case 7: return launch_stats_variant<DK, 7, QT>(P, pl, s);
+            default: break;
+        }
     }
     snf::set_error("sparse_attn_stats: key-block count %d not built", pl.nkb);
     return SNF_EUNSUPPORTED;
@@ -969,8 +1079,8 @@ struct ChunkPlan {
     int n_chunks, chunk_k;   // chunk c covers keys [c * chunk_k, min(k, (c + 1) * chunk_k))
 };
 inline bool make_chunks(int k, int dk, ChunkPlan* cp) {
-    if (!(dk == 64 || dk == 128) || k < 1) return false;
-    const int kmax = dk == 128 ? 224 : 256;
+    const int kmax = attn_kmax(dk);
+    if (!kmax || k < 1) return false;
     const int nc = (k + kmax - 1) / kmax;
     if (nc > MAX_CHUNKS) return false;
     cp->n_chunks = nc;
@@ -995,6 +1105,8 @@ int attn_launch_dk128(int qv_dtype, bool stats_pass, const snf_attn::AttnParams&
                       hipStream_t s);
 int attn_launch_dk64(int qv_dtype, bool stats_pass, const snf_attn::AttnParams& P, const snf_attn::Plan& pl, float* out,
                      hipStream_t s);
+int attn_launch_dk192(int qv_dtype, bool stats_pass, const snf_attn::AttnParams& P, const snf_attn::Plan& pl, float* out,
+                      hipStream_t s);
 int attn_launch_varlen_dk128(const snf_attn::AttnParams& P, const snf_attn::Plan& pl, float* out, hipStream_t s);
 int attn_launch_varlen_dk64(const snf_attn::AttnParams& P, const snf_attn::Plan& pl, float* out, hipStream_t s);
 }  // namespace snf

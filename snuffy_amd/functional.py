@@ -43,6 +43,10 @@ BF16_DEEP_STACKS = "fp32"
 # folded into Wq | Wv and W1, in fp64, rounded once; after the attention only the K patched rows are re-normalised into the image)
 # instead of a second full LayerNorm pass over the bag -- what the bf16 path has always done.  Needs equal eps in both LayerNorms.
 FP32_SHARED_NORM = True
+# bf16 inference at head width 192 (D = 768 with h = 4, the README's MAE recipe) on the MFMA attention's dk = 192 kernels
+# (ops.mfma_attn_dk192_supported); False: such layers make fp32 copies of Q and V for the exact-fp32 kernel, as before.  Ships off: the
+# route has not been timed against the one of before yet (tools/attn_dk192_time.py writes profiles/attn_dk192.txt; on once it wins there)
+MFMA_ATTN_DK192 = False
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -763,7 +767,10 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
         ops.layernorm_rows(x2, None, None, n0.eps, out=xhat)
     qv = ops.linear_bf16(xhat, fw["wqv"], fw["bqv_f"], fw["bqv"])                   # [N, 2D] bf16 = [Q | V], bias epilogue
     q, v = qv[:, :dp], qv[:, dp:]                                                   # row-strided views, used in place
-    if ragged is None and (packed is not None or ops.mfma_attn_supported(k, dkp, n, qv.stride(0))):
+    # dk = 192 (the README's MAE recipe, D = 768 with h = 4; no padded form) has kernel variants of its own, single bags only
+    dk192 = (MFMA_ATTN_DK192 and dkp == 192 and ragged is None and packed is None
+             and ops.mfma_attn_dk192_supported(k, n, qv.stride(0)))
+    if ragged is None and (packed is not None or dk192 or ops.mfma_attn_supported(k, dkp, n, qv.stride(0))):
         # keys = RAW selected rows: the gather also leaves them in bf16, the projection runs like Q | V (bf16 operands,
         # fp32 accumulate, bf16 out) and the attention kernel reads Kp as it is
         xs, slot, xs16 = ops.gather_slot_map(x2, sel, bf16_copy=True)               # snuffy.py:131,145-147 (+ row -> slot map)

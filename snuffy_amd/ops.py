@@ -606,7 +606,8 @@ def sparse_attn_bwd_mfma(q, v, kp, dout, lse, h, mask=None, scale=None, dropout=
     ds = torch.empty(h, n, k, dtype=torch.bfloat16 if bf16 else torch.float32, device=q.device)
     dt = DT_F32 if q.dtype == torch.float32 else DT_BF16
     pdrop, seed, offset = dropout if dropout is not None else (0.0, 0, 0)
-    if mfma_attn_bwd_supported(k, dk) or not mfma_attn_train_chunks_supported(k, dk):   # one chunk (or the library's own refusal)
+    # one chunk (or the library's own refusal); dk = 192 is built into the chunked kernel only, whatever the key count
+    if dk != 192 and (mfma_attn_bwd_supported(k, dk) or not mfma_attn_train_chunks_supported(k, dk)):
         check(lib.snf_sparse_attn_bwd_mfma_ex(_p(q), q.stride(0), _p(v), v.stride(0), dt, _p(kp), _p(dout), _p(lse), _p(mask),
                                               float(pdrop), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), n, k, h, dk,
                                               float(scale), _p(dq), _p(dv), ldd, gdt, _p(ds), DT_BF16 if bf16 else DT_F32, _stream()),
@@ -643,6 +644,17 @@ def mfma_attn_supported(k, dk, n=None, ld=None):
     images in the 160 KiB LDS of a CU; up to 8 key chunks are run back to back with exact cross-chunk softmax statistics.
     n / ld (rows and row pitch of q, v) are optional: the kernel addresses rows with 32-bit element offsets."""
     if not ((dk == 64 and 1 <= k <= 8 * 256) or (dk == 128 and 1 <= k <= 8 * 224)):
+        return False
+    if n is not None and (n > 0xffff00 or (ld is not None and (ld >= (1 << 24) or n * ld >= 0x7fffffff))):
+        return False
+    return True
+
+
+def mfma_attn_dk192_supported(k, n=None, ld=None):
+    """Shapes the MFMA attention takes at head width 192 (the README's MAE recipe: D = 768, h = 4), forward -- with or without in-kernel
+    dropout -- and backward (ops.sparse_attn_fwd_mfma / sparse_attn_bwd_mfma): one launch holds 128 keys (Kp 48 + P 40 + V 48 KiB of
+    LDS), up to 8 key chunks.  n / ld as in mfma_attn_supported.  The older predicates keep answering for dk = 64 / 128 only."""
+    if not 1 <= k <= 8 * 128:
         return False
     if n is not None and (n > 0xffff00 or (ld is not None and (ld >= (1 << 24) or n * ld >= 0x7fffffff))):
         return False
@@ -1152,9 +1164,9 @@ def sparse_attn_fwd_mfma(q, v, kp, n, h, scale=None, need_attn=False, need_lse=F
     dt = DT_F32 if q.dtype == torch.float32 else DT_BF16
     kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
     pdrop, seed, offset = dropout if dropout is not None else (0.0, 0, 0)
-    if pdrop > 0 and not mfma_attn_train_chunks_supported(k, dk):
+    if pdrop > 0 and not (mfma_attn_train_chunks_supported(k, dk) or (dk == 192 and mfma_attn_dk192_supported(k))):
         raise ValueError("sparse_attn_fwd_mfma: in-kernel dropout needs at most 8 key chunks (k <= %d at dk = %d), got k = %d"
-                         % (8 * (224 if dk == 128 else 256), dk, k))
+                         % (8 * {128: 224, 192: 128}.get(dk, 256), dk, k))
     check(lib.snf_sparse_attn_fwd_mfma_dropout(_p(q), q.stride(0), _p(v), v.stride(0), dt, _p(kp), kdt, n, k, h, dk, float(scale),
                                                _p(out), _p(attn), _p(lse), float(pdrop), int(seed) & (2 ** 64 - 1),
                                                int(offset) & (2 ** 64 - 1), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_mfma")

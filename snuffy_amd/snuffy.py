@@ -485,7 +485,7 @@ class MILNet(nn.Module):
             from . import autograd as SA
             lin = ic.fc[0]
             layer0 = self.b_classifier.encoder.layers[0]
-            if SA.fused_layer0_train_ok(layer0, x.shape[1], x.shape[2]):
+            if SA.fused_layer0_train_ok(layer0, x.shape[1], x.shape[2]) or SA.fused_layer0_dk192_ok(layer0, x.shape[1], x.shape[2]):
                 s = SA.critic_train(x[0], lin.weight, lin.bias, layer0, layer0.sublayer[0].norm.eps)
                 return x, s.view(1, x.shape[1], -1)
         return ic(x)
