@@ -631,6 +631,31 @@ int snf_sparse_attn_x3_varlen_plan(const int64_t* offsets, int bags, int k, int 
 int snf_sparse_attn_fwd_x3_varlen(const float* q, int64_t ldq, const float* v, int64_t ldv, const float* kp, const int64_t* offsets,
                                   int bags, int k, int h, int dk, float scale, float* out, float* attn, float* lse,
                                   const int32_t* table_dev, void* workspace, size_t workspace_bytes, snf_stream_t stream);
+/* Varlen attention ABOVE ONE KEY CHUNK (k up to 8 x 224 at dk = 128, 8 x 256 at dk = 64; dk = 192 is not built).  The keys run as the
+ * chunks of the single-bag entry point of the same family (bf16: ceil(k / chunks) keys; fp32-class: that, rounded up to a multiple
+ * of 4; the last chunk is shorter): one statistics launch per chunk over all bags, then the chunks' main launches, each normalising
+ * with the statistics of all chunks -- a bag's attn and lse are those of snf_sparse_attn_fwd_mfma / _x3 on that bag alone, bit for bit,
+ * out within the fp32 order of the partial sums, and nothing depends on what a bag is packed with.
+ *   ..._chunked_plan   as the plans above (one table serves every chunk: a bag's tile geometry depends on n and h only; word 3 of a
+ *                      descriptor stays b k), plus the chunk count and the size of all chunks but the last (either nullable).
+ *                      Workspace = partial tiles at the largest chunk's key-block count | statistics [chunks][h][T] (max, sum) pairs
+ *                      over all T packed rows, 8 bytes each (none with one chunk) | bf16 form: Kp staging.  At k within one chunk: one
+ *                      chunk and the table of the plan above, integer for integer.  SNF_EUNSUPPORTED: k > 8 chunks, dk outside
+ *                      {64, 128}, an empty bag.
+ *   ..._varlen_chunked the launches; arguments and layouts as snf_sparse_attn_fwd_mfma_varlen / _x3_varlen, table and workspace from
+ *                      the chunked plan.  With one chunk they are those entry points. */
+int snf_sparse_attn_varlen_chunked_plan(const int64_t* offsets, int bags, int k, int h, int dk, int32_t* table, size_t table_ints,
+                                        size_t* table_ints_needed, size_t* workspace_bytes, int* n_chunks, int* chunk_k);
+int snf_sparse_attn_fwd_mfma_varlen_chunked(const void* q, int64_t ldq, const void* v, int64_t ldv, const void* kp, int kp_dtype,
+                                            const int64_t* offsets, int bags, int k, int h, int dk, float scale, float* out,
+                                            float* attn, float* lse, const int32_t* table_dev, void* workspace,
+                                            size_t workspace_bytes, snf_stream_t stream);
+int snf_sparse_attn_x3_varlen_chunked_plan(const int64_t* offsets, int bags, int k, int h, int dk, int32_t* table, size_t table_ints,
+                                           size_t* table_ints_needed, size_t* workspace_bytes, int* n_chunks, int* chunk_k);
+int snf_sparse_attn_fwd_x3_varlen_chunked(const float* q, int64_t ldq, const float* v, int64_t ldv, const float* kp,
+                                          const int64_t* offsets, int bags, int k, int h, int dk, float scale, float* out, float* attn,
+                                          float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
+                                          snf_stream_t stream);
 /* Ragged form for SMALL bags (exact fp32, any head width, every bag with its own key count: a bag shorter than Lambda selects
  * all of its rows -- snuffy.py:129 `min(ceil(...), n)` -- as the MIL benchmark sets do).  desc_dev [bags][4] int32 in DEVICE
  * memory = (first packed row, rows, first key row, keys) per bag; kp / out [sum of keys, h * dk]; attn [h, T, kmax] nullable

@@ -1,7 +1,8 @@
 #pragma once
 // K7 (fast form): Snuffy's sparse attention on the CDNA4 matrix cores.
 // (implementation header: compiled once per head width by sparse_attn_mfma.hip (dk = 128 + the C entry points),
-// sparse_attn_mfma_dk64.hip and sparse_attn_mfma_dk192.hip, so the kernel variants of the three widths build in parallel)
+// sparse_attn_mfma_dk64.hip and sparse_attn_mfma_dk192.hip, so the kernel variants of the three widths build in parallel; the varlen
+// variants live in sparse_attn_mfma_varlen*.hip, their key-chunked forms in sparse_attn_mfma_varlen_chunks*.hip)
 //
 //   per head a:   P_a = softmax_j(Q_a Kp_a^T * scale)  [n, k]      O_a = P_a^T V_a  [k, dk]        (snuffy.py:160-168)
 //
@@ -50,7 +51,8 @@ struct AttnParams {
     float* attn;     // [h, n, attn_ld] or null (already offset to this key chunk's first column)
     int64_t attn_ld; // row pitch of attn (= total number of keys)
     // key-chunked launches (more keys than one LDS image holds): per-chunk row statistics [n_chunks][h][n][2] =
-    // (row max * scale * log2 e, sum exp) written by sparse_attn_stats_kernel; null = single chunk, statistics computed here
+    // (row max * scale * log2 e, sum exp) written by sparse_attn_stats_kernel; null = single chunk, statistics computed here.
+    // Varlen launches: [n_chunks][h][T][2] over ALL packed rows (T = n_stride), addressed like lse: row0 + the row inside the bag
     const float* stats;
     float* stats_out;
     int n_chunks;
@@ -159,6 +161,7 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
         P.kp = PA.kp + (int64_t)dsc[3] * PA.ldkp;
         if (PA.attn) P.attn = PA.attn + (int64_t)row0 * PA.attn_ld;
         if (PA.lse) P.lse = PA.lse + row0;
+        if constexpr (EXT) P.stats = PA.stats + (int64_t)row0 * 2;   // this bag's rows of every (chunk, head) plane of n_stride rows
         P.tiles_per_head = dsc[4];
         P.tiles_per_wg = dsc[5];
         P.total_tiles = dsc[6];
@@ -368,8 +371,11 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
             float mc, lrow = 0.f;
             if constexpr (EXT) {
                 // key-chunked launch: the softmax runs over ALL chunks' keys -- combine their (max, sum) pairs
-                const float* st0 = P.stats + ((int64_t)a * P.n + (rvalid ? row : 0)) * 2;
-                const int64_t cs = (int64_t)P.h * P.n * 2;
+                // (rows of a plane: the bag's own n, or all packed rows of a varlen launch; a padded row of the bag's last tile reads
+                // the bag's OWN first row -- inside the bag whatever it is packed with)
+                const int64_t sn = VL ? P.n_stride : P.n;
+                const float* st0 = P.stats + ((int64_t)a * sn + (rvalid ? row : 0)) * 2;
+                const int64_t cs = (int64_t)P.h * sn * 2;
                 float m = st0[0];
                 for (int c = 1; c < P.n_chunks; ++c) m = fmaxf(m, st0[c * cs]);
                 float l = 0.f;
@@ -734,9 +740,26 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
 
 // Row statistics of one key chunk (key-chunked launches, k above what one LDS image holds): the GEMM1 + max / exp / sum half
 // of the kernel above, nothing else.  stats_out[(a * n + row) * 2 + {0, 1}] = (row max * scale * log2 e, sum of exp).
-template <int DK, int NKB, typename QT>
-__global__ __launch_bounds__(256, 1) void sparse_attn_stats_kernel(AttnParams P) {
+// VL: varlen launch -- the descriptor preamble of the main kernel (the same table: a bag's tile geometry depends on n and h only),
+// stats_out[(a * n_stride + row0 + row) * 2 + {0, 1}] over the packed rows.
+template <int DK, int NKB, typename QT, bool VL = false>
+__global__ __launch_bounds__(256, 1) void sparse_attn_stats_kernel(AttnParams PA) {
     constexpr int NKS = DK / 16;
+    AttnParams P = PA;
+    int bid = blockIdx.x;
+    if constexpr (VL) {
+        const int* __restrict__ tb = PA.vl;
+        const int* __restrict__ dsc = tb + VL_DESC * tb[VL_DESC * PA.vl_bags + bid];
+        const int row0 = dsc[1];
+        bid -= dsc[0];
+        P.n = dsc[2];
+        P.q = reinterpret_cast<const QT*>(PA.q) + (int64_t)row0 * PA.ldq;
+        P.kp = PA.kp + (int64_t)dsc[3] * PA.ldkp;
+        P.stats_out = PA.stats_out + (int64_t)row0 * 2;
+        P.tiles_per_head = dsc[4];
+        P.tiles_per_wg = dsc[5];
+        P.total_tiles = dsc[6];
+    }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32x4* lds_kp = reinterpret_cast<u32x4*>(smem);                    // [NKB][NKS][64] MFMA A fragments of Kp
     const int lane = threadIdx.x & 63;
@@ -747,7 +770,7 @@ __global__ __launch_bounds__(256, 1) void sparse_attn_stats_kernel(AttnParams P)
     const int n32 = (int)P.n;
     const int prow = 32 * w + j;
     const int ldq32 = (int)P.ldq;
-    const int f_begin = blockIdx.x * P.tiles_per_wg;
+    const int f_begin = bid * P.tiles_per_wg;
     int f_end = f_begin + P.tiles_per_wg;
     if (f_end > P.total_tiles) f_end = P.total_tiles;
     const int first_head = f_begin / P.tiles_per_head;
@@ -821,7 +844,7 @@ __global__ __launch_bounds__(256, 1) void sparse_attn_stats_kernel(AttnParams P)
         });
         const float lrow = xhalf_sum(l0 + l1);
         if (row < n32 && hf == 0) {
-            float* dst = P.stats_out + ((int64_t)a * P.n + row) * 2;
+            float* dst = P.stats_out + ((int64_t)a * (VL ? P.n_stride : P.n) + row) * 2;
             dst[0] = mc;
             dst[1] = lrow;
         }
@@ -1030,10 +1053,10 @@ inline size_t mfma_workspace_bytes(const Plan& pl, int dk) {
     return (size_t)pl.num_wg * pl.seg_count * (size_t)(pl.nkb * (dk / 32)) * 1024 * sizeof(float);
 }
 
-template <int DK, int NKB, typename QT>
+template <int DK, int NKB, typename QT, bool VL = false>
 int launch_stats_variant(const AttnParams& P, const Plan& pl, hipStream_t s) {
     constexpr int NKS = DK / 16;
-    hipLaunchKernelGGL((sparse_attn_stats_kernel<DK, NKB, QT>), dim3(pl.num_wg), dim3(256), (size_t)(NKB * NKS) * 1024, s, P);
+    hipLaunchKernelGGL((sparse_attn_stats_kernel<DK, NKB, QT, VL>), dim3(pl.num_wg), dim3(256), (size_t)(NKB * NKS) * 1024, s, P);
     return snf::check_launch("sparse_attn_stats_kernel");
 }
 template <int DK, typename QT>
@@ -1058,6 +1081,38 @@ int launch_stats(const AttnParams& P, const Plan& pl, hipStream_t s) {
         }
     }
     snf::set_error("sparse_attn_stats: key-block count %d not built", pl.nkb);
+    return SNF_EUNSUPPORTED;
+}
+
+// key-chunked varlen launches (bf16 Q | V): one chunk's statistics pass, or its main pass normalising over all chunks.  The chunks of
+// make_chunks hold more than kmax / 2 - 7 keys: 4, 6, 7 (or, at dk = 64, 8) key blocks
+constexpr bool varlen_chunk_built(int dk, int nkb) { return nkb == 4 || nkb == 6 || nkb == 7 || (nkb == 8 && dk == 64); }
+template <int DK>
+int launch_nkb_varlen_chunk(bool stats_pass, const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
+    using QT = unsigned short;
+    const bool aux = P.attn != nullptr || P.lse != nullptr;
+#define SNF_ATTN_VLC_CASE(NB)                                                                                             \
+    case NB:                                                                                                              \
+        if (stats_pass) return launch_stats_variant<DK, NB, QT, true>(P, pl, s);                                          \
+        return aux ? launch_variant<DK, NB, QT, true, true, 8, true>(P, pl, out, s)                                       \
+                   : launch_variant<DK, NB, QT, false, true, 8, true>(P, pl, out, s);
+    switch (pl.nkb) {
+#ifndef SNF_ATTN_DEV
+        SNF_ATTN_VLC_CASE(4)
+        SNF_ATTN_VLC_CASE(6)
+        case 8:
+            if constexpr (DK == 64) {
+                if (stats_pass) return launch_stats_variant<DK, 8, QT, true>(P, pl, s);
+                return aux ? launch_variant<DK, 8, QT, true, true, 8, true>(P, pl, out, s)
+                           : launch_variant<DK, 8, QT, false, true, 8, true>(P, pl, out, s);
+            }
+            break;
+#endif
+        SNF_ATTN_VLC_CASE(7)
+        default: break;
+    }
+#undef SNF_ATTN_VLC_CASE
+    snf::set_error("sparse_attn_mfma (varlen, key chunks): key-block count %d not built", pl.nkb);
     return SNF_EUNSUPPORTED;
 }
 
@@ -1109,4 +1164,6 @@ int attn_launch_dk192(int qv_dtype, bool stats_pass, const snf_attn::AttnParams&
                       hipStream_t s);
 int attn_launch_varlen_dk128(const snf_attn::AttnParams& P, const snf_attn::Plan& pl, float* out, hipStream_t s);
 int attn_launch_varlen_dk64(const snf_attn::AttnParams& P, const snf_attn::Plan& pl, float* out, hipStream_t s);
+int attn_launch_varlen_chunk_dk128(bool stats_pass, const snf_attn::AttnParams& P, const snf_attn::Plan& pl, float* out, hipStream_t s);
+int attn_launch_varlen_chunk_dk64(bool stats_pass, const snf_attn::AttnParams& P, const snf_attn::Plan& pl, float* out, hipStream_t s);
 }  // namespace snf

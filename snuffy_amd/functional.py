@@ -432,6 +432,25 @@ def head_pad(dk):
     return None
 
 
+def packed_head_pad(dk):
+    """Head width a head of true width dk runs at on the PACKED (varlen) path, or None: the varlen kernels' own widths, and the widths
+    between them zero-padded to 128 as head_pad() does (the README recipes' dk = 96).  dk < 64 is not padded here: such models keep the
+    ragged exact kernel."""
+    if dk in (64, 128):
+        return dk
+    if dk % 16 == 0 and 64 < dk < 128:
+        return 128
+    return None
+
+
+def _rows_linear_padded(x, w, bias, out_dtype=torch.float32):
+    """x [r, k] @ w^T + bias with a zero-padded key / output projection (_padded_heads), fp32-class: the skinny kernel of the single-bag
+    path, in slices of 8192 rows for the B x K selected rows of a packed batch (row by row the single bag's arithmetic)."""
+    if x.shape[0] <= 8192:
+        return ops.linear_rows_x3(x, w, bias, out_dtype=out_dtype)
+    return torch.cat([ops.linear_rows_x3(x[i:i + 8192], w, bias, out_dtype=out_dtype) for i in range(0, x.shape[0], 8192)])
+
+
 def _pad_heads_out(w, b, h, dk, dkp):
     """Rows of w [h dk, d] (and entries of b) regrouped per head and zero-padded to dkp per head -> ([h dkp, d], [h dkp])."""
     d_in = w.shape[1]
@@ -600,7 +619,7 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
         if packed is None or ragged.total != k or not ops.ragged_attn_supported(ragged.kmax, d // h):
             raise SnuffyHipError("ragged packed bags: %d keys (max %d per bag) at head width %d is outside the ragged attention "
                                  "kernel" % (k, ragged.kmax, d // h))
-    elif packed is not None and (kb < 1 or not ops.varlen_attn_supported(precision, kb, d // h)):
+    elif packed is not None and (kb < 1 or not ops.varlen_attn_chunks_supported(precision, kb, packed_head_pad(d // h) or d // h)):
         raise SnuffyHipError("packed bags: %d keys per bag at head width %d is outside the varlen attention kernels" % (kb, d // h))
     n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
     lq, lk, lv, lo = mha.linears
@@ -630,6 +649,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
                    and lk.weight.dtype == torch.float32 and (dkp == dk or ops.gemm_supported(n, 2 * h * dkp, 3 * d)))
         if not hl_attn:
             dkp = dk
+        if packed is not None and ragged is None and lk.weight.dtype == torch.float32 and d % 16 == 0:
+            dkp = packed_head_pad(dk) or dk                                         # packed bags: the varlen kernels' widths (dk = 96 -> 128)
         dp = h * dkp                                                                # width of Q, V, Kp, O (d unless padded)
         fw = _split_weights(layer, dkp)
         # large bags: the one-pass kernel on interleaved [hi(32) | lo(32)] images (one full-line DMA per operand row and K step,
@@ -655,7 +676,7 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
         elif frag_ok:
             kp = ops.linear_rows_x3_kpfrag(xs, wk, bk, h, scale=scale)
         elif fp is not None:
-            kp = ops.linear_rows_x3(xs, wk, bk)
+            kp = _rows_linear_padded(xs, wk, bk)
         else:
             kp = _rows_linear(xs, lk)
         if hl:
@@ -670,14 +691,14 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             qv = ops.gemm_x3(xn3, fw["wqv"], fw["bqv"], out_dtype=torch.float32, hl_out=hl_attn)
         if not shared:
             del xn3
-        q, v = (None, None) if hl_attn else (qv[:, :d], qv[:, d:])
+        q, v = (None, None) if hl_attn else (qv[:, :dp], qv[:, dp:])
         if hl_attn:
             o, attn, _ = ops.sparse_attn_fwd_x3_hl(qv[:, :2 * dp], qv[:, 2 * dp:], kp, h, need_attn=need_attn,
                                                    scale=None if isinstance(kp, ops.KpFrag) else scale)   # snuffy.py:160-168
         elif ragged is not None:
             o, attn, _ = ops.sparse_attn_fwd_ragged(q, v, kp, packed, ragged, h, need_attn=need_attn)
         elif packed is not None:
-            o, attn, _ = ops.sparse_attn_fwd_x3_varlen(q, v, kp, packed, kb, h, need_attn=need_attn)
+            o, attn, _ = ops.sparse_attn_fwd_x3_varlen(q, v, kp, packed, kb, h, scale=scale, need_attn=need_attn)
         elif FP32_ATTENTION == "x3" and ops.x3_attn_supported(k, d // h):
             o, attn, _ = ops.sparse_attn_fwd_x3(q, v, kp, h, need_attn=need_attn)    # snuffy.py:160-168
         elif FP32_ATTENTION == "x3" and ops.x3u_attn_supported(k, d // h):
@@ -688,7 +709,7 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
         del q, v, qv
         x_sel = None
         if fp is not None:                                              # padded heads: the zero columns of O meet zero columns of Wo
-            delta = ops.linear_rows_x3(o, fp["wo"], None if lo.bias is None else lo.bias.detach())
+            delta = _rows_linear_padded(o, fp["wo"], None if lo.bias is None else lo.bias.detach())
         elif (not shared and FP32_GEMM == "x3" and lo.weight.dtype == torch.float32 and o.shape[0] < 2048
                 and ops.linear_rows_x3_supported(o.shape[0], lo.weight.shape[0], o.shape[1])):
             # the output projection also writes x_sel = xs + delta (snuffy.py:205, 108): one launch instead of two (round 6)
@@ -753,9 +774,14 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
     if n0.eps != n1.eps:
         raise NotImplementedError("bf16 path shares one normalisation between both sublayers: eps must match")
     dk = d // h
-    # head widths between the MFMA kernel's ride zero-padded (head_pad: the README recipes' dk = 96 -> 128), single bags only
+    # head widths between the MFMA kernel's ride zero-padded (head_pad: the README recipes' dk = 96 -> 128); packed bags: to the varlen
+    # kernels' widths (packed_head_pad)
     dkp = head_pad(dk) if (ragged is None and packed is None and lk.weight.dtype == torch.float32) else dk
-    if dkp is None or (dkp != dk and not (ops.mfma_attn_supported(k, dkp, n, 2 * h * dkp) and ops.linear_rows_x3_supported(k, h * dkp, d)
+    if packed is not None and ragged is None and lk.weight.dtype == torch.float32 and d % 16 == 0:
+        dkp = packed_head_pad(dk) or dk
+        if dkp != dk and not ops.gemm_supported(n, 2 * h * dkp, d):
+            dkp = dk
+    elif dkp is None or (dkp != dk and not (ops.mfma_attn_supported(k, dkp, n, 2 * h * dkp) and ops.linear_rows_x3_supported(k, h * dkp, d)
                                          and ops.gemm_supported(n, 2 * h * dkp, d))):
         dkp = dk
     dp = h * dkp
@@ -775,7 +801,7 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
         # fp32 accumulate, bf16 out) and the attention kernel reads Kp as it is
         xs, slot, xs16 = ops.gather_slot_map(x2, sel, bf16_copy=True)               # snuffy.py:131,145-147 (+ row -> slot map)
         if fp is not None:
-            kp = ops.linear_rows_x3(xs, fp["wk"], fp["bk"], out_dtype=torch.bfloat16)
+            kp = _rows_linear_padded(xs, fp["wk"], fp["bk"], out_dtype=torch.bfloat16)
         elif (FP32_GEMM == "x3" and xs.shape[0] < 2048 and ops.linear_rows_x3_supported(xs.shape[0], d, d)
                 and lk.weight.dtype == torch.float32):
             # keys of one bag: fp32-class product of the fp32 rows, rounded once to the bf16 the attention kernel reads
@@ -783,7 +809,7 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
         else:
             kp = torch.addmm(fw["bk"], xs16, fw["wk"].t())
         if packed is not None:
-            o, attn, _ = ops.sparse_attn_fwd_mfma_varlen(q, v, kp, packed, kb, h, need_attn=need_attn)
+            o, attn, _ = ops.sparse_attn_fwd_mfma_varlen(q, v, kp, packed, kb, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
         else:
             o, attn, _ = ops.sparse_attn_fwd_mfma(q, v, kp, n, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
     else:
@@ -797,7 +823,7 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             o, attn, _ = ops.sparse_attn_fwd(q.float(), kp, v.float(), h, need_attn=need_attn)
     del q, v, qv
     if fp is not None:
-        delta = ops.linear_rows_x3(o, fp["wo"], None if lo.bias is None else lo.bias.detach())
+        delta = _rows_linear_padded(o, fp["wo"], None if lo.bias is None else lo.bias.detach())
     else:
         delta = _rows_linear(o, lo)
     x_sel = xs + delta

@@ -941,7 +941,8 @@ class PackedBags:
         return hit
 
     def plan(self, kind, *shape):
-        """(device table int32, workspace bytes) of a segmented launch: kind in {"mfma", "x3", "head"}."""
+        """(device table int32, workspace bytes) of a segmented launch: kind in {"mfma", "x3", "head"}; the key-chunked attention
+        plans "mfma_chunks" / "x3_chunks" add (chunk count, keys per chunk)."""
         import numpy as np
         key = (kind,) + tuple(shape)
         hit = self._plans.get(key)
@@ -950,12 +951,15 @@ class PackedBags:
         lib = _ffi.load()
         need, wsb = ctypes.c_size_t(0), ctypes.c_size_t(0)
         fn = {"mfma": lib.snf_sparse_attn_varlen_plan, "x3": lib.snf_sparse_attn_x3_varlen_plan,
+              "mfma_chunks": lib.snf_sparse_attn_varlen_chunked_plan, "x3_chunks": lib.snf_sparse_attn_x3_varlen_chunked_plan,
               "head": lib.snf_ln_mean_head_varlen_plan}[kind]
-        check(fn(self._host_ptr(), self.bags, *shape, None, 0, ctypes.byref(need), ctypes.byref(wsb)), "varlen plan (%s)" % kind)
+        chunks = (ctypes.c_int(0), ctypes.c_int(0)) if kind.endswith("_chunks") else ()
+        extra = tuple(ctypes.byref(c) for c in chunks)
+        check(fn(self._host_ptr(), self.bags, *shape, None, 0, ctypes.byref(need), ctypes.byref(wsb), *extra), "varlen plan (%s)" % kind)
         table = np.zeros(need.value, dtype=np.int32)
         check(fn(self._host_ptr(), self.bags, *shape, ctypes.c_void_p(table.ctypes.data), table.size, ctypes.byref(need),
-                 ctypes.byref(wsb)), "varlen plan (%s)" % kind)
-        hit = self._plans[key] = (torch.from_numpy(table).to(self.device), int(wsb.value))
+                 ctypes.byref(wsb), *extra), "varlen plan (%s)" % kind)
+        hit = self._plans[key] = (torch.from_numpy(table).to(self.device), int(wsb.value)) + tuple(int(c.value) for c in chunks)
         return hit
 
 
@@ -1027,6 +1031,12 @@ def varlen_attn_supported(precision_kind, k, dk):
     return (dk == 128 and 1 <= k <= 224) or (dk == 64 and 1 <= k <= 256)
 
 
+def varlen_attn_chunks_supported(precision_kind, k, dk):
+    """The varlen attention with key chunks (snf_sparse_attn_fwd_mfma_varlen_chunked / _x3_varlen_chunked): up to 8 chunks of 224
+    (dk = 128) / 256 (dk = 64) keys; one chunk is the launch varlen_attn_supported() describes."""
+    return (dk == 128 and 1 <= k <= 8 * 224) or (dk == 64 and 1 <= k <= 8 * 256)
+
+
 def topk_segmented(scores, packed, k):
     """Top-k of every bag of a packed score vector in one launch: [B, k] int64 indices INSIDE each bag (descending score, ties
     by ascending index -- the same one-workgroup kernel body as topk(), one workgroup per bag).  A bag with fewer than k rows fills
@@ -1045,7 +1055,8 @@ def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fa
     """bf16-MFMA sparse attention of B packed bags in one launch.  q, v [T, d] bf16 (row-strided views allowed), kp [B * k, d]
     (bag b's keys in rows b k ..) -> (out [B * k, d] f32, attn [h, T, k] or None, lse [h, T] or None).  A bag's result
     does not depend on what it is packed with (bit for bit); against sparse_attn_fwd_mfma() bag by bag P / lse are identical and
-    O differs by the fp32 order of the partial sums only (small bags get more rows per workgroup here)."""
+    O differs by the fp32 order of the partial sums only (small bags get more rows per workgroup here).  k above one key chunk
+    (varlen_attn_chunks_supported) runs as the key chunks of sparse_attn_fwd_mfma(), with the same guarantees."""
     if q.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
         raise TypeError("sparse_attn_fwd_mfma_varlen: q and v must be bfloat16")
     q = _rows16(q, "q")
@@ -1059,21 +1070,25 @@ def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fa
                          % (tuple(q.shape), tuple(v.shape), tuple(kp.shape), packed.total, packed.bags, k))
     dk = d // h
     scale = 1.0 / math.sqrt(dk) if scale is None else scale
-    table, wsb = packed.plan("mfma", k, h, dk)
+    chunked = not varlen_attn_supported("bf16", k, dk)
+    table, wsb = packed.plan("mfma_chunks" if chunked else "mfma", k, h, dk)[:2]
     ws = _ws(wsb, q.device)
     out = torch.empty(packed.bags * k, d, dtype=torch.float32, device=q.device)
     attn = torch.empty(h, t, k, dtype=torch.float32, device=q.device) if need_attn else None
     lse = torch.empty(h, t, dtype=torch.float32, device=q.device) if need_lse else None
     kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
-    check(_ffi.load().snf_sparse_attn_fwd_mfma_varlen(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(),
-                                                      packed.bags, k, h, dk, float(scale), _p(out), _p(attn), _p(lse), _p(table),
-                                                      _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_mfma_varlen")
+    lib = _ffi.load()
+    fn = lib.snf_sparse_attn_fwd_mfma_varlen_chunked if chunked else lib.snf_sparse_attn_fwd_mfma_varlen
+    check(fn(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(), packed.bags, k, h, dk, float(scale), _p(out),
+             _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()),
+          "snf_sparse_attn_fwd_mfma_varlen_chunked" if chunked else "snf_sparse_attn_fwd_mfma_varlen")
     return out, attn, lse
 
 
 def sparse_attn_fwd_x3_varlen(q, v, kp, packed, k, h, scale=None, need_attn=False, need_lse=False):
     """fp32-class sparse attention of B packed bags in one launch (f32 q, v [T, d], kp [B * k, d]); composition-independent bit
-    for bit, O within the fp32 summation order of sparse_attn_fwd_x3() bag by bag."""
+    for bit, O within the fp32 summation order of sparse_attn_fwd_x3() bag by bag.  k above one key chunk
+    (varlen_attn_chunks_supported) runs as the key chunks of sparse_attn_fwd_x3(), with the same guarantees."""
     if q.dtype != torch.float32 or v.dtype != torch.float32:
         raise TypeError("sparse_attn_fwd_x3_varlen: q and v must be float32")
     q = _rows16(q, "q")
@@ -1085,14 +1100,17 @@ def sparse_attn_fwd_x3_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fals
                          % (tuple(q.shape), tuple(v.shape), tuple(kp.shape), packed.total, packed.bags, k))
     dk = d // h
     scale = 1.0 / math.sqrt(dk) if scale is None else scale
-    table, wsb = packed.plan("x3", k, h, dk)
+    chunked = not varlen_attn_supported("fp32", k, dk)
+    table, wsb = packed.plan("x3_chunks" if chunked else "x3", k, h, dk)[:2]
     ws = _ws(wsb, q.device)
     out = torch.empty(packed.bags * k, d, dtype=torch.float32, device=q.device)
     attn = torch.empty(h, t, k, dtype=torch.float32, device=q.device) if need_attn else None
     lse = torch.empty(h, t, dtype=torch.float32, device=q.device) if need_lse else None
-    check(_ffi.load().snf_sparse_attn_fwd_x3_varlen(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags,
-                                                    k, h, dk, float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb,
-                                                    _stream()), "snf_sparse_attn_fwd_x3_varlen")
+    lib = _ffi.load()
+    fn = lib.snf_sparse_attn_fwd_x3_varlen_chunked if chunked else lib.snf_sparse_attn_fwd_x3_varlen
+    check(fn(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h, dk, float(scale), _p(out), _p(attn),
+             _p(lse), _p(table), _p(ws), wsb, _stream()),
+          "snf_sparse_attn_fwd_x3_varlen_chunked" if chunked else "snf_sparse_attn_fwd_x3_varlen")
     return out, attn, lse
 
 

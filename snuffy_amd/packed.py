@@ -10,6 +10,12 @@ import torch
 from . import functional as SF
 from . import snuffy
 
+# Uniform groups above one key chunk (Lambda > 224 / 256) and at head widths between the kernels' (64 < dk < 128, zero-padded to 128:
+# functional.packed_head_pad) -- the README recipes D = 384, h = 4, Lambda = 900 / 500.  False: such bags take the per-bag loop, the
+# routing of before.  On: in profiles/varlen_key_chunks.txt (tools/varlen_key_chunks_time.py) the packed route is at least level with the
+# loop at every measured composition of both recipes -- 64 x 1000 patches 4.3 - 8.5x, 64 x 8000 1.00 - 1.34x fp32-class / 1.9 - 2.5x bf16,
+# the synthetic CAMELYON16-shaped mix 1.1 - 1.95x -- with no crossover in bag length up to PACK_MAX_ROWS per launch set: no length gate.
+PACK_KEY_CHUNKS = True
 RAGGED_MAX_ROWS = 4096      # longest bag the ragged (exact fp32, one workgroup per bag and head) attention is meant for
 
 
@@ -18,7 +24,8 @@ def pack_groups(net, bags):
 
     The packed path covers inference of the binary model with a plain one-logit FCLayer critic.  "uniform" groups (ragged =
     False): every bag has at least Lambda patches, so all select the same K rows, and the head width is one the MFMA kernels
-    take -- varlen forms of the bf16 / fp32-class attention kernels.  "ragged" groups: bags shorter than Lambda (they select
+    take -- varlen forms of the bf16 / fp32-class attention kernels (with PACK_KEY_CHUNKS also Lambda above one key chunk and head widths
+    between the kernels', zero-padded).  "ragged" groups: bags shorter than Lambda (they select
     ALL their rows, snuffy.py:129) or head widths outside the MFMA kernels (the MIL benchmark sets: D = 166 / 230, h = 2) --
     exact-fp32 ragged attention, bags of at most _RAGGED_MAX_ROWS patches.  With a random share the draws of the reference
     must stay in bag order, so only one uniform group over all bags is formed."""
@@ -50,7 +57,8 @@ def pack_groups(net, bags):
     if cfg.compute == "bf16" and any(l.sublayer[0].norm.eps != l.sublayer[1].norm.eps for l in layers):
         return None
     sizes = [x.shape[-2] for x in bags]
-    uniform_dims = (d % 4 == 0 and SF.ops.varlen_attn_supported(cfg.compute, k1 + k2, d // h)
+    uniform_dims = (d % 4 == 0 and (SF.ops.varlen_attn_supported(cfg.compute, k1 + k2, d // h)
+                                    or key_chunks_ok(layers, cfg.compute, d, h, k1 + k2, len(bags), sum(sizes)))
                     and (cfg.compute == "bf16" or SF.FP32_ATTENTION == "x3"))
     if k2 > 0:
         ok = (uniform_dims and min(sizes) >= k1 + k2 and max(sizes) <= 65536 and (k1 + k2) * len(bags) <= (1 << 20)
@@ -65,6 +73,28 @@ def pack_groups(net, bags):
     for g, r in ((uni, False), (rag, True)):
         groups += [(c, r) for c in chunk_rows(net, g, sizes) if len(c) >= 2]
     return groups or None
+
+
+def key_chunks_ok(layers, compute, d, h, k, bags, rows):
+    """PACK_KEY_CHUNKS: the packed width (functional.packed_head_pad) and the key count are inside the key-chunked varlen kernels, and
+    the padded projections' shapes pass the checks the single-bag path applies to them (functional.encoder_layer)."""
+    ops = SF.ops
+    dk = d // h
+    dkp = SF.packed_head_pad(dk)
+    if not PACK_KEY_CHUNKS or dkp is None or not ops.varlen_attn_chunks_supported(compute, k, dkp):
+        return False
+    if dkp == dk:
+        return True
+    rows = min(rows, PACK_MAX_ROWS)
+    kr = min(k * bags, 8192)                                             # _rows_linear_padded slices the B x K selected rows
+    if (d % 16 or any(l.self_attn.linears[1].weight.dtype != torch.float32 for l in layers)
+            or not ops.linear_rows_x3_supported(kr, h * dkp, d) or not ops.linear_rows_x3_supported(kr, d, h * dkp)):
+        return False
+    if compute == "bf16":
+        return ops.gemm_supported(rows, 2 * h * dkp, d)
+    f = layers[0].feed_forward.w_2.weight.shape[1]
+    return (SF.FP32_GEMM == "x3" and ops.gemm_supported(rows, d, 3 * f) and ops.gemm_supported(rows, 2 * d, 3 * d)
+            and ops.gemm_supported(rows, 2 * h * dkp, 3 * d))
 
 
 PACK_MAX_ROWS = 196608      # rows of one packed launch set: the GEMMs address their [T, 3F] images with 32-bit element offsets
