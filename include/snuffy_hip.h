@@ -258,6 +258,14 @@ int snf_ln_mean_head_f32(const float* z, int64_t n, int d, const void* add_bf16,
                          const int32_t* slot_map, const float* delta_rows, float* z_out, const float* gamma,
                          const float* beta, float eps, const float* w_head, const float* b_head, int c_out,
                          float* logits, float* pooled, void* workspace, size_t workspace_bytes, snf_stream_t stream);
+/* The same with one more addend, read FIRST: the deferred K part of snf_gemm_hl_deferred_f32.  For row i and 256-column block cb a
+ * non-zero tile_map[(i / 256) * tiles_n + cb] = s + 1 adds row i % 256 of slab s (slabs [..][256][256] fp32) to z[i, 256 cb ..] before
+ * the other addends: logits, pooled and z_out are bit for bit those of snf_ln_mean_head_f32 on the summed z.  d <= 256 * tiles_n. */
+int snf_ln_mean_head_deferred_f32(const float* z, int64_t n, int d, const float* slabs, const int32_t* tile_map, int tiles_n,
+                                  const void* add_bf16, const float* add_bias, const int32_t* slot_map, const float* delta_rows,
+                                  float* z_out, const float* gamma, const float* beta, float eps, const float* w_head,
+                                  const float* b_head, int c_out, float* logits, float* pooled, void* workspace,
+                                  size_t workspace_bytes, snf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * K7  sparse attention forward                 replaces attention(), snuffy.py:160-168 (+ head split/merge of
@@ -513,6 +521,19 @@ int snf_gemm_tn_f32(const void* a, int64_t lda, int a_hi, int a_lo, const void* 
 int snf_gemm_hl_ws_bf16(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias, const float* resid,
                         int64_t ldr, int64_t m, int n, int k, int act, void* c, int64_t ldc, int out_dtype, void* workspace,
                         size_t workspace_bytes, snf_stream_t stream);
+/* The split of the last round WITHOUT its sum, for an fp32 result with exactly one reader that can add as it reads (the eval forward's last
+ * FFN output projection, read by snf_ln_mean_head_deferred_f32): same geometry, two K parts at most.  Part 0 of a split tile runs the
+ * ordinary epilogue (bias, residual) into c; part 1 writes its bare partial tile into a 256 x 256 fp32 slab of the workspace.  No
+ * tickets, no slab reads, nobody waits.  After the call
+ *     result tile t = c tile t + (map[t] ? slab[map[t] - 1] : 0),   t = (row / 256) * ceil(n / 256) + col / 256
+ * with the int32 tile map at workspace offset 0 (written in full by every call) and the slabs [..][256][256] at *slab_offset (private
+ * to their tiles: rows / columns past m / n hold values nobody reads).  snf_gemm_hl_deferred_ws_bytes: workspace size, 0 = the shape does
+ * not split (use snf_gemm_hl_resid_bf16); slab_offset nullable.  The workspace is part of the RESULT: it lives as long as c is read.
+ * act must be SNF_ACT_NONE and out_dtype SNF_DT_F32 (anything else: SNF_EUNSUPPORTED); workspace 128-byte aligned. */
+size_t snf_gemm_hl_deferred_ws_bytes(int64_t m, int n, int k, size_t* slab_offset);
+int snf_gemm_hl_deferred_f32(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias, const float* resid,
+                             int64_t ldr, int64_t m, int n, int k, int act, float* c, int64_t ldc, int out_dtype, void* workspace,
+                             size_t workspace_bytes, snf_stream_t stream);
 /* Encoder dropout of a training step (nn.Dropout(encoder_dropout) of snuffy.py:225 and :110) in the epilogue of the one-pass GEMM:
  *   C = M o act(A W^T + bias) (+ resid: the residual is NOT masked),  M[i, j] = 0 or 1 / (1 - dropout_p)
  * M is the Philox keep-mask of snf_dropout_mask_f32(dropout_p, seed, offset, h = 1, n = m, k = n) -- element (i, j) of it whatever the tiling

@@ -75,6 +75,9 @@ SIGNATURES = {
     "snf_ln_mean_head_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p, c_size_t, c_void_p]),
+    "snf_ln_mean_head_deferred_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                              c_void_p, c_size_t, c_void_p]),
     "snf_sparse_attn_fwd_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
     "snf_sparse_attn_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -151,6 +154,9 @@ SIGNATURES = {
     "snf_split_hl_colsum_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "snf_gemm_hl_ws_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
                                     c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p]),
+    "snf_gemm_hl_deferred_ws_bytes": (c_size_t, [c_int64, c_int, c_int, c_void_p]),
+    "snf_gemm_hl_deferred_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
+                                         c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p]),
     "snf_gemm_bf16_dropout": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64,
                                       c_int, c_int, c_float, c_uint64, c_uint64, c_void_p]),
     "snf_dropout_rows_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int, c_float, c_uint64, c_uint64, c_void_p]),

@@ -48,6 +48,10 @@ struct GemmParams {
     // its W workgroups busy in the last round gives each of those tiles to S = min(W / r, split_cap) workgroups, a K range each.
     // Every part but the last to finish parks its accumulators in a slab; the last arriver (ticket) adds them in part order and runs the
     // epilogue.  ws: [8 * split_rcap] tickets (zeroed by the plain launch), then [8 * split_rcap][split_cap] slabs of 256 KiB.
+    // Deferred form (snf_gemm_hl_deferred_f32, DEFER = true, two parts at most): nobody waits and nobody sums.  Part 0 of a remainder tile
+    // runs the ordinary epilogue into c; part 1 runs the same epilogue, without bias and residual, into slab `slot` of [8 * rcap] slabs of
+    // 256 x 256 fp32 and writes slot + 1 at its tile of the tile map int32[tiles_m * tiles_n] (split_cnt; zeroed by the plain launch, which
+    // is handed a split_rcap that covers the map: 8 * split_rcap >= tiles).  The one reader of c adds the slab where the map says so.
     unsigned int* split_cnt = nullptr;
     float* split_slab = nullptr;
     int split_cap = 0, split_rcap = 0;
@@ -596,8 +600,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams P) {
 // SPLIT (second launch of snf_gemm_hl_ws_bf16): the tiles of the last, partly filled round, one K part per workgroup (see GemmParams).
 // DROP (snf_gemm_hl_ws_dropout_bf16): the encoder-dropout mask in the epilogue (GemmParams::drop); with DROP = false the code is what it was
 // before the option existed.
-template <int ACT, int OUT, bool SPLIT = false, bool GATE = false, bool DROP = false>
+// SPLIT_MODE 2 = DEFER (second launch of snf_gemm_hl_deferred_f32): SPLIT without the reduction (see GemmParams); everything up to the
+// SPLIT tail is SPLIT's.  (One parameter for both: 0 plain, 1 / true split with the ticketed sum, 2 deferred.)
+template <int ACT, int OUT, int SPLIT_MODE = 0, bool GATE = false, bool DROP = false>
 __global__ __launch_bounds__(512, 2) void gemm_hl_kernel(GemmParams P) {
+    constexpr bool SPLIT = SPLIT_MODE != 0, DEFER = SPLIT_MODE == 2;
+    static_assert(!DEFER || (SPLIT && OUT == 1 && ACT == SNF_ACT_NONE && !GATE && !DROP), "gemm_hl: the deferred split writes plain fp32");
     static_assert(!GATE || (OUT == 3 && ACT == SNF_ACT_NONE && !SPLIT), "gemm_hl: the gated form writes an hl image, no activation, no split");
     static_assert(!DROP || (!GATE && (OUT == 1 || OUT == 3)), "gemm_hl: dropout goes with the fp32 and the hl-image outputs");
     constexpr int NI = 4, BN = 256;
@@ -933,7 +941,23 @@ __global__ __launch_bounds__(512, 2) void gemm_hl_kernel(GemmParams P) {
             __builtin_amdgcn_s_setprio(0);
             buf ^= 1;
         }
-        if constexpr (SPLIT) {
+        int etile = tile;      // where the epilogue writes: the tile itself, or (DEFER, part 1) tile 0 of the part's private slab
+        bool efull = full;
+#ifdef SNF_GEMM_SPLIT_NOSUM   // timing ablation: every part of the SPLIT launch runs the epilogue on its own sum; results wrong
+        if constexpr (false) {
+#else
+        if constexpr (DEFER) {
+            if (sp_part != 0) {   // wave-uniform
+                int mark = sp_slot + 1;
+                asm volatile("" : "+s"(mark));   // (opaque: hipcc otherwise parks a vector copy of it in scratch across the K loop)
+                if (threadIdx.x == 0) reinterpret_cast<int*>(P.split_cnt)[tile] = mark;
+                P.c = P.split_slab + (size_t)sp_slot * (size_t)(BM * BN);
+                P.ldc = BN;
+                P.bias = nullptr, P.resid = nullptr;
+                etile = 0, efull = true;   // the slab is private: rows and columns past m / n need no predicate
+            }
+        } else if constexpr (SPLIT) {
+#endif
             // Whoever draws the last ticket adds the other parts' slabs to its accumulators in part order and runs the epilogue;
             // everybody else parks its accumulators and leaves (cdna_hip_programming.md, in-launch split-K: plain slab stores ->
             // vmcnt(0) -> barrier -> one agent release -> ticket; reducer: one agent acquire -> barrier -> plain loads).
@@ -980,13 +1004,13 @@ __global__ __launch_bounds__(512, 2) void gemm_hl_kernel(GemmParams P) {
                 }
         }
         // bias: fetched here (one L2 round trip per tile) instead of being carried in 16 registers through the K loop
-        load_bias(tile);
+        load_bias(etile);
         wait_vmcnt<0>();
         bias_landed();
-        if (full)
-            epilogue(tile, std::true_type{});
+        if (efull)
+            epilogue(etile, std::true_type{});
         else
-            epilogue(tile, std::false_type{});
+            epilogue(etile, std::false_type{});
         after_epilogue = true;
         if (!has_next) break;
         tile = next;
@@ -1545,6 +1569,100 @@ extern "C" int snf_gemm_hl_ws_bf16(const void* a_hl, int64_t lda, const void* w_
                                    const float* resid, int64_t ldr, int64_t m, int n, int k, int act, void* c, int64_t ldc,
                                    int out_dtype, void* workspace, size_t workspace_bytes, snf_stream_t stream) {
     return gemm_hl_ws_impl(a_hl, lda, w_hl, ldw, bias, resid, ldr, m, n, k, act, c, ldc, out_dtype, nullptr, workspace, workspace_bytes, stream);
+}
+
+namespace {
+// Deferred form: [tile map, int32, padded to 4 KiB][8 * rcap slabs of 256 x 256 fp32].  map_ints is what the plain launch zeroes
+// (8 workgroup-0 strides of its `split_rcap`): at least one entry per tile.
+struct HlDeferred {
+    HlSplit g;
+    int map_rcap;        // the plain launch's split_rcap: 8 * map_rcap >= tiles
+    size_t slab_offset, bytes;
+};
+HlDeferred hl_deferred_geometry(int64_t m, int n, int k) {
+    HlDeferred d = {hl_split_geometry(m, n, k), 0, 0, 0};
+    if (d.g.cap < 2) return d;
+    d.g.cap = 2;
+    const int ntiles = (int)(((m + BM - 1) / BM) * ((n + 255) / 256));
+    d.map_rcap = (ntiles + 7) / 8 > d.g.rcap ? (ntiles + 7) / 8 : d.g.rcap;
+    d.slab_offset = ((size_t)8 * d.map_rcap * sizeof(int32_t) + 4095) & ~(size_t)4095;
+    d.bytes = d.slab_offset + (size_t)8 * d.g.rcap * (size_t)(BM * 256) * sizeof(float);
+    return d;
+}
+
+int launch_hl_deferred(GemmParams P, const HlDeferred& d, hipStream_t s) {
+    constexpr int lds = 2 * 2 * BM * 128 + 8 * 4096;
+    auto kern = gemm_hl_kernel<SNF_ACT_NONE, 1>;
+    auto kern2 = gemm_hl_kernel<SNF_ACT_NONE, 1, 2>;
+    static thread_local unsigned long long attr_set_mask = 0, attr_set2_mask = 0;   // devices (bit = device id) that have the opt-in
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "gemm_hl")) return rc;
+    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern2), lds, &attr_set2_mask, "gemm_hl")) return rc;
+    const int ntiles = P.tiles_m * P.tiles_n;
+    int grid = snf::cu_count() & ~7;
+    if (grid < 8) grid = 8;
+    const int per_xcd = (ntiles + 7) / 8;
+    if (per_xcd * 8 < grid) grid = per_xcd * 8;
+    // The plain launch walks the full rounds and zeroes the map: 8 * split_rcap entries, so it is told map_rcap.  Its only other use of
+    // split_rcap is `r <= split_rcap`, true for every XCD that splits at all under either value (rcap is their maximum).
+    P.split_cap = 2, P.split_rcap = d.map_rcap;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, P);
+    if (int rc = snf::check_launch("gemm_hl_kernel")) return rc;
+    P.split_rcap = d.g.rcap;   // slot numbering of the compact slab array
+    hipLaunchKernelGGL(kern2, dim3(grid), dim3(512), lds, s, P);
+    return snf::check_launch("gemm_hl_kernel<deferred split>");
+}
+}  // namespace
+
+// Workspace of snf_gemm_hl_deferred_f32 for this shape (0: the shape does not split -- use snf_gemm_hl_resid_bf16); *slab_offset
+// (nullable): where the slabs start.  Layout: int32 tile map [tiles_m * tiles_n] (tiles of 256 x 256, row-major) at offset 0, fp32 slabs
+// [..][256][256] at *slab_offset.  Plain memory, no state before the call.
+extern "C" size_t snf_gemm_hl_deferred_ws_bytes(int64_t m, int n, int k, size_t* slab_offset) {
+    const HlDeferred d = hl_deferred_geometry(m, n, k);
+    if (slab_offset) *slab_offset = d.slab_offset;
+    return d.bytes;
+}
+
+// c + (slab where the map is non-zero) = A W^T + bias + resid, the last round's tiles split in two K parts that nobody sums here:
+// map[tile] = 1 + (index of the 256 x 256 slab to add to that tile of c), 0 = c is complete there.  fp32 output, no activation.
+extern "C" int snf_gemm_hl_deferred_f32(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias, const float* resid,
+                                        int64_t ldr, int64_t m, int n, int k, int act, float* c, int64_t ldc, int out_dtype, void* workspace,
+                                        size_t workspace_bytes, snf_stream_t stream) {
+    SNF_REQUIRE(a_hl && w_hl && c && workspace, "snf_gemm_hl_deferred_f32: null pointer");
+    SNF_REQUIRE(m >= 1 && n >= 1 && k >= 1, "snf_gemm_hl_deferred_f32: bad shape m=%lld n=%d k=%d", (long long)m, n, k);
+    if (act != SNF_ACT_NONE || out_dtype != SNF_DT_F32) {
+        snf::set_error("snf_gemm_hl_deferred_f32: fp32 output without activation only (act %d, out_dtype %d)", act, out_dtype);
+        return SNF_EUNSUPPORTED;
+    }
+    SNF_REQUIRE(!resid || (ldr >= n && ldr % 4 == 0 && reinterpret_cast<uintptr_t>(resid) % 16 == 0),
+                "snf_gemm_hl_deferred_f32: a residual needs 16-byte aligned rows (ldr=%lld)", (long long)ldr);
+    const HlDeferred d = hl_deferred_geometry(m, n, k);
+    if (k % BKS || k < BKS || n % 8 || lda % 8 || ldw % 8 || ldc % 4 || lda < 2 * (int64_t)k || ldw < 2 * (int64_t)k || ldc < n ||
+        (reinterpret_cast<uintptr_t>(a_hl) | reinterpret_cast<uintptr_t>(w_hl) | reinterpret_cast<uintptr_t>(c)) % 16 ||
+        (bias && reinterpret_cast<uintptr_t>(bias) % 16) || m * lda >= 0x7fffffffll || (int64_t)n * ldw >= 0x7fffffffll || !d.bytes) {
+        snf::set_error("snf_gemm_hl_deferred_f32: shape m=%lld n=%d k=%d (lda %lld ldw %lld ldc %lld) outside the kernel's domain "
+                       "(snf_gemm_hl_bf16's, and a last round that splits: snf_gemm_hl_deferred_ws_bytes > 0)",
+                       (long long)m, n, k, (long long)lda, (long long)ldw, (long long)ldc);
+        return SNF_EUNSUPPORTED;
+    }
+    if (workspace_bytes < d.bytes || reinterpret_cast<uintptr_t>(workspace) % 128) {
+        snf::set_error("snf_gemm_hl_deferred_f32: workspace %zu < %zu (or not 128-byte aligned)", workspace_bytes, d.bytes);
+        return SNF_EWORKSPACE;
+    }
+    GemmParams P;
+    P.a = reinterpret_cast<const unsigned short*>(a_hl);
+    P.w = reinterpret_cast<const unsigned short*>(w_hl);
+    P.bias = bias;
+    P.c = c;
+    P.lda = lda, P.ldw = ldw, P.ldc = ldc;
+    P.m = (int)m, P.n = n, P.k = k, P.act = act;
+    P.tiles_m = (int)((m + BM - 1) / BM);
+    P.tiles_n = (n + 255) / 256;
+    P.trace = nullptr;
+    P.resid = resid;
+    P.ldr = ldr;
+    P.split_cnt = reinterpret_cast<unsigned int*>(workspace);
+    P.split_slab = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + d.slab_offset);
+    return launch_hl_deferred(P, d, snf::as_stream(stream));
 }
 
 extern "C" int snf_gemm_hl_ws_dropout_bf16(const void* a_hl, int64_t lda, const void* w_hl, int64_t ldw, const float* bias,

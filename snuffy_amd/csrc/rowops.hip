@@ -1167,7 +1167,10 @@ __device__ __forceinline__ void add_row_bf16(const unsigned short* __restrict__ 
     }
 }
 
-template <int VEC, int NV>
+// DEFER (snf_ln_mean_head_deferred_f32): z's producer left the second K part of some 256 x 256 tiles in slabs (snf_gemm_hl_deferred_f32);
+// tile_map[(row >> 8) * tiles_n + column block] = slab + 1 or 0.  The slab row is added to the base row FIRST, so everything behind it is
+// bit for bit what the kernel computes from the summed z.  Vector i of a row lies inside column block i * 64 * VEC / 256.
+template <int VEC, int NV, bool DEFER = false>
 __global__ __launch_bounds__(WG) void ln_colsum_kernel(const float* __restrict__ z, int64_t n, int d, float eps,
                                                        const unsigned short* __restrict__ add_bf16,
                                                        const float* __restrict__ add_bias,
@@ -1175,7 +1178,9 @@ __global__ __launch_bounds__(WG) void ln_colsum_kernel(const float* __restrict__
                                                        const float* __restrict__ delta_rows,
                                                        float* __restrict__ z_out,
                                                        float* __restrict__ partial /*[grid, d]*/,
-                                                       const int* __restrict__ vl = nullptr, int vl_bags = 0) {
+                                                       const int* __restrict__ vl = nullptr, int vl_bags = 0,
+                                                       const float* __restrict__ slabs = nullptr,
+                                                       const int32_t* __restrict__ tile_map = nullptr, int tiles_n = 0) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     int bid = blockIdx.x, gdim = gridDim.x;
@@ -1204,8 +1209,38 @@ __global__ __launch_bounds__(WG) void ln_colsum_kernel(const float* __restrict__
     const int64_t rstride = (int64_t)gdim * WAVES;
     float nz[NV * VEC];     // prefetched base row
     uint2 nb[NV];           // prefetched raw bf16 addend (VEC == 4 only)
+    // DEFER: the slab row rides with the base row's prefetch; the (wave-uniform, scalar) map entries of a row are fetched one trip
+    // further ahead, so no row load waits behind a map lookup
+    constexpr int NCB = DEFER ? (NV * VEC * 64 + 255) / 256 : 1;
+    float ns[DEFER ? NV * VEC : 1];
+    int mp_n[NCB], mp_nn[NCB];   // map entries of the row in flight (being reduced, then the one just issued) and of the row behind it
+    auto lookup = [&](int64_t row, int (&mp)[NCB]) __attribute__((always_inline)) {
+        const int trow = __builtin_amdgcn_readfirstlane((int)(row >> 8));
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) mp[cb] = cb < tiles_n ? tile_map[(int64_t)trow * tiles_n + cb] : 0;
+    };
     auto issue = [&](int64_t row) __attribute__((always_inline)) {
         load_row<VEC, NV>(z + row * d, d, lane, nz);
+        if constexpr (DEFER) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int sl = mp_n[i * 64 * VEC / 256];   // wave-uniform
+#pragma unroll
+                for (int t = 0; t < VEC; ++t) ns[i * VEC + t] = 0.f;
+                if (sl) {
+                    const int e = (i * 64 + lane) * VEC;
+                    const float* __restrict__ sp = slabs + ((int64_t)(sl - 1) * 256 + (row & 255)) * 256 + (e & 255);
+                    if constexpr (VEC == 4) {
+                        if (e < d) {
+                            const float4 t4 = *reinterpret_cast<const float4*>(sp);
+                            ns[i * 4 + 0] = t4.x, ns[i * 4 + 1] = t4.y, ns[i * 4 + 2] = t4.z, ns[i * 4 + 3] = t4.w;
+                        }
+                    } else {
+                        if (e < d) ns[i] = *sp;
+                    }
+                }
+            }
+        }
         if constexpr (VEC == 4) {
             if (add_bf16) {
 #pragma unroll
@@ -1217,11 +1252,28 @@ __global__ __launch_bounds__(WG) void ln_colsum_kernel(const float* __restrict__
         }
     };
     int64_t row = (int64_t)bid * WAVES + wave;
+    if constexpr (DEFER) {
+        if (row < n) lookup(row, mp_n);
+    }
     if (row < n) issue(row);
+    if constexpr (DEFER) {
+        if (row + rstride < n) lookup(row + rstride, mp_nn);
+    }
     for (; row < n; row += rstride) {
         float r[NV * VEC];
 #pragma unroll
         for (int i = 0; i < NV * VEC; ++i) r[i] = nz[i];
+        if constexpr (DEFER) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                if (mp_n[i * 64 * VEC / 256]) {   // wave-uniform
+#pragma unroll
+                    for (int t = 0; t < VEC; ++t) r[i * VEC + t] += ns[i * VEC + t];
+                }
+            }
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) mp_n[cb] = mp_nn[cb];
+        }
         if constexpr (VEC == 4) {
             if (add_bf16) {
 #pragma unroll
@@ -1236,6 +1288,9 @@ __global__ __launch_bounds__(WG) void ln_colsum_kernel(const float* __restrict__
             if (add_bf16) add_row_bf16<VEC, NV>(add_bf16 + row * d, d, lane, r);
         }
         if (row + rstride < n) issue(row + rstride);   // wave-uniform
+        if constexpr (DEFER) {
+            if (row + 2 * rstride < n) lookup(row + 2 * rstride, mp_nn);
+        }
         if (add_bias) {
 #pragma unroll
             for (int i = 0; i < NV * VEC; ++i) r[i] += bias_r[i];
@@ -2051,10 +2106,11 @@ size_t snf_ln_mean_head_workspace_bytes(int d) {
     return ((size_t)snf::cu_count() * 4 + HEAD_NSLICE) * (size_t)d * sizeof(float);
 }
 
-int snf_ln_mean_head_f32(const float* z, int64_t n, int d, const void* add_bf16, const float* add_bias,
-                         const int32_t* slot_map, const float* delta_rows, float* z_out, const float* gamma,
-                         const float* beta, float eps, const float* w_head, const float* b_head, int c_out, float* logits,
-                         float* pooled, void* workspace, size_t workspace_bytes, snf_stream_t stream) {
+static int ln_mean_head_impl(const float* z, int64_t n, int d, const float* slabs, const int32_t* tile_map, int tiles_n,
+                             const void* add_bf16, const float* add_bias, const int32_t* slot_map, const float* delta_rows,
+                             float* z_out, const float* gamma, const float* beta, float eps, const float* w_head,
+                             const float* b_head, int c_out, float* logits, float* pooled, void* workspace, size_t workspace_bytes,
+                             snf_stream_t stream) {
     SNF_REQUIRE(z && w_head && logits && workspace, "snf_ln_mean_head_f32: null pointer");
     SNF_REQUIRE(!slot_map || delta_rows, "snf_ln_mean_head_f32: slot_map without delta_rows");
     SNF_REQUIRE(n >= 1 && d >= 1 && c_out >= 1, "snf_ln_mean_head_f32: bad shape");
@@ -2071,10 +2127,17 @@ int snf_ln_mean_head_f32(const float* z, int64_t n, int d, const void* add_bf16,
     hipStream_t s = snf::as_stream(stream);
     float* partial = reinterpret_cast<float*>(workspace);
     float* partial2 = partial + (size_t)parts * d;
-    SNF_ROW_DISPATCH(cfg, hipLaunchKernelGGL((ln_colsum_kernel<VEC, NV>), dim3(parts), dim3(WG),
-                                              WAVES * NV * VEC * 64 * sizeof(float), s, z, n, d, eps,
-                                              reinterpret_cast<const unsigned short*>(add_bf16), add_bias, slot_map,
-                                              delta_rows, z_out, partial));
+    if (tile_map) {
+        SNF_ROW_DISPATCH(cfg, hipLaunchKernelGGL((ln_colsum_kernel<VEC, NV, true>), dim3(parts), dim3(WG),
+                                                  WAVES * NV * VEC * 64 * sizeof(float), s, z, n, d, eps,
+                                                  reinterpret_cast<const unsigned short*>(add_bf16), add_bias, slot_map,
+                                                  delta_rows, z_out, partial, nullptr, 0, slabs, tile_map, tiles_n));
+    } else {
+        SNF_ROW_DISPATCH(cfg, hipLaunchKernelGGL((ln_colsum_kernel<VEC, NV>), dim3(parts), dim3(WG),
+                                                  WAVES * NV * VEC * 64 * sizeof(float), s, z, n, d, eps,
+                                                  reinterpret_cast<const unsigned short*>(add_bf16), add_bias, slot_map,
+                                                  delta_rows, z_out, partial));
+    }
     int rc = snf::check_launch("ln_colsum_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(ln_colreduce_kernel, dim3((d + 63) / 64, HEAD_NSLICE), dim3(256), 0, s, partial, parts, d, partial2);
@@ -2083,6 +2146,26 @@ int snf_ln_mean_head_f32(const float* z, int64_t n, int d, const void* add_bf16,
     hipLaunchKernelGGL(head_gemv_kernel, dim3(c_out), dim3(256), 0, s, partial2, n, d, gamma, beta, w_head, b_head, pooled,
                        logits);
     return snf::check_launch("head_gemv_kernel");
+}
+
+int snf_ln_mean_head_f32(const float* z, int64_t n, int d, const void* add_bf16, const float* add_bias,
+                         const int32_t* slot_map, const float* delta_rows, float* z_out, const float* gamma,
+                         const float* beta, float eps, const float* w_head, const float* b_head, int c_out, float* logits,
+                         float* pooled, void* workspace, size_t workspace_bytes, snf_stream_t stream) {
+    return ln_mean_head_impl(z, n, d, nullptr, nullptr, 0, add_bf16, add_bias, slot_map, delta_rows, z_out, gamma, beta, eps, w_head,
+                             b_head, c_out, logits, pooled, workspace, workspace_bytes, stream);
+}
+
+int snf_ln_mean_head_deferred_f32(const float* z, int64_t n, int d, const float* slabs, const int32_t* tile_map, int tiles_n,
+                                  const void* add_bf16, const float* add_bias, const int32_t* slot_map, const float* delta_rows,
+                                  float* z_out, const float* gamma, const float* beta, float eps, const float* w_head,
+                                  const float* b_head, int c_out, float* logits, float* pooled, void* workspace,
+                                  size_t workspace_bytes, snf_stream_t stream) {
+    SNF_REQUIRE(slabs && tile_map, "snf_ln_mean_head_deferred_f32: null slabs / tile map");
+    SNF_REQUIRE(aligned16(slabs) && tiles_n >= 1 && d <= 256 * (int64_t)tiles_n,
+                "snf_ln_mean_head_deferred_f32: d=%d beyond %d column tiles (or unaligned slabs)", d, tiles_n);
+    return ln_mean_head_impl(z, n, d, slabs, tile_map, tiles_n, add_bf16, add_bias, slot_map, delta_rows, z_out, gamma, beta, eps,
+                             w_head, b_head, c_out, logits, pooled, workspace, workspace_bytes, stream);
 }
 
 // ---- varlen head: logits of every bag of a packed residual stream in three launches (instead of three per bag) --------------

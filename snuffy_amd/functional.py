@@ -302,16 +302,18 @@ def ffn_forward(ff, x2, precision):
 # fused encoder layer
 # ----------------------------------------------------------------------------------------------------------------------
 class Parts:
-    """z = base (+ add_bf16) (+ add_bias) (+ delta[slot]) -- the residual stream after a layer, not yet assembled."""
+    """z = base (+ deferred) (+ add_bf16) (+ add_bias) (+ delta[slot]) -- the residual stream after a layer, not yet assembled.
+    deferred (ops.DeferredK): the second K part of the tiles that base's GEMM split (ops.gemm_hl_deferred), added first."""
 
-    __slots__ = ("base", "add_bf16", "add_bias", "slot", "delta")
+    __slots__ = ("base", "add_bf16", "add_bias", "slot", "delta", "deferred")
 
-    def __init__(self, base, add_bf16=None, add_bias=None, slot=None, delta=None):
+    def __init__(self, base, add_bf16=None, add_bias=None, slot=None, delta=None, deferred=None):
         self.base, self.add_bf16, self.add_bias, self.slot, self.delta = base, add_bf16, add_bias, slot, delta
+        self.deferred = deferred
 
     @property
     def plain(self):
-        return self.add_bf16 is None and self.add_bias is None and self.slot is None
+        return self.add_bf16 is None and self.add_bias is None and self.slot is None and self.deferred is None
 
 
 _MATERIALIZE_CONST = {}
@@ -329,7 +331,7 @@ def materialize(parts):
         _MATERIALIZE_CONST[key] = const
     dummy_w, ones = const
     _, _, z = ops.ln_mean_head(parts.base, ones, dummy_w[0], 1e-5, dummy_w, None, parts.add_bf16, parts.add_bias,
-                               parts.slot, parts.delta, want_z=True)
+                               parts.slot, parts.delta, want_z=True, deferred=parts.deferred)
     return z
 
 
@@ -337,6 +339,8 @@ def head(parts, norm, linear, packed=None):
     """logits = Linear(mean_n LayerNorm(z))  (snuffy.py:86,71), residual assembly fused into the read.  packed (ops.PackedBags):
     the rows are B packed bags -> logits [B, C], one mean per bag."""
     if packed is not None:
+        if parts.deferred is not None:
+            parts = Parts(materialize(parts))
         logits, _ = ops.ln_mean_head_varlen(parts.base, packed, norm.weight, norm.bias, norm.eps, linear.weight, linear.bias,
                                             parts.add_bf16, parts.add_bias, parts.slot, parts.delta)
         return logits
@@ -344,7 +348,7 @@ def head(parts, norm, linear, packed=None):
         from . import autograd as SA
         return SA.head_train(materialize(parts), norm, linear)
     logits, _, _ = ops.ln_mean_head(parts.base, norm.weight, norm.bias, norm.eps, linear.weight, linear.bias,
-                                    parts.add_bf16, parts.add_bias, parts.slot, parts.delta)
+                                    parts.add_bf16, parts.add_bias, parts.slot, parts.delta, deferred=parts.deferred)
     return logits
 
 
@@ -597,6 +601,16 @@ def _rows_linear(x, lin):
     return F.linear(x, lin.weight, lin.bias)
 
 
+def _ffn_out_hl(hid3, w2, b2, x2, deferred_ok):
+    """z = x + W2 hid + b2 on the one-pass kernel -> (z, DeferredK or None).  Where z goes straight to the head (the last layer of an
+    eval forward) and the shape's last round of tiles splits, the split's second K part stays unsummed in its slabs and the head adds it
+    as it reads (ops.gemm_hl_deferred): no slab round trip, no ticket, no workgroup waiting for another inside the GEMM."""
+    if deferred_ok and ops.GEMM_HL_DEFERRED and ops.GEMM_HL_SPLITK \
+            and ops.gemm_hl_deferred_ws_bytes(hid3.shape[0], w2.shape[0], hid3.shape[1] // 2):
+        return ops.gemm_hl_deferred(hid3, w2, b2, resid=x2)
+    return ops.gemm_hl(hid3, w2, b2, resid=x2), None
+
+
 def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None, last=False):
     """EncoderLayer.forward (snuffy.py:126-157) for x2 [N, D] and selected rows sel [K].  Returns (Parts, A).
 
@@ -722,14 +736,14 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             ops.layernorm_rows_hl_patch_(xn3, sel, xs, delta, eps=n1.eps)
             hid3 = ops.gemm_hl(xn3, fhf["w1"], fhf["b1"], ff.activation_name, hl_out=True)   # snuffy.py:224-225, [N, 2F] image
             del xn3
-            z = ops.gemm_hl(hid3, fh["w2"], fw["b2"], resid=x2)                    # x + W2 hid + b2: the residual rides in the epilogue
+            z, zk = _ffn_out_hl(hid3, fh["w2"], fw["b2"], x2, last and packed is None)   # x + W2 hid + b2: the residual rides in the epilogue
         elif hl:
             if x_sel is None:
                 x_sel = xs + delta                                                  # snuffy.py:108
             yn3 = ops.layernorm_rows_hl(x2, n1.weight, n1.bias, n1.eps, slot=slot, patch_rows=x_sel)   # LN(y), y never built
             hid3 = ops.gemm_hl(yn3, fh["w1"], fw["b1"], ff.activation_name, hl_out=True)   # snuffy.py:224-225, [N, 2F] image
             del yn3
-            z = ops.gemm_hl(hid3, fh["w2"], fw["b2"], resid=x2)                    # x + W2 hid + b2: the residual rides in the epilogue
+            z, zk = _ffn_out_hl(hid3, fh["w2"], fw["b2"], x2, last and packed is None)   # x + W2 hid + b2: the residual rides in the epilogue
         else:
             if x_sel is None:
                 x_sel = xs + delta                                                  # snuffy.py:108
@@ -737,9 +751,10 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             hid3 = ops.gemm_x3(yn3, fw["w1"], fw["b1"], ff.activation_name, split3=True)   # [N, 3F] image
             del yn3
             z = ops.gemm_x3(hid3, fw["w2"], fw["b2"], out_dtype=torch.float32, resid=x2)   # x + W2 hid + b2: the residual rides in the epilogue
+            zk = None
         del hid3
         if last:                                                                    # rows S: x -> x_sel (snuffy.py:155), in the head's read
-            return Parts(z, slot=slot, delta=delta), (attn.unsqueeze(0) if attn is not None else None)
+            return Parts(z, slot=slot, delta=delta, deferred=zk), (attn.unsqueeze(0) if attn is not None else None)
         ops.scatter_add_rows_(z, sel, delta)                                        # rows S: x -> x_sel (snuffy.py:155)
         return Parts(z), (attn.unsqueeze(0) if attn is not None else None)
 

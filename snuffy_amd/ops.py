@@ -489,9 +489,10 @@ def bias_act_(h, bias, act):
 
 
 def ln_mean_head(z, gamma, beta, eps, w_head, b_head, add_bf16=None, add_bias=None, slot=None, delta_rows=None,
-                 want_z=False):
-    """logits = W_head mean_n(LN(z')) + b_head  (snuffy.py:86,71) where z' = z (+ add_bf16) (+ add_bias)
-    (+ delta_rows[slot]).  Returns (logits [C], pooled [D], z' or None)."""
+                 want_z=False, deferred=None):
+    """logits = W_head mean_n(LN(z')) + b_head  (snuffy.py:86,71) where z' = z (+ deferred) (+ add_bf16) (+ add_bias)
+    (+ delta_rows[slot]).  Returns (logits [C], pooled [D], z' or None).  deferred (DeferredK of gemm_hl_deferred): the K part z's
+    producer left unsummed, added first -- bit for bit the call on the summed z."""
     z = _req(z, torch.float32, "z", 2)
     n, d = z.shape
     if add_bf16 is not None:
@@ -513,6 +514,14 @@ def ln_mean_head(z, gamma, beta, eps, w_head, b_head, add_bf16=None, add_bias=No
     pooled = torch.empty(d, dtype=torch.float32, device=z.device)
     wsb = lib.snf_ln_mean_head_workspace_bytes(d)
     ws = _ws(wsb, z.device)
+    if deferred is not None:
+        if tuple(deferred.tile_map.shape) != ((n + 255) // 256, (d + 255) // 256):
+            raise ValueError("ln_mean_head: deferred part of a %s-tile result with z %s" % (tuple(deferred.tile_map.shape), (n, d)))
+        check(lib.snf_ln_mean_head_deferred_f32(_p(z), n, d, _p(deferred.slabs), _p(deferred.tile_map), deferred.tile_map.shape[1],
+                                                _p(add_bf16), _p(add_bias), _p(slot), _p(delta_rows), _p(z_out), _p(gamma), _p(beta),
+                                                float(eps), _p(w_head), _p(b_head), c, _p(logits), _p(pooled), _p(ws), wsb, _stream()),
+              "snf_ln_mean_head_deferred_f32")
+        return logits, pooled, z_out
     check(lib.snf_ln_mean_head_f32(_p(z), n, d, _p(add_bf16), _p(add_bias), _p(slot), _p(delta_rows), _p(z_out),
                                    _p(gamma), _p(beta), float(eps), _p(w_head), _p(b_head), c, _p(logits), _p(pooled),
                                    _p(ws), wsb, _stream()), "snf_ln_mean_head_f32")
@@ -1677,6 +1686,72 @@ def hl_colsum(img):
 
 
 GEMM_HL_SPLITK = True   # split-K of the last, partly filled round of tiles (snf_gemm_hl_ws_bf16); False: plain tile walk
+GEMM_HL_DEFERRED = True   # eval forward, last FFN output projection: the split's second K part is summed in the head's read (gemm_hl_deferred)
+
+
+class DeferredK:
+    """The unsummed second K part of a gemm_hl_deferred result: slabs [S, 256, 256] f32 and tile_map [tiles_m, tiles_n] int32
+    (0 = the tile of z is complete, s + 1 = add slab s), both views of ONE workspace tensor that this object keeps alive."""
+
+    __slots__ = ("slabs", "tile_map", "ws")
+
+    def __init__(self, slabs, tile_map, ws):
+        self.slabs, self.tile_map, self.ws = slabs, tile_map, ws
+
+    def add_to(self, z):
+        """z + the deferred part, assembled with torch ops (tests, debugging): a new tensor."""
+        z = z.clone()
+        for tm, tn in self.tile_map.nonzero().tolist():
+            blk = z[256 * tm:256 * (tm + 1), 256 * tn:256 * (tn + 1)]
+            blk += self.slabs[int(self.tile_map[tm, tn]) - 1, :blk.shape[0], :blk.shape[1]]
+        return z
+
+
+def gemm_hl_deferred_ws_bytes(m, n, k):
+    """Workspace of gemm_hl_deferred for A [m, k] W [n, k]^T (0: the shape's last round does not split -- use gemm_hl)."""
+    return int(_ffi.load().snf_gemm_hl_deferred_ws_bytes(m, n, k, None))
+
+
+def gemm_hl_deferred(a_hl, w_hl, bias=None, resid=None, workspace=None):
+    """gemm_hl(a_hl, w_hl, bias, resid=resid) -> fp32 [m, n] whose last round of tiles is split in two K parts that are NOT summed here:
+    returns (z, DeferredK) with result = z + DeferredK (ln_mean_head(..., deferred=) adds it as it reads).  The workspace is an ordinary
+    tensor of its own (caching allocator / graph pool) owned by the DeferredK: it lives until the reader has run, whatever gemm_hl calls
+    follow.  workspace (optional): a uint8 tensor of at least gemm_hl_deferred_ws_bytes to use instead; its contents do not matter.
+    Shapes whose last round does not split (gemm_hl_deferred_ws_bytes == 0) raise."""
+    if a_hl.dtype != torch.bfloat16 or w_hl.dtype != torch.bfloat16:
+        raise TypeError("gemm_hl_deferred: operands must be bfloat16 hl images")
+    a_hl = _rows16(a_hl, "a_hl")
+    w_hl = _rows16(w_hl, "w_hl")
+    m, k2 = a_hl.shape
+    n = w_hl.shape[0]
+    if w_hl.shape[1] != k2 or k2 % 64:
+        raise ValueError("gemm_hl_deferred: images are %s and %s" % (tuple(a_hl.shape), tuple(w_hl.shape)))
+    if bias is not None:
+        bias = _req(bias, torch.float32, "bias", 1)
+    ldr = 0
+    if resid is not None:
+        if resid.dtype != torch.float32 or tuple(resid.shape) != (m, n):
+            raise ValueError("gemm_hl_deferred: resid needs an fp32 [m, n] tensor")
+        resid = _rows16(resid, "resid")
+        ldr = resid.stride(0)
+    lib = _ffi.load()
+    off = ctypes.c_size_t(0)
+    ws_bytes = int(lib.snf_gemm_hl_deferred_ws_bytes(m, n, k2 // 2, ctypes.byref(off)))
+    if not ws_bytes:
+        raise ValueError("gemm_hl_deferred: m=%d n=%d k=%d has no split last round" % (m, n, k2 // 2))
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a_hl.device)
+    elif ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_contiguous() or ws.numel() < ws_bytes or ws.device != a_hl.device:
+        raise ValueError("gemm_hl_deferred: workspace must be a contiguous uint8 tensor of >= %d bytes on %s" % (ws_bytes, a_hl.device))
+    out = torch.empty(m, n, dtype=torch.float32, device=a_hl.device)
+    check(lib.snf_gemm_hl_deferred_f32(_p(a_hl), a_hl.stride(0), _p(w_hl), w_hl.stride(0), _p(bias), _p(resid), ldr, m, n, k2 // 2,
+                                       ACT_CODES["none"], _p(out), out.stride(0), DT_F32, _p(ws), ws_bytes, _stream()),
+          "snf_gemm_hl_deferred_f32")
+    tm, tn = (m + 255) // 256, (n + 255) // 256
+    tile_map = ws[:4 * tm * tn].view(torch.int32).view(tm, tn)
+    slabs = ws[off.value:ws_bytes].view(torch.float32).view(-1, 256, 256)
+    return out, DeferredK(slabs, tile_map, ws)
 
 
 def _hl_workspace(device, nbytes):
