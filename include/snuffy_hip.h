@@ -641,6 +641,19 @@ int snf_tile_preprocess_u8(const void* img_u8, int b, int h, int w, int c, int o
  * --------------------------------------------------------------------------------------------------------- */
 int snf_topk_segmented_f32(const float* scores, const int64_t* offsets_dev, int bags, int64_t max_n, int k, int64_t* idx_out,
                            snf_stream_t stream);
+/* ---------------------------------------------------------------------------------------------------------
+ * K2m class-union selection of the multiclass model          replaces snuffy_multiclass.py:136-141 (per class torch.sort, top
+ *     rows, flatten, torch.unique) for every batch row in ONE launch.
+ *   snf_multiclass_select_f32: scores [b, n, c] f32 contiguous.  For row i and every class j the k1 highest of scores[i, :, j]
+ *     (descending score, ties by ascending index: the rule of snf_topk_f32, the same for +-0 / +-inf / NaN); the union of those
+ *     indices, ascending and duplicate-free, goes to uniq_out[i, 0 .. count_out[i]) (uniq_out [b, c * k1] int64, count_out [b]
+ *     int32, both in device memory; entries past the count are not written).
+ *   One workgroup per batch row, the classes looped inside it; no workgroup waits for another and nothing but plain stores
+ *     reaches global memory: bit-identical on every run.
+ *   Domain: 1 <= k1 <= min(n, 2048), c * k1 <= 4096, n < 2^30; outside it SNF_EUNSUPPORTED / SNF_EINVAL.
+ * --------------------------------------------------------------------------------------------------------- */
+int snf_multiclass_select_f32(const float* scores, int b, int64_t n, int c, int k1, int64_t* uniq_out, int32_t* count_out,
+                              snf_stream_t stream);
 int snf_sparse_attn_varlen_plan(const int64_t* offsets, int bags, int k, int h, int dk, int32_t* table, size_t table_ints,
                                 size_t* table_ints_needed, size_t* workspace_bytes);
 int snf_sparse_attn_fwd_mfma_varlen(const void* q, int64_t ldq, const void* v, int64_t ldv, const void* kp, int kp_dtype,
@@ -700,10 +713,16 @@ int snf_ln_mean_head_varlen_f32(const float* z, const int64_t* offsets, int bags
  *     (snf_topk_f32) are a uniform sample without replacement of the rows not excluded, in random order.
  *   state: 16-byte device record {u64 seed, u64 offset}, owned by the caller; snf_sampler_advance adds 1 to the offset ON THE DEVICE,
  *     so a captured graph (advance, keys, top-k) draws fresh rows on every replay.  Host twin: oracle/philox_ref.py.
+ *   snf_random_share_keys_batched_f32: the same for b batch rows in two launches (keys, then excludes): keys [b, n], row i draws
+ *     from stream layer + 64 i (row 0 is the single-row stream; layer < 64, b <= 64), keys[i, exclude[i, j]] = -1 for
+ *     j < counts_dev[i] (exclude [b, pitch] int64, counts_dev [b] int32, both in DEVICE memory: the counts are never read on the host).
+ *     The k2 largest keys of every row: snf_topk_segmented_f32 over the b rows of n keys.
  * --------------------------------------------------------------------------------------------------------- */
 int snf_sampler_advance(void* state, snf_stream_t stream);
 int snf_random_share_keys_f32(const void* state, int layer, int64_t n, const int64_t* exclude_rows, int n_exclude, float* keys,
                               snf_stream_t stream);
+int snf_random_share_keys_batched_f32(const void* state, int layer, int b, int64_t n, const int64_t* exclude, const int32_t* counts_dev,
+                                      int pitch, float* keys, snf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Debug hooks -- PROCESS-WIDE state, outside the stateless / re-entrant contract at the top of this header (see there).  Callers:

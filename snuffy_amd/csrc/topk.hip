@@ -54,6 +54,32 @@ __device__ __forceinline__ unsigned int block_excl_scan_1024(unsigned int v, uns
     return base + incl - v;
 }
 
+// The same sum for a caller that runs in a loop (multiclass_select_kernel): nothing in it depends on the hardware lane id -- the wave
+// step is six DPP adds (shifts inside a row of 16, then the row broadcasts) instead of shuffles, whose six lane-address registers a
+// loop would keep alive from trip to trip --, and the thread index comes in as tix.
+__device__ __forceinline__ unsigned int block_excl_scan_1024_dpp(unsigned int v, unsigned int* wave_tot, unsigned int* total,
+                                                                 const unsigned int tix) {
+    const int lane = tix & 63, wv = tix >> 6;
+    unsigned int incl = v;
+    incl += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, true);    // row_shr:1, zero fill
+    incl += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, true);    // row_shr:2
+    incl += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, true);    // row_shr:4
+    incl += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xf, 0xf, true);    // row_shr:8
+    incl += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
+    incl += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
+    __syncthreads();
+    if (lane == 63) wave_tot[wv] = incl;
+    __syncthreads();
+    unsigned int base = 0, tot = 0;
+    for (int i = 0; i < 16; ++i) {
+        unsigned int t = wave_tot[i];
+        if (i < wv) base += t;
+        tot += t;
+    }
+    *total = tot;
+    return base + incl - v;
+}
+
 // IPT > 0: n <= 1024 * IPT and every thread keeps its IPT keys in registers -- the scores are read from memory ONCE (all
 // loads in flight together) instead of once per counting pass plus once for the collection; one workgroup pays a full
 // memory latency per dependent read round, which is what this kernel's time is made of.  IPT == 0: streaming form, any n.
@@ -109,9 +135,12 @@ struct TopkLds {
     unsigned int s_digit, s_above, s_cnt_sel, s_eq_base, s_a, s_b, s_c, s_d;
 };
 
-template <int IPT, int HIST_WORDS>
+// EMIT = false: the selection without its ordering step -- on return (behind a workgroup barrier) the k survivors sit in L.sel[0 .. k)
+// as composites in no particular order, L.hist is dead and idx_out is not touched.  tix = threadIdx.x (a caller that runs this in a loop
+// passes it through an opaque copy per trip: see multiclass_select_kernel)
+template <int IPT, bool EMIT = true, int HIST_WORDS>
 __device__ __forceinline__ void topk_radix_body(const float* __restrict__ scores, int64_t n, int64_t stride, int k,
-                                                int64_t* __restrict__ idx_out, TopkLds<HIST_WORDS>& L) {
+                                                int64_t* __restrict__ idx_out, TopkLds<HIST_WORDS>& L, const unsigned int tix) {
     constexpr bool REG = IPT > 0;
     static_assert(HIST_WORDS >= (REG ? 4 * 2048 : 2048), "histogram too small");
     unsigned int* const hist = L.hist;
@@ -128,15 +157,15 @@ __device__ __forceinline__ void topk_radix_body(const float* __restrict__ scores
     // slot u of thread t holds score index 4 (t + 1024 (u / 4)) + u % 4 with vector loads, t + 1024 u otherwise
     const bool vec = REG && stride == 1 && (reinterpret_cast<uintptr_t>(scores) & 15) == 0;
     auto slot_index = [&](int u) __attribute__((always_inline)) -> unsigned int {
-        return vec ? 4u * ((unsigned int)threadIdx.x + 1024u * (unsigned int)(u >> 2)) + (unsigned int)(u & 3)
-                   : (unsigned int)threadIdx.x + 1024u * (unsigned int)u;
+        return vec ? 4u * ((unsigned int)tix + 1024u * (unsigned int)(u >> 2)) + (unsigned int)(u & 3)
+                   : (unsigned int)tix + 1024u * (unsigned int)u;
     };
     unsigned int rkey[REG ? IPT : 1];
     if constexpr (REG) {
         if (vec) {   // uniform: 16-byte loads, 4 consecutive scores per slot group (one CU pulls dword loads at ~11 B/clk)
 #pragma unroll
             for (int g4 = 0; g4 < IPT / 4; ++g4) {
-                const int base = 4 * ((int)threadIdx.x + 1024 * g4);
+                const int base = 4 * ((int)tix + 1024 * g4);
                 if (base + 3 < n) {
                     const float4 f = *reinterpret_cast<const float4*>(scores + base);
                     rkey[4 * g4] = orderable_desc(f.x);
@@ -151,20 +180,20 @@ __device__ __forceinline__ void topk_radix_body(const float* __restrict__ scores
         } else if (stride == 1) {   // uniform: unit-stride scores need no 64-bit index multiply per load
 #pragma unroll
             for (int u = 0; u < IPT; ++u) {
-                const int i = (int)threadIdx.x + u * 1024;
+                const int i = (int)tix + u * 1024;
                 rkey[u] = (i < n) ? orderable_desc(scores[i]) : 0u;
             }
         } else {
 #pragma unroll
             for (int u = 0; u < IPT; ++u) {
-                const int64_t i = threadIdx.x + (int64_t)u * 1024;
+                const int64_t i = tix + (int64_t)u * 1024;
                 rkey[u] = (i < n) ? orderable_desc(scores[i * stride]) : 0u;
             }
         }
     }
     // first pass: 4 replicas interleaved per digit (word 4 d + lane % 4; 8 replicas measured slower) -- real scores crowd into a few dozen of the 2048
     // (sign, exponent, 2 mantissa bits) bins, and lanes adding to the SAME word serialise; later passes use words 0..2047
-    const int tid = threadIdx.x;
+    const int tid = tix;
     unsigned int prefix = 0, mask = 0, krem = (unsigned int)k, cnt_eq = 0;
     const int shifts[3] = {21, 10, 0};
     const int nbits[3] = {11, 11, 10};
@@ -219,7 +248,8 @@ __device__ __forceinline__ void topk_radix_body(const float* __restrict__ scores
             local += own[e];
         }
         unsigned int total;
-        const unsigned int below = block_excl_scan_1024(local, wave_tot, &total);   // keys with a smaller digit
+        const unsigned int below = EMIT ? block_excl_scan_1024(local, wave_tot, &total)   // keys with a smaller digit
+                                        : block_excl_scan_1024_dpp(local, wave_tot, &total, tix);
         unsigned int s_hi = total - below - local;                                   // keys in digits above this thread's
         for (int e = dpt - 1; e >= 0; --e) {
             const unsigned int s_d = s_hi + own[e];                                  // S(d) for d = dpt*tid + e
@@ -289,7 +319,8 @@ __device__ __forceinline__ void topk_radix_body(const float* __restrict__ scores
         }
         if (!take_all_eq) {   // ties straddle the k-th place: keep the lowest indices (uniform branch)
             unsigned int tot;
-            const unsigned int rank = s_eq_base + block_excl_scan_1024(eq ? 1u : 0u, wave_tot, &tot);
+            const unsigned int rank = s_eq_base + (EMIT ? block_excl_scan_1024(eq ? 1u : 0u, wave_tot, &tot)
+                                                        : block_excl_scan_1024_dpp(eq ? 1u : 0u, wave_tot, &tot, tix));
             if (eq && rank < krem) {
                 const unsigned int pos = atomicAdd(&s_cnt_sel, 1u);
                 sel[pos] = ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - (unsigned int)i);
@@ -301,7 +332,7 @@ __device__ __forceinline__ void topk_radix_body(const float* __restrict__ scores
     }
     __syncthreads();
     TSTAMP(9);
-    sort_emit(sel, k, idx_out);
+    if constexpr (EMIT) sort_emit(sel, k, idx_out);
     TSTAMP(10);
 }
 
@@ -309,7 +340,7 @@ template <int IPT>
 __global__ __launch_bounds__(1024) void topk_radix_kernel(const float* __restrict__ scores, int64_t n, int64_t stride, int k,
                                                           int64_t* __restrict__ idx_out) {
     __shared__ TopkLds<(IPT > 0) ? 4 * 2048 : 2048> L;
-    topk_radix_body<IPT>(scores, n, stride, k, idx_out, L);
+    topk_radix_body<IPT>(scores, n, stride, k, idx_out, L, threadIdx.x);
 }
 
 // many bags, one launch: workgroup b runs the one-workgroup form on scores[offsets[b] .. offsets[b + 1]) and writes the bag's k
@@ -322,7 +353,94 @@ __global__ __launch_bounds__(1024) void topk_radix_segmented_kernel(const float*
     const int64_t lo = offsets[blockIdx.x], hi = offsets[blockIdx.x + 1];
     // a bag shorter than k selects (and orders) all of its rows: entries k_b .. k - 1 of its output row are not written
     const int kb = hi - lo < k ? (int)(hi - lo) : k;
-    topk_radix_body<IPT>(scores + lo, hi - lo, 1, kb, idx_out + (int64_t)blockIdx.x * k, L);
+    topk_radix_body<IPT>(scores + lo, hi - lo, 1, kb, idx_out + (int64_t)blockIdx.x * k, L, threadIdx.x);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Class-union selection of the multiclass model (snuffy_multiclass.py:136-141): for every class c the k1 highest of scores[b, :, c],
+// then the ascending, duplicate-free union of those indices.  ONE workgroup per batch row runs the selection above without its
+// ordering step (EMIT = false) on every column in turn (stride = C) and keeps each column's k1 survivor indices; after the last
+// column it sorts the C k1 candidates (bitonic, 32-bit, in the histogram's words, which are dead by then), flags the first of every
+// run, scans the flags and writes.  No workgroup ever waits for or reads from another one, and nothing but plain stores reaches
+// global memory.
+//
+// LDS: TopkLds<8192> is 48 KiB + 96 bytes, which leaves 4072 words under the 64 KiB of static LDS -- 24 short of the (C - 1) k1 <=
+// 4095 candidates of the earlier columns.  Candidates 4072 .. 4095 therefore live in the last 12 slots of L.sel: those candidates
+// exist only at k1 < 24, where a column's survivors stay far below slot 2036, and the slots are in use only at k1 > 2036, where
+// C <= 2 keeps the earlier columns' candidates below 2048.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int MC_MAX_CAND = 4096;      // C * k1
+constexpr int MC_PREV_WORDS = 4072;    // candidates of the earlier columns held outside TopkLds
+
+template <int IPT>
+__global__ __launch_bounds__(1024) void multiclass_select_kernel(const float* __restrict__ scores, int64_t n, int ncls, int k1,
+                                                                 int64_t* __restrict__ uniq_out, int32_t* __restrict__ count_out) {
+    constexpr int HW = (IPT > 0) ? 4 * 2048 : MC_MAX_CAND;   // the streaming form's 2048 words would not hold the final sort
+    __shared__ TopkLds<HW> L;
+    __shared__ unsigned int prev[MC_PREV_WORDS];
+    static_assert(sizeof(TopkLds<HW>) + sizeof(unsigned int) * MC_PREV_WORDS <= 65536, "static LDS above 64 KiB");
+    static_assert(HW >= MC_MAX_CAND, "the final sort runs in the histogram");
+    const float* const row = scores + (int64_t)blockIdx.x * n * ncls;
+    unsigned int* const over = reinterpret_cast<unsigned int*>(L.sel + RS_MAXK) - (MC_MAX_CAND - MC_PREV_WORDS);
+    auto cand = [&](int i) __attribute__((always_inline)) -> unsigned int& {
+        return i < MC_PREV_WORDS ? prev[i] : over[i - MC_PREV_WORDS];
+    };
+    const int total = ncls * k1, prior = total - k1;
+    unsigned int tix = threadIdx.x;
+    for (int c = 0; c < ncls; ++c) {
+        // opaque per column: hoisted out of this loop, the per-key terms that depend on the thread index alone (slot indices, bounds
+        // tests, address offsets) would stay in registers over the whole loop -- several per key, spilled from IPT = 16 on
+        asm volatile("" : "+v"(tix));
+        topk_radix_body<IPT, false>(row + c, n, ncls, k1, nullptr, L, tix);
+        if (c + 1 < ncls) {   // the last column's survivors are read where they are
+            for (int j = (int)tix; j < k1; j += 1024) cand(c * k1 + j) = 0xffffffffu - (unsigned int)(L.sel[j] & 0xffffffffull);
+            __syncthreads();   // the next column rewrites L.sel
+        }
+    }
+    const int tid = (int)tix;
+    // all candidates into the histogram's words, padded to a power of two with a value no index reaches (n < 2^30)
+    unsigned int* const buf = L.hist;
+    int p2 = 1;
+    while (p2 < total) p2 <<= 1;
+    for (int i = tid; i < p2; i += 1024) {
+        unsigned int v = 0xffffffffu;
+        if (i < prior) v = cand(i);
+        else if (i < total) v = 0xffffffffu - (unsigned int)(L.sel[i - prior] & 0xffffffffull);
+        buf[i] = v;
+    }
+    for (int size = 2; size <= p2; size <<= 1) {
+        for (int st = size >> 1; st > 0; st >>= 1) {
+            __syncthreads();
+            for (int p = tid; p < p2 / 2; p += 1024) {
+                const int lo = 2 * p - (p & (st - 1));
+                const int hi = lo + st;
+                const bool asc = (lo & size) == 0;
+                const unsigned int a = buf[lo], b = buf[hi];
+                if (asc ? (a > b) : (a < b)) {
+                    buf[lo] = b;
+                    buf[hi] = a;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // thread t owns sorted entries 4 t .. 4 t + 3: the first of every run of equal indices is kept
+    unsigned int v[4], prevv = 0xffffffffu;
+    unsigned int keep = 0;
+    if (4 * tid > 0 && 4 * tid < total) prevv = buf[4 * tid - 1];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int i = 4 * tid + e;
+        v[e] = i < total ? buf[i] : 0xffffffffu;
+        if (i < total && (i == 0 || v[e] != (e ? v[e - 1] : prevv))) keep |= 1u << e;
+    }
+    unsigned int tot;
+    unsigned int pos = block_excl_scan_1024_dpp((unsigned int)__builtin_popcount(keep), L.wave_tot, &tot, tix);
+    int64_t* const dst = uniq_out + (int64_t)blockIdx.x * total;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (keep & (1u << e)) dst[pos++] = (int64_t)v[e];
+    if (tid == 0) count_out[blockIdx.x] = (int32_t)tot;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -502,7 +620,7 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(const float* __restri
         __syncthreads();
         sort_emit(L.sel, k, idx_out);
     } else {
-        topk_radix_body<0>(scores, n, stride, k, idx_out, L);
+        topk_radix_body<0>(scores, n, stride, k, idx_out, L, threadIdx.x);
         if (tid == 0) st->fallbacks += 1;
     }
     // leave the counted state zeroed for the next call (nobody else reads or writes it any more)
@@ -616,6 +734,33 @@ int snf_topk_segmented_f32(const float* scores, const int64_t* offsets_dev, int 
     else
         hipLaunchKernelGGL(topk_radix_segmented_kernel<0>, grid, wg, 0, s, scores, offsets_dev, k, idx_out);
     return snf::check_launch("topk_radix_segmented_kernel");
+}
+
+// class-union selection of the multiclass model, every batch row in ONE launch (one workgroup per row, the classes looped inside it).
+// scores [b, n, c] f32 contiguous; uniq_out [b, c * k1]: row i holds the ascending union of the per-class top-k1 indices in its first
+// count_out[i] entries, the rest is not written.
+int snf_multiclass_select_f32(const float* scores, int b, int64_t n, int c, int k1, int64_t* uniq_out, int32_t* count_out,
+                              snf_stream_t stream) {
+    SNF_REQUIRE(scores && uniq_out && count_out, "snf_multiclass_select_f32: null pointer");
+    SNF_REQUIRE(b >= 1 && c >= 1 && n >= 1 && n < 0x3fffffffll, "snf_multiclass_select_f32: bad b=%d n=%lld c=%d", b, (long long)n, c);
+    SNF_REQUIRE(k1 >= 1 && k1 <= n, "snf_multiclass_select_f32: need 1 <= k1 <= n (k1=%d n=%lld)", k1, (long long)n);
+    if (k1 > RS_MAXK || (int64_t)c * k1 > MC_MAX_CAND) {
+        snf::set_error("snf_multiclass_select_f32: k1=%d c=%d is outside the kernel (k1 <= %d, c * k1 <= %d)", k1, c, RS_MAXK, MC_MAX_CAND);
+        return SNF_EUNSUPPORTED;
+    }
+    hipStream_t s = snf::as_stream(stream);
+    const dim3 grid((unsigned)b), wg(1024);
+    if (n <= 1024 * 8)
+        hipLaunchKernelGGL(multiclass_select_kernel<8>, grid, wg, 0, s, scores, n, c, k1, uniq_out, count_out);
+    else if (n <= 1024 * 16)
+        hipLaunchKernelGGL(multiclass_select_kernel<16>, grid, wg, 0, s, scores, n, c, k1, uniq_out, count_out);
+    else if (n <= 1024 * 32)
+        hipLaunchKernelGGL(multiclass_select_kernel<32>, grid, wg, 0, s, scores, n, c, k1, uniq_out, count_out);
+    else if (n <= 1024 * 64)
+        hipLaunchKernelGGL(multiclass_select_kernel<64>, grid, wg, 0, s, scores, n, c, k1, uniq_out, count_out);
+    else
+        hipLaunchKernelGGL(multiclass_select_kernel<0>, grid, wg, 0, s, scores, n, c, k1, uniq_out, count_out);
+    return snf::check_launch("multiclass_select_kernel");
 }
 
 int snf_topk_gather_f32(const float* scores, int64_t n, int64_t stride, int k, int64_t* idx_out, const float* x, int d,

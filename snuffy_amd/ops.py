@@ -241,6 +241,32 @@ def topk_hist_select(scores, k):
     return idx
 
 
+MULTICLASS_SELECT_MAX_CAND = 4096    # c * k1 of snf_multiclass_select_f32 (the candidate list of one workgroup's LDS)
+
+
+def multiclass_select_supported(b, n, c, k1):
+    """Domain of multiclass_select(): 1 <= k1 <= min(n, 2048), c * k1 <= 4096, n < 2^30."""
+    return b >= 1 and c >= 1 and 1 <= k1 <= min(n, TOPK_MAX_K) and c * k1 <= MULTICLASS_SELECT_MAX_CAND and n < (1 << 30)
+
+
+def multiclass_select(c, k1):
+    """Class-union selection of the multiclass model (snuffy_multiclass.py:136-141) for every batch row in ONE launch.
+
+    c [B, N, C] f32 -> (uniq [B, C * k1] int64, counts [B] int32), both on the device: row b's ascending, duplicate-free union of the
+    per-class top-k1 indices (descending score, ties by ascending index, as topk()) in uniq[b, :counts[b]]; the rest of the row is
+    uninitialised."""
+    c = _req(c, torch.float32, "c", 3)
+    b, n, ncls = c.shape
+    k1 = int(k1)
+    if not multiclass_select_supported(b, n, ncls, k1):
+        raise _ffi.SnuffyHipError("multiclass_select: B=%d N=%d C=%d k1=%d is outside the kernel (1 <= k1 <= min(N, %d), C * k1 <= %d)"
+                                  % (b, n, ncls, k1, TOPK_MAX_K, MULTICLASS_SELECT_MAX_CAND))
+    uniq = torch.empty(b, ncls * k1, dtype=torch.int64, device=c.device)
+    counts = torch.empty(b, dtype=torch.int32, device=c.device)
+    check(_ffi.load().snf_multiclass_select_f32(_p(c), b, n, ncls, k1, _p(uniq), _p(counts), _stream()), "snf_multiclass_select_f32")
+    return uniq, counts
+
+
 class DeviceSampler:
     """State of the device-side random patch share (csrc/sampler.hip): a 16-byte device record {seed, offset}.  The seed is torch's
     CPU seed at construction and the first offset is drawn from torch's CPU generator (reproducible under torch.manual_seed, no
@@ -268,6 +294,37 @@ class DeviceSampler:
         if k2 == 0:
             return torch.empty(0, dtype=torch.int64, device=keys.device)
         return topk(keys, k2)
+
+    def draw_batch(self, n, k, uniq, counts, layer=0):
+        """draw() for B batch rows at once: k rows of 0 .. n - 1 per row outside uniq[b, :counts[b]] (uniq [B, pitch] int64, counts [B]
+        int32, both on the device and never read on the host) -> [B, k] int64.  Row b draws from stream layer + 64 b, row 0 from the
+        stream draw() uses; the caller guarantees k <= n - counts[b]."""
+        uniq = _req(uniq, torch.int64, "uniq", 2)
+        counts = _req(counts, torch.int32, "counts", 1)
+        b, pitch = uniq.shape
+        n, k = int(n), int(k)
+        if counts.shape[0] != b or not (1 <= b <= 64) or not (0 <= int(layer) < 64) or not (0 <= k <= min(n, TOPK_MAX_K)):
+            raise ValueError("DeviceSampler.draw_batch: B=%d (<= 64) layer=%d (< 64) k=%d n=%d" % (b, layer, k, n))
+        if k == 0:
+            return torch.empty(b, 0, dtype=torch.int64, device=uniq.device)
+        keys = torch.empty(b, n, dtype=torch.float32, device=self.state.device)
+        check(_ffi.load().snf_random_share_keys_batched_f32(_p(self.state), int(layer), b, n, _p(uniq), _p(counts), pitch, _p(keys),
+                                                            _stream()), "snf_random_share_keys_batched_f32")
+        return topk_segmented(keys.view(-1), _uniform_bags(b, n, keys.device), k)
+
+
+_UNIFORM_BAGS = {}
+
+
+def _uniform_bags(b, n, device):
+    """PackedBags of b bags of n rows each (offsets uploaded once per shape)."""
+    key = (b, n, str(device))
+    pk = _UNIFORM_BAGS.get(key)
+    if pk is None:
+        if len(_UNIFORM_BAGS) >= 64:
+            _UNIFORM_BAGS.pop(next(iter(_UNIFORM_BAGS)))
+        pk = _UNIFORM_BAGS[key] = PackedBags([n] * b, device)
+    return pk
 
 
 def gather_rows(x, idx):

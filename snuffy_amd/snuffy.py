@@ -307,7 +307,8 @@ class MILNet(nn.Module):
         stays on the device (random_patch_share == 0, or sampler="device"), outside autograd.
         sampler: "reference" (default: the random patch share is np.random.choice on the host, the reference's MT19937 draws bit
         for bit) or "device" (opt-in fast mode: Philox keys + top-k on the GPU, same distribution, no host sync; a captured graph
-        draws fresh rows on every replay).  "device" applies to the one-bag-per-forward path; forward_bags (packed.py) draws the
+        draws fresh rows on every replay).  "device" applies to the one-bag-per-forward path and to the multiclass model's batch
+        (snuffy_multiclass: every row's draw in one launch pair, never graph-captured: its ref_dim read is a sync); forward_bags (packed.py) draws the
         random share of a packed batch with the reference's host draws whatever this says, and is not graph-captured then."""
         self.b_classifier.configure(precision, return_attention)
         if sampler is not None:
