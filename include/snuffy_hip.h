@@ -717,8 +717,21 @@ int snf_ln_mean_head_varlen_f32(const float* z, const int64_t* offsets, int bags
  *     from stream layer + 64 i (row 0 is the single-row stream; layer < 64, b <= 64), keys[i, exclude[i, j]] = -1 for
  *     j < counts_dev[i] (exclude [b, pitch] int64, counts_dev [b] int32, both in DEVICE memory: the counts are never read on the host).
  *     The k2 largest keys of every row: snf_topk_segmented_f32 over the b rows of n keys.
+ *   snf_random_share_draw_segmented_f32: the draws of every bag and every layer of a PACKED batch (varlen path).  offsets_dev [bags + 1]
+ *     and top [bags, k1] as snf_topk_segmented_f32 takes / writes them (a bag with n_b < k1 rows: its first n_b entries are read);
+ *     rnd_out [layers, bags, k2] int64, indices inside each bag: bag b's first k2_b = min(k2, max(0, n_b - k1)) entries are its draw
+ *     (descending key, ties by ascending row), the rest of the row is padding.  Bag b draws from offset state[1] + 1 + b, layer l from
+ *     stream l << 48 -- what the b-th of `bags` single-bag forwards (advance, keys, top-k) draws -- and the record is advanced by `bags`
+ *     on the device behind the draws.  max_n (the longest bag) <= 32768: ONE launch, one workgroup per (bag, layer), the keys are made in
+ *     registers and never reach memory.  Up to 65536: per layer a key image of the packed rows in `workspace` (total_rows floats,
+ *     snf_random_share_draw_workspace_bytes) and snf_topk_segmented_f32 on it.  layers > 4096, k2 > 2048, longer bags or a missing
+ *     workspace: SNF_EUNSUPPORTED.
  * --------------------------------------------------------------------------------------------------------- */
 int snf_sampler_advance(void* state, snf_stream_t stream);
+size_t snf_random_share_draw_workspace_bytes(int64_t max_n, int64_t total_rows);
+int snf_random_share_draw_segmented_f32(void* state, int layers, const int64_t* offsets_dev, int bags, int64_t max_n, int64_t total_rows,
+                                        const int64_t* top, int k1, int k2, int64_t* rnd_out, void* workspace, size_t workspace_bytes,
+                                        snf_stream_t stream);
 int snf_random_share_keys_f32(const void* state, int layer, int64_t n, const int64_t* exclude_rows, int n_exclude, float* keys,
                               snf_stream_t stream);
 int snf_random_share_keys_batched_f32(const void* state, int layer, int b, int64_t n, const int64_t* exclude, const int32_t* counts_dev,

@@ -203,6 +203,9 @@ SIGNATURES = {
     "snf_sampler_advance": (c_int, [c_void_p, c_void_p]),
     "snf_random_share_keys_f32": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "snf_random_share_keys_batched_f32": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "snf_random_share_draw_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "snf_random_share_draw_segmented_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p,
+                                                    c_void_p, c_size_t, c_void_p]),
     "snf_multiclass_select_f32": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "snf_debug_attn_trace": (None, [c_void_p]),
     "snf_debug_attn_trace_wg": (None, [c_int]),

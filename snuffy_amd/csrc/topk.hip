@@ -13,6 +13,7 @@
 // classify their slice (above the threshold bin / inside it) and append the few hundred survivors to two short lists; the
 // workgroup that arrives last finishes the selection on those lists alone.  Same result, bit for bit.
 #include "selector.h"
+#include "philox.h"
 
 namespace {
 
@@ -135,13 +136,24 @@ struct TopkLds {
     unsigned int s_digit, s_above, s_cnt_sel, s_eq_base, s_a, s_b, s_c, s_d;
 };
 
+// Key source of the device sampler (GEN = true below): the keys are not read from memory but made in registers, one Philox4x32-10 call
+// per slot group of 4 consecutive rows (counter word 0 = row / 4, element row & 3 -- sampler_keys_kernel's mapping in sampler.hip).  A
+// row whose bit is set in the LDS bitmap `excl` gets the key of -1, every other row the key of its 30 random bits read as a positive float.
+struct PhiloxKeys {
+    unsigned int seed_lo, seed_hi, off_lo, off_hi;
+    const unsigned int* excl;
+};
+
 // EMIT = false: the selection without its ordering step -- on return (behind a workgroup barrier) the k survivors sit in L.sel[0 .. k)
 // as composites in no particular order, L.hist is dead and idx_out is not touched.  tix = threadIdx.x (a caller that runs this in a loop
 // passes it through an opaque copy per trip: see multiclass_select_kernel)
-template <int IPT, bool EMIT = true, int HIST_WORDS>
+// GEN = true (register forms only): `scores` is not read, the keys come from *gen in the slot layout of the vector path
+template <int IPT, bool EMIT = true, bool GEN = false, int HIST_WORDS>
 __device__ __forceinline__ void topk_radix_body(const float* __restrict__ scores, int64_t n, int64_t stride, int k,
-                                                int64_t* __restrict__ idx_out, TopkLds<HIST_WORDS>& L, const unsigned int tix) {
+                                                int64_t* __restrict__ idx_out, TopkLds<HIST_WORDS>& L, const unsigned int tix,
+                                                const PhiloxKeys* gen = nullptr) {
     constexpr bool REG = IPT > 0;
+    static_assert(!GEN || (REG && IPT % 4 == 0), "generated keys live in registers");
     static_assert(HIST_WORDS >= (REG ? 4 * 2048 : 2048), "histogram too small");
     unsigned int* const hist = L.hist;
     unsigned long long* const sel = L.sel;
@@ -155,13 +167,29 @@ __device__ __forceinline__ void topk_radix_body(const float* __restrict__ scores
     // and never passes the final threshold, so the per-key loops below carry no bounds test.
     TSTAMP(0);
     // slot u of thread t holds score index 4 (t + 1024 (u / 4)) + u % 4 with vector loads, t + 1024 u otherwise
-    const bool vec = REG && stride == 1 && (reinterpret_cast<uintptr_t>(scores) & 15) == 0;
+    const bool vec = GEN || (REG && stride == 1 && (reinterpret_cast<uintptr_t>(scores) & 15) == 0);
     auto slot_index = [&](int u) __attribute__((always_inline)) -> unsigned int {
         return vec ? 4u * ((unsigned int)tix + 1024u * (unsigned int)(u >> 2)) + (unsigned int)(u & 3)
                    : (unsigned int)tix + 1024u * (unsigned int)u;
     };
     unsigned int rkey[REG ? IPT : 1];
-    if constexpr (REG) {
+    if constexpr (GEN) {
+#pragma unroll
+        for (int g4 = 0; g4 < IPT / 4; ++g4) {
+            const unsigned int grp = tix + 1024u * (unsigned int)g4;
+            const int base = 4 * (int)grp;
+            if (base < n) {   // rows base .. base + 3 share one word of the bitmap
+                const snf::philox_u4 r = snf::philox4x32_10(snf::philox_u4{grp, 0u, gen->off_lo, gen->off_hi}, gen->seed_lo, gen->seed_hi);
+                const unsigned int ex = gen->excl[base >> 5] >> (base & 31);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    rkey[4 * g4 + e] = (base + e < n) ? (((ex >> e) & 1u) ? orderable_desc(-1.f) : ((r[e] >> 2) | 0x80000000u)) : 0u;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) rkey[4 * g4 + e] = 0u;
+            }
+        }
+    } else if constexpr (REG) {
         if (vec) {   // uniform: 16-byte loads, 4 consecutive scores per slot group (one CU pulls dword loads at ~11 B/clk)
 #pragma unroll
             for (int g4 = 0; g4 < IPT / 4; ++g4) {
@@ -354,6 +382,71 @@ __global__ __launch_bounds__(1024) void topk_radix_segmented_kernel(const float*
     // a bag shorter than k selects (and orders) all of its rows: entries k_b .. k - 1 of its output row are not written
     const int kb = hi - lo < k ? (int)(hi - lo) : k;
     topk_radix_body<IPT>(scores + lo, hi - lo, 1, kb, idx_out + (int64_t)blockIdx.x * k, L, threadIdx.x);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Random patch share of a packed batch (snuffy.py:134-143 with the device sampler of sampler.hip): workgroup (b, l) draws layer l's
+// k2 random rows of bag b outside the bag's top rows.  It marks top[b, :min(k1, n_b)] in an LDS bitmap, makes the bag's Philox keys
+// in registers (PhiloxKeys) and runs the selection above on them: the k2_b = min(k2, n_b - min(k1, n_b)) largest keys, descending,
+// ties by ascending row, into rnd[l, b, :k2_b].  The keys never reach memory and no workgroup waits for another.  Bag b draws from
+// Philox offset state[1] + 1 + b and stream l << 48 -- what the b-th of B one-bag forwards draws after its own advance of the record.
+// ---------------------------------------------------------------------------------------------------------------
+template <int IPT>
+__global__ __launch_bounds__(1024) void random_share_draw_kernel(const unsigned long long* __restrict__ state,
+                                                                 const int64_t* __restrict__ offsets, const int64_t* __restrict__ top,
+                                                                 int k1, int k2, int64_t* __restrict__ rnd) {
+    __shared__ TopkLds<4 * 2048> L;
+    __shared__ unsigned int excl[IPT * 32];   // one bit per row of the longest bag of this form
+    static_assert(sizeof(TopkLds<4 * 2048>) + sizeof(unsigned int) * IPT * 32 <= 65536, "static LDS above 64 KiB");
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x, layer = blockIdx.y;
+    const int64_t n64 = offsets[b + 1] - offsets[b];
+    if (n64 < 1 || n64 > 1024 * IPT) return;   // outside this form (the caller's max_n is wrong): nothing is written
+    const int n = (int)n64;
+    const int ne = n < k1 ? n : k1;            // valid entries of the bag's row of top
+    const int kb = n - ne < k2 ? n - ne : k2;
+    if (kb <= 0) return;                       // no row left to draw from
+    for (int i = tid; i < IPT * 32; i += 1024) excl[i] = 0u;
+    __syncthreads();
+    for (int i = tid; i < ne; i += 1024) {
+        const int64_t r = top[b * k1 + i];
+        if (r >= 0 && r < n) atomicOr(&excl[r >> 5], 1u << (r & 31));
+    }
+    __syncthreads();
+    const unsigned long long seed = state[0], off = state[1] + 1ull + (unsigned long long)b + ((unsigned long long)layer << 48);
+    const PhiloxKeys gen{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)off, (unsigned)(off >> 32), excl};
+    topk_radix_body<IPT, true, true>(nullptr, n, 1, kb, rnd + (layer * (int64_t)gridDim.x + b) * k2, L, threadIdx.x, &gen);
+}
+
+// Bags above the register forms (32 k < n_b <= 64 k): layer l's keys of every bag as an image in memory, which the segmented
+// selection then reads.  blockIdx.y = bag; same counters, offsets and keys as random_share_draw_kernel.
+__global__ __launch_bounds__(256) void random_share_keys_segmented_kernel(const unsigned long long* __restrict__ state,
+                                                                          unsigned long long layer, const int64_t* __restrict__ offsets,
+                                                                          int64_t total, float* __restrict__ keys) {
+    const int64_t b = blockIdx.y, lo = offsets[b], n = offsets[b + 1] - lo;
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;      // rows 4 g .. 4 g + 3 of the bag
+    if (4 * g >= n) return;
+    const unsigned long long seed = state[0], off = state[1] + 1ull + (unsigned long long)b + (layer << 48);
+    const snf::philox_u4 r = snf::philox4x32_10(snf::philox_u4{(unsigned)g, 0u, (unsigned)off, (unsigned)(off >> 32)}, (unsigned)seed,
+                                                (unsigned)(seed >> 32));
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (4 * g + e < n && lo + 4 * g + e < total) keys[lo + 4 * g + e] = __uint_as_float(r[e] >> 2);
+}
+
+__global__ __launch_bounds__(256) void random_share_exclude_segmented_kernel(const int64_t* __restrict__ offsets,
+                                                                             const int64_t* __restrict__ top, int k1, int64_t total,
+                                                                             float* __restrict__ keys) {
+    const int64_t b = blockIdx.y, lo = offsets[b], n = offsets[b + 1] - lo;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < k1 && i < n) {
+        const int64_t r = top[b * k1 + i];
+        if (r >= 0 && r < n && lo + r < total) keys[lo + r] = -1.f;
+    }
+}
+
+__global__ __launch_bounds__(64) void sampler_advance_by_kernel(unsigned long long* state, unsigned long long count) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) state[1] += count;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -761,6 +854,66 @@ int snf_multiclass_select_f32(const float* scores, int b, int64_t n, int c, int 
     else
         hipLaunchKernelGGL(multiclass_select_kernel<0>, grid, wg, 0, s, scores, n, c, k1, uniq_out, count_out);
     return snf::check_launch("multiclass_select_kernel");
+}
+
+// Random patch share of every bag and every layer of a packed batch (device sampler).  state: the 16-byte {seed, offset} record; top
+// [bags, k1] as snf_topk_segmented_f32 writes it (a bag with n_b < k1 rows: its first n_b entries); rnd_out [layers, bags, k2], indices
+// inside each bag -- bag b's first min(k2, max(0, n_b - k1)) entries are its draw, the rest of the row is padding.  Bag b draws from
+// Philox offset state[1] + 1 + b, layer l from stream l << 48; the record is advanced by `bags` on the device behind the draws.
+// max_n <= 32768: ONE launch, keys in registers.  Up to 65536: per layer a key image of the packed rows in `workspace` (total_rows
+// floats: snf_random_share_draw_workspace_bytes) and the segmented selection on it.
+size_t snf_random_share_draw_workspace_bytes(int64_t max_n, int64_t total_rows) {
+    return max_n > 1024 * 32 && total_rows > 0 ? (size_t)total_rows * sizeof(float) : 0;
+}
+
+int snf_random_share_draw_segmented_f32(void* state, int layers, const int64_t* offsets_dev, int bags, int64_t max_n, int64_t total_rows,
+                                        const int64_t* top, int k1, int k2, int64_t* rnd_out, void* workspace, size_t workspace_bytes,
+                                        snf_stream_t stream) {
+    SNF_REQUIRE(state && offsets_dev && top && rnd_out && (reinterpret_cast<uintptr_t>(state) & 7) == 0,
+                "snf_random_share_draw_segmented_f32: null / unaligned pointer");
+    SNF_REQUIRE(bags >= 1 && max_n >= 1 && total_rows >= max_n && k1 >= 1 && k2 >= 1,
+                "snf_random_share_draw_segmented_f32: bad bags=%d max_n=%lld total_rows=%lld k1=%d k2=%d", bags, (long long)max_n,
+                (long long)total_rows, k1, k2);
+    if (layers < 1 || layers > 4096 || k2 > RS_MAXK || max_n > TOPK_SINGLE_WG_MAX_N) {
+        snf::set_error("snf_random_share_draw_segmented_f32: layers=%d k2=%d max_n=%lld is outside the kernel (layers <= 4096, k2 <= %d, "
+                       "bags of at most %lld rows)", layers, k2, (long long)max_n, RS_MAXK, (long long)TOPK_SINGLE_WG_MAX_N);
+        return SNF_EUNSUPPORTED;
+    }
+    hipStream_t s = snf::as_stream(stream);
+    unsigned long long* st = reinterpret_cast<unsigned long long*>(state);
+    int rc = 0;
+    if (max_n <= 1024 * 32) {
+        const dim3 grid((unsigned)bags, (unsigned)layers), wg(1024);
+        if (max_n <= 1024 * 8)
+            hipLaunchKernelGGL(random_share_draw_kernel<8>, grid, wg, 0, s, st, offsets_dev, top, k1, k2, rnd_out);
+        else if (max_n <= 1024 * 16)
+            hipLaunchKernelGGL(random_share_draw_kernel<16>, grid, wg, 0, s, st, offsets_dev, top, k1, k2, rnd_out);
+        else
+            hipLaunchKernelGGL(random_share_draw_kernel<32>, grid, wg, 0, s, st, offsets_dev, top, k1, k2, rnd_out);
+        rc = snf::check_launch("random_share_draw_kernel");
+        if (rc) return rc;
+    } else {
+        if (!workspace || workspace_bytes < (size_t)total_rows * sizeof(float) || bags > 65535) {
+            snf::set_error("snf_random_share_draw_segmented_f32: bags above 32768 rows need a workspace of %lld bytes (got %lld) and at "
+                           "most 65535 bags (bags=%d)", (long long)(total_rows * (int64_t)sizeof(float)), (long long)workspace_bytes, bags);
+            return SNF_EUNSUPPORTED;
+        }
+        float* keys = reinterpret_cast<float*>(workspace);
+        for (int l = 0; l < layers; ++l) {
+            hipLaunchKernelGGL(random_share_keys_segmented_kernel, dim3((unsigned)((max_n + 1023) / 1024), (unsigned)bags), dim3(256), 0, s,
+                               st, (unsigned long long)l, offsets_dev, total_rows, keys);
+            rc = snf::check_launch("random_share_keys_segmented_kernel");
+            if (rc) return rc;
+            hipLaunchKernelGGL(random_share_exclude_segmented_kernel, dim3((unsigned)((k1 + 255) / 256), (unsigned)bags), dim3(256), 0, s,
+                               offsets_dev, top, k1, total_rows, keys);
+            rc = snf::check_launch("random_share_exclude_segmented_kernel");
+            if (rc) return rc;
+            rc = snf_topk_segmented_f32(keys, offsets_dev, bags, max_n, k2, rnd_out + (int64_t)l * bags * k2, stream);
+            if (rc) return rc;
+        }
+    }
+    hipLaunchKernelGGL(sampler_advance_by_kernel, dim3(1), dim3(64), 0, s, st, (unsigned long long)bags);
+    return snf::check_launch("sampler_advance_by_kernel");
 }
 
 int snf_topk_gather_f32(const float* scores, int64_t n, int64_t stride, int k, int64_t* idx_out, const float* x, int d,

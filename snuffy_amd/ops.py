@@ -313,6 +313,40 @@ class DeviceSampler:
         return topk_segmented(keys.view(-1), _uniform_bags(b, n, keys.device), k)
 
 
+    def draw_packed(self, packed, k1, k2, top, layers):
+        """The random share of every bag and every layer of a packed batch in ONE launch (snf_random_share_draw_segmented_f32):
+        top [B, k1] int64 as topk_segmented() returns it -> [layers, B, k2] int64, indices inside each bag.  Bag b's first
+        min(k2, max(0, n_b - k1)) entries are its draw, the rest of its row is uninitialised padding.  Bag b draws from Philox offset
+        (record) + 1 + b and layer l from stream l << 48 -- exactly what advance() + draw(layer=l) of the b-th of B one-bag forwards
+        draws -- and the record moves on by B on the device.  No device data is read on the host."""
+        top = _req(top, torch.int64, "top", 2)
+        k1, k2, layers = int(k1), int(k2), int(layers)
+        if tuple(top.shape) != (packed.bags, k1) or top.device != self.state.device or packed.dev.device != self.state.device:
+            raise ValueError("DeviceSampler.draw_packed: top %s on %s for %d bags, k1=%d" % (tuple(top.shape), top.device, packed.bags, k1))
+        if not draw_packed_supported(packed.max_n, k1, k2, layers):
+            raise _ffi.SnuffyHipError("DeviceSampler.draw_packed: max_n=%d k1=%d k2=%d layers=%d is outside the kernel (bags of at most "
+                                      "%d rows, 1 <= k2 <= %d, layers <= %d)" % (packed.max_n, k1, k2, layers, DRAW_PACKED_MAX_N,
+                                                                                TOPK_MAX_K, DRAW_PACKED_MAX_LAYERS))
+        _on_current_device(top, "top")
+        lib = _ffi.load()
+        rnd = torch.empty(layers, packed.bags, k2, dtype=torch.int64, device=top.device)
+        wsb = lib.snf_random_share_draw_workspace_bytes(packed.max_n, packed.total)
+        ws = _ws(wsb, top.device)
+        check(lib.snf_random_share_draw_segmented_f32(_p(self.state), layers, _p(packed.dev), packed.bags, packed.max_n, packed.total,
+                                                      _p(top), k1, k2, _p(rnd), _p(ws), wsb, _stream()),
+              "snf_random_share_draw_segmented_f32")
+        return rnd
+
+
+DRAW_PACKED_MAX_N = 65536        # longest bag of DeviceSampler.draw_packed (one workgroup per bag and layer)
+DRAW_PACKED_MAX_LAYERS = 4096
+
+
+def draw_packed_supported(max_n, k1, k2, layers):
+    """Domain of DeviceSampler.draw_packed(): bags of 1 .. 65536 rows, k1 >= 1, 1 <= k2 <= 2048, 1 <= layers <= 4096."""
+    return 1 <= max_n <= DRAW_PACKED_MAX_N and k1 >= 1 and 1 <= k2 <= TOPK_MAX_K and 1 <= layers <= DRAW_PACKED_MAX_LAYERS
+
+
 _UNIFORM_BAGS = {}
 
 

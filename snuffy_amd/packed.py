@@ -16,6 +16,13 @@ from . import snuffy
 # loop at every measured composition of both recipes -- 64 x 1000 patches 4.3 - 8.5x, 64 x 8000 1.00 - 1.34x fp32-class / 1.9 - 2.5x bf16,
 # the synthetic CAMELYON16-shaped mix 1.1 - 1.95x -- with no crossover in bag length up to PACK_MAX_ROWS per launch set: no length gate.
 PACK_KEY_CHUNKS = True
+# The random patch share of a packed batch drawn on the device when the model is configured with sampler="device": ONE launch
+# (ops.DeviceSampler.draw_packed) for every bag and layer instead of a device -> host copy of the top rows and one np.random.choice per bag
+# and layer, several groups (uniform chunks and a ragged group) instead of one, and graph replay under graph_max_patches.  False: the
+# routing of before -- host draws whatever the sampler, one uniform group, never captured.  The rule PACK_KEY_CHUNKS follows decides the
+# shipped value: on only where the device route is at least level with the host draws at every composition of
+# profiles/packed_device_sampler.txt (tools/packed_sampler_time.py).
+PACK_DEVICE_SAMPLER = True
 RAGGED_MAX_ROWS = 4096      # longest bag the ragged (exact fp32, one workgroup per bag and head) attention is meant for
 
 
@@ -28,7 +35,12 @@ def pack_groups(net, bags):
     between the kernels', zero-padded).  "ragged" groups: bags shorter than Lambda (they select
     ALL their rows, snuffy.py:129) or head widths outside the MFMA kernels (the MIL benchmark sets: D = 166 / 230, h = 2) --
     exact-fp32 ragged attention, bags of at most _RAGGED_MAX_ROWS patches.  With a random share the draws of the reference
-    must stay in bag order, so only one uniform group over all bags is formed."""
+    sampler must stay in bag order, so only one uniform group over all bags is formed.  With the device sampler
+    (device_draws()) a random-share model is grouped like a deterministic one: uniform groups hold the bags with at least
+    k1 + k2 rows, a ragged bag selects its min(k1, n_b) top rows and min(k2, n_b - min(k1, n_b)) random ones, min(k1 + k2, n_b)
+    keys.  Philox offsets follow the order in which forward_bags() runs things: the groups in the order returned here (the
+    uniform chunks, then the ragged ones), each taking one offset per bag in the group's bag order, then the bags left to the
+    per-bag loop in their own order."""
     cfg = net.b_classifier.cfg
     layers = list(net.b_classifier.encoder.layers)
     if (len(bags) < 2 or net.training or torch.is_grad_enabled() or type(net.i_classifier) is not snuffy.FCLayer or not layers
@@ -60,19 +72,25 @@ def pack_groups(net, bags):
     uniform_dims = (d % 4 == 0 and (SF.ops.varlen_attn_supported(cfg.compute, k1 + k2, d // h)
                                     or key_chunks_ok(layers, cfg.compute, d, h, k1 + k2, len(bags), sum(sizes)))
                     and (cfg.compute == "bf16" or SF.FP32_ATTENTION == "x3"))
-    if k2 > 0:
+    on_device = k2 > 0 and device_draws(cfg) and SF.ops.draw_packed_supported(min(max(sizes), 65536), k1, k2, len(layers))
+    if k2 > 0 and not on_device:
         ok = (uniform_dims and min(sizes) >= k1 + k2 and max(sizes) <= 65536 and (k1 + k2) * len(bags) <= (1 << 20)
               and sum(sizes) <= getattr(net, "_PACK_MAX_ROWS", PACK_MAX_ROWS))      # one group only: the draws must stay in bag order
         return [(list(range(len(bags))), False)] if ok else None
-    uni = [i for i, n in enumerate(sizes) if uniform_dims and k1 <= n <= 65536]
+    uni = [i for i, n in enumerate(sizes) if uniform_dims and k1 + k2 <= n <= 65536]
     rest = [i for i in range(len(bags)) if i not in set(uni)]
     rag = [i for i in rest if sizes[i] <= getattr(net, "_RAGGED_MAX_ROWS", RAGGED_MAX_ROWS)]
-    if rag and not SF.ops.ragged_attn_supported(min(k1, max(sizes[i] for i in rag)), d // h):
+    if rag and not SF.ops.ragged_attn_supported(min(k1 + k2, max(sizes[i] for i in rag)), d // h):
         rag = []
     groups = []
     for g, r in ((uni, False), (rag, True)):
         groups += [(c, r) for c in chunk_rows(net, g, sizes) if len(c) >= 2]
     return groups or None
+
+
+def device_draws(cfg):
+    """The packed path draws the random share with the device sampler (PACK_DEVICE_SAMPLER and configure(sampler="device"))."""
+    return PACK_DEVICE_SAMPLER and cfg.sampler == "device"
 
 
 def key_chunks_ok(layers, compute, d, h, k, bags, rows):
@@ -125,8 +143,11 @@ def forward_bags(net, bags):
     """``[net(x) for x in bags]`` with the bags' rows packed into ONE set of launches (bags of <= 8 k patches
     are launch-latency bound -- ~25 launches per bag whatever its size).  bags: sequence of [1, N_b, D] (or [N_b, D]) fp32 GPU
     tensors.  Returns the list of (classes [1, N_b, 1], prediction_bag [1, C], A [1, h, N_b, K_b] or None) tuples the per-bag
-    forwards return: same selections (bit-exact, random share included: the numpy draws are made bag by bag in the order the
-    per-bag forwards make them).  At kernel level (top-k, attention, head) a bag's result does not depend on what it is packed
+    forwards return: same selections (bit-exact, random share included: the reference sampler's numpy draws are made bag by bag
+    in the order the per-bag forwards make them; the device sampler (configure(sampler="device"), PACK_DEVICE_SAMPLER) draws all
+    bags and layers of a group in one launch, bag b from the Philox offset the b-th per-bag forward would use -- bit-exact
+    against the loop when one uniform group covers all bags in order (packable()), otherwise in the order pack_groups()
+    documents -- with no host read, numpy's stream untouched, and graph replay under graph_max_patches).  At kernel level (top-k, attention, head) a bag's result does not depend on what it is packed
     with, bit for bit; the projections pick their kernel by the PACKED row count, so a bag's logits move by fp32 / bf16 rounding
     with the batch composition (metrics computed from packed evaluation carry that rounding).  Against the per-bag forwards the
     top-k and head kernels are bit-identical, the attention sums its partial tiles in another order, and the projections
@@ -140,7 +161,8 @@ def forward_bags(net, bags):
         return [net(x) for x in bags]
     out = [None] * len(bags)
     lim = getattr(net, "_graph_max_patches", 0)
-    graph_ok = lim > 0 and all(l.random_patch_share == 0 for l in net.b_classifier.encoder.layers)
+    graph_ok = lim > 0 and (all(l.random_patch_share == 0 for l in net.b_classifier.encoder.layers)
+                            or device_draws(net.b_classifier.cfg))      # a selection that stays on the device
     for idx, ragged in groups:
         sizes = tuple(bags[i].shape[-2] for i in idx)
         rows = [bags[i].reshape(-1, bags[i].shape[-1]) for i in idx]
@@ -171,7 +193,9 @@ def packed_cache(net, sizes, device):
 
 def forward_bags_graph(net, rows, sizes, ragged=False):
     """forward_bags() as ONE captured HIP graph per batch composition (configure(graph_max_patches=...), deterministic
-    selection only): the bags are copied into the graph's static packed buffer and the ~30 launches replay without the host."""
+    selection or the device sampler's random share): the bags are copied into the graph's static packed buffer and the ~30
+    launches replay without the host.  The device sampler's record is advanced inside the graph, so every replay draws fresh
+    rows; a graph is bound to the record it was captured with (and keeps it alive)."""
     sig = net._weights_signature()
     if sig != getattr(net, "_graph_sig", None):
         net._graphs.clear()
@@ -180,6 +204,10 @@ def forward_bags_graph(net, rows, sizes, ragged=False):
     cfg = net.b_classifier.cfg
     dev = rows[0].device
     key = ("bags", sizes, bool(ragged), dev, cfg.precision, cfg.return_attention)
+    sampler = None
+    if device_draws(cfg) and any(l.random_patch_share > 0 for l in net.b_classifier.encoder.layers):
+        sampler = cfg.device_sampler(dev)
+        key += (sampler.state.data_ptr(),)
     ent = net._graphs.get(key)
     if ent is None:
         packed = packed_cache(net, sizes, dev)
@@ -206,6 +234,7 @@ def forward_bags_graph(net, rows, sizes, ragged=False):
                 net._graph_pool = torch.cuda.graph_pool_handle()
             graph = torch.cuda.CUDAGraph()
             graph._snf_selector = sel_state
+            graph._snf_sampler = sampler                   # the record's address is baked into the capture
             with torch.cuda.graph(graph, pool=net._graph_pool, stream=side, capture_error_mode="thread_local"):
                 out = forward_packed_raw(net, static_x, packed, ragged)
         except Exception as exc:
@@ -231,7 +260,8 @@ def forward_bags_graph(net, rows, sizes, ragged=False):
 def forward_packed(net, x_cat, packed, ragged=False):
     """forward_bags() on rows that are already packed: x_cat [T, D] fp32, packed = ops.PackedBags(sizes, device) (keep it
     between calls with the same bag sizes: it caches the launch plans).  ragged: the bags select different numbers of rows
-    (some are shorter than Lambda) or the head width is outside the MFMA kernels -- deterministic selection only."""
+    (some are shorter than Lambda) or the head width is outside the MFMA kernels -- deterministic selection, or a random share drawn
+    by the device sampler (device_draws())."""
     return split_packed(forward_packed_raw(net, x_cat, packed, ragged), packed)
 
 
@@ -271,14 +301,22 @@ def forward_packed_raw(net, x_cat, packed, ragged=False):
     top = SF.ops.topk_segmented(c1, packed, k1)                                   # [B, k1] inside each bag
     first = packed.dev[:-1].unsqueeze(1)
     rnd = rag = None
+    on_device = k2 > 0 and device_draws(cfg) and SF.ops.draw_packed_supported(packed.max_n, k1, k2, len(layers))
+    if on_device:
+        if not ragged and min(packed.sizes) < k1 + k2:
+            raise SF.SnuffyHipError("a uniform packed group needs at least Lambda = %d rows per bag (shortest: %d): pass ragged=True"
+                                    % (k1 + k2, min(packed.sizes)))
+        # every bag's and every layer's draw in one launch, bag b from the offset the b-th per-bag forward would use; no host read
+        rnd = cfg.device_sampler(top.device).draw_packed(packed, k1, k2, top, len(layers))      # [layers, B, k2]
     if ragged:
-        if k2 > 0:
-            raise SF.SnuffyHipError("ragged packed bags support the deterministic selection only (random_patch_share == 0)")
+        if k2 > 0 and not on_device:
+            raise SF.SnuffyHipError("ragged packed bags support the deterministic selection (random_patch_share == 0) or the device "
+                                    "sampler (configure(sampler='device')) only")
         # a bag shorter than Lambda selects all of its rows (snuffy.py:129): per-bag key counts, selected rows concatenated
-        rag = packed.ragged([min(k1, n) for n in packed.sizes])
-        pos, base = rag.flat_index(k1)
-        sel_ragged = top.reshape(-1)[pos] + base
-    elif k2 > 0:
+        rag = packed.ragged([min(k1 + k2, n) for n in packed.sizes])
+        pos, base = rag.flat_index(k1) if k2 == 0 else ragged_random_index(packed, rag, k1, k2)
+        sel_ragged = top.reshape(-1)[pos] + base if k2 == 0 else None
+    elif k2 > 0 and not on_device:
         # the reference's draws (snuffy.py:134-143), in the order the per-bag forwards consume the global numpy stream:
         # bag by bag, and inside a bag layer by layer (every layer draws from the complement of the same `top`)
         top_h = top.cpu().numpy()
@@ -297,7 +335,9 @@ def forward_packed_raw(net, x_cat, packed, ragged=False):
             x2 = SF.materialize(parts)
         layer.last_selection = None
         layer.last_selection_bags = (top, None if rnd is None else rnd[li])     # ragged: entries >= K_b of a row are padding
-        if ragged:
+        if ragged and k2 > 0:      # bag b: top[b, :min(k1, n_b)] ++ rnd[li, b, :k2_b], the valid entries of the padded [B, k1 + k2] rows
+            sel = torch.cat((top, rnd[li]), dim=1).reshape(-1)[pos] + base
+        elif ragged:
             sel = sel_ragged
         else:
             sel_local = top if rnd is None else torch.cat((top, rnd[li]), dim=1)  # [B, K]: top ++ random, as snuffy.py:145
@@ -307,3 +347,21 @@ def forward_packed_raw(net, x_cat, packed, ragged=False):
     logits = SF.head(parts, enc.norm, net.b_classifier.linear, packed=packed)   # [B, C]
     return s, logits, attn, (rag.kbs if rag is not None else None)
 
+
+
+def ragged_random_index(packed, rag, k1, k2):
+    """RaggedKeys.flat_index for rows laid out as top [B, k1] ++ random [B, k2]: the positions of bag b's min(k1, n_b) top rows and of its
+    min(k2, n_b - min(k1, n_b)) random rows in the flattened [B, k1 + k2] array, and the bag's first packed row per entry (device int64,
+    built from the bag sizes alone and cached on the PackedBags)."""
+    key = ("ragged_random", k1, k2)
+    hit = packed._plans.get(key)
+    if hit is None:
+        pos = []
+        for b, n in enumerate(packed.sizes):
+            t = min(k1, n)
+            r = min(k2, n - t)
+            pos.append(b * (k1 + k2) + np.arange(t, dtype=np.int64))
+            pos.append(b * (k1 + k2) + k1 + np.arange(r, dtype=np.int64))
+        base = np.repeat(packed.host[:-1], rag.kbs)
+        hit = packed._plans[key] = (torch.from_numpy(np.concatenate(pos)).to(packed.device), torch.from_numpy(base).to(packed.device))
+    return hit

@@ -308,8 +308,11 @@ class MILNet(nn.Module):
         sampler: "reference" (default: the random patch share is np.random.choice on the host, the reference's MT19937 draws bit
         for bit) or "device" (opt-in fast mode: Philox keys + top-k on the GPU, same distribution, no host sync; a captured graph
         draws fresh rows on every replay).  "device" applies to the one-bag-per-forward path and to the multiclass model's batch
-        (snuffy_multiclass: every row's draw in one launch pair, never graph-captured: its ref_dim read is a sync); forward_bags (packed.py) draws the
-        random share of a packed batch with the reference's host draws whatever this says, and is not graph-captured then."""
+        (snuffy_multiclass: every row's draw in one launch pair, never graph-captured: its ref_dim read is a sync) and to forward_bags
+        (packed.py, switch PACK_DEVICE_SAMPLER): every bag's and every layer's draw of a packed batch in ONE launch, bag b from the
+        Philox offset the b-th one-bag forward would use, no host read, graph-captured under graph_max_patches like the deterministic
+        selection, and bags shorter than Lambda packed as a ragged group.  With "reference" (or the switch off) forward_bags draws
+        with numpy bag by bag behind a device -> host copy and is not graph-captured."""
         self.b_classifier.configure(precision, return_attention)
         if sampler is not None:
             self.b_classifier.cfg.set_sampler(sampler)       # RuntimeConfig.set_sampler: "reference" (parity, default) | "device"

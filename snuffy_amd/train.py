@@ -64,6 +64,10 @@ def get_args_parser():
     p.add_argument('--betas', default=[0.5, 0.9])
     p.add_argument('--l2normed_embeddings', default=0, type=int)
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='eval-forward arithmetic (snuffy_amd)')
+    p.add_argument('--sampler', default='reference', choices=['reference', 'device'],
+                   help='snuffy_amd, binary model: who draws the random patch share -- reference = np.random.choice on the host (the '
+                        'reference\'s MT19937 draws bit for bit), device = Philox keys + top-k on the GPU (same distribution, no host '
+                        'sync; MILNet.forward_bags draws a whole packed batch in one launch and can replay it as a graph)')
     p.add_argument('--eval_bags_per_launch', default=1, type=int,
                    help='snuffy_amd: the evaluation loops pack up to this many SMALL bags (<= --eval_pack_max_patches patches each) '
                         'into one set of launches (MILNet.forward_bags: same selections, same draws of the random share; '
@@ -471,7 +475,8 @@ class Snuffy(SmallWeightTrainer):
             for name, p in milnet.named_parameters():
                 if p.dim() > 1 and name.split(".")[0] == module_name:
                     fn(p)
-        milnet.configure(precision=getattr(a, 'precision', 'fp32'), return_attention=False)   # A is discarded, train.py:830
+        milnet.configure(precision=getattr(a, 'precision', 'fp32'), return_attention=False,   # A is discarded, train.py:830
+                         sampler=getattr(a, 'sampler', 'reference'))
         return milnet
 
     def _run_model(self, bag_feats, bag_label, outputs=None):
