@@ -665,7 +665,7 @@ int snf_sparse_attn_x3_varlen_plan(const int64_t* offsets, int bags, int k, int 
 int snf_sparse_attn_fwd_x3_varlen(const float* q, int64_t ldq, const float* v, int64_t ldv, const float* kp, const int64_t* offsets,
                                   int bags, int k, int h, int dk, float scale, float* out, float* attn, float* lse,
                                   const int32_t* table_dev, void* workspace, size_t workspace_bytes, snf_stream_t stream);
-/* Varlen attention ABOVE ONE KEY CHUNK (k up to 8 x 224 at dk = 128, 8 x 256 at dk = 64; dk = 192 is not built).  The keys run as the
+/* Varlen attention ABOVE ONE KEY CHUNK (k up to 8 x 224 at dk = 128, 8 x 256 at dk = 64; dk = 192: the _dk192 pair below).  The keys run as the
  * chunks of the single-bag entry point of the same family (bf16: ceil(k / chunks) keys; fp32-class: that, rounded up to a multiple
  * of 4; the last chunk is shorter): one statistics launch per chunk over all bags, then the chunks' main launches, each normalising
  * with the statistics of all chunks -- a bag's attn and lse are those of snf_sparse_attn_fwd_mfma / _x3 on that bag alone, bit for bit,
@@ -688,6 +688,23 @@ int snf_sparse_attn_x3_varlen_chunked_plan(const int64_t* offsets, int bags, int
                                            size_t* table_ints_needed, size_t* workspace_bytes, int* n_chunks, int* chunk_k);
 int snf_sparse_attn_fwd_x3_varlen_chunked(const float* q, int64_t ldq, const float* v, int64_t ldv, const float* kp,
                                           const int64_t* offsets, int bags, int k, int h, int dk, float scale, float* out, float* attn,
+                                          float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
+                                          snf_stream_t stream);
+/* Varlen bf16 attention at HEAD WIDTH 192 (the reference README's MAE recipe: D = 768, h = 4, Lambda = 500).  The plan functions above
+ * keep answering SNF_EUNSUPPORTED at dk = 192; the width has entry points of its own, with the protocol of the chunked pair.  One launch
+ * holds 128 keys (Kp 48 + P 40 + V 48 KiB of LDS at 4 key blocks); more keys run as the chunks of snf_sparse_attn_fwd_mfma at dk = 192
+ * (ceil(k / chunks) keys, the last chunk shorter): one statistics launch per chunk over all bags, then the chunks' main launches.  A
+ * bag's attn and lse are those of snf_sparse_attn_fwd_mfma on that bag alone, bit for bit, out within the fp32 order of the partial
+ * sums, and nothing depends on what a bag is packed with.  bf16 q | v only; inference only (no dropout).
+ *   snf_sparse_attn_varlen_dk192_plan      1 <= k <= 8 x 128.  table = NULL sizes the table; n_chunks / chunk_k nullable.  Workspace =
+ *                      partial tiles at the largest chunk's key-block count | statistics [chunks][h][T] (max, sum) pairs over all T
+ *                      packed rows, 8 bytes each (none with one chunk) | Kp staging (used when kp is f32).  SNF_EUNSUPPORTED: k above
+ *                      8 chunks, an empty bag, a chunk whose key-block count is not built (one chunk: 1, 2, 4; chunked: 2, 4).
+ *   snf_sparse_attn_fwd_mfma_varlen_dk192  arguments and layouts of snf_sparse_attn_fwd_mfma_varlen_chunked without dk. */
+int snf_sparse_attn_varlen_dk192_plan(const int64_t* offsets, int bags, int k, int h, int32_t* table, size_t table_ints,
+                                      size_t* table_ints_needed, size_t* workspace_bytes, int* n_chunks, int* chunk_k);
+int snf_sparse_attn_fwd_mfma_varlen_dk192(const void* q, int64_t ldq, const void* v, int64_t ldv, const void* kp, int kp_dtype,
+                                          const int64_t* offsets, int bags, int k, int h, float scale, float* out, float* attn,
                                           float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
                                           snf_stream_t stream);
 /* Ragged form for SMALL bags (exact fp32, any head width, every bag with its own key count: a bag shorter than Lambda selects

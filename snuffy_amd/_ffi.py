@@ -184,6 +184,11 @@ SIGNATURES = {
     "snf_sparse_attn_fwd_mfma_varlen_chunked": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
                                                         c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                         c_size_t, c_void_p]),
+    "snf_sparse_attn_varlen_dk192_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
+    "snf_sparse_attn_fwd_mfma_varlen_dk192": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
+                                                      c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                      c_void_p]),
     "snf_sparse_attn_x3_varlen_chunked_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                                        c_void_p, c_void_p]),
     "snf_sparse_attn_fwd_x3_varlen_chunked": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int,

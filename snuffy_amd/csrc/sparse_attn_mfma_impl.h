@@ -2,7 +2,8 @@
 // K7 (fast form): Snuffy's sparse attention on the CDNA4 matrix cores.
 // (implementation header: compiled once per head width by sparse_attn_mfma.hip (dk = 128 + the C entry points),
 // sparse_attn_mfma_dk64.hip and sparse_attn_mfma_dk192.hip, so the kernel variants of the three widths build in parallel; the varlen
-// variants live in sparse_attn_mfma_varlen*.hip, their key-chunked forms in sparse_attn_mfma_varlen_chunks*.hip)
+// variants live in sparse_attn_mfma_varlen*.hip, their key-chunked forms in sparse_attn_mfma_varlen_chunks*.hip, every varlen form of
+// dk = 192 with its entry points in sparse_attn_mfma_varlen_dk192.hip)
 //
 //   per head a:   P_a = softmax_j(Q_a Kp_a^T * scale)  [n, k]      O_a = P_a^T V_a  [k, dk]        (snuffy.py:160-168)
 //
@@ -78,6 +79,17 @@ struct AttnParams {
 using Plan = TilePlan;   // make_plan below; the varlen table (VL_DESC, make_varlen_table) is described in attn_plan.h
 }  // namespace snf_attn
 
+// Names of the two kernel templates below.  A translation unit may set them before it includes this header to get the same kernels
+// under symbols of its own (sparse_attn_mfma_varlen_dk192.hip does: the varlen forms of dk = 192 are sparse_attn_mfma_vl192_kernel /
+// sparse_attn_stats_vl192_kernel, so the single-bag kernels of that width keep their names to themselves); the text is the same, and
+// with the default names nothing about the existing kernels changes.
+#ifndef SNF_ATTN_MFMA_KERNEL
+#define SNF_ATTN_MFMA_KERNEL sparse_attn_mfma_kernel
+#endif
+#ifndef SNF_ATTN_STATS_KERNEL
+#define SNF_ATTN_STATS_KERNEL sparse_attn_stats_kernel
+#endif
+
 namespace {
 using snf_attn::AttnParams;
 using snf_attn::Plan;
@@ -145,7 +157,7 @@ __device__ __forceinline__ void pin_vgpr(f32x16& x) { asm volatile("" : "+v"(x))
 // never stored), i.e. ~11 % of the softmax wave's VALU work, decided at compile time (the run-time form of the same skip
 // measured slower in round 1: its wave-uniform branches cost more than they saved).
 template <int DK, int NKB, typename QT, bool AUX, bool EXT, int TAILP = 8, bool VL = false>
-__global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
+__global__ __launch_bounds__(512) void SNF_ATTN_MFMA_KERNEL(AttnParams PA) {
     constexpr int NKS = DK / 16;             // k-steps of GEMM1
     AttnParams P = PA;
     int bid = blockIdx.x;
@@ -636,15 +648,19 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
             if constexpr (VL) {
                 if (P.out_direct) {   // this workgroup owns the whole head: registers 4 q4 + i of tile (kb, cb) = O[32 kb + i + 8 q4 + 4 hf, 32 cb + j]
                     const int64_t ld = (int64_t)P.h * DK;
+                    // DK = 192: opaque copy of the lane's key offset -- the row offsets key * ld are loop-invariant, and hoisted out of the
+                    // tile loop they are 16 64-bit values per tile held (spilled) across the whole loop for a once-per-head store
+                    int hfo = hf;
+                    if constexpr (D192) asm volatile("" : "+v"(hfo));
 #pragma unroll
                     for (int ti = 0; ti < NT; ++ti) {
-                        const int t_idx = w + 4 * ti;   // (varlen launches are built for DK = 64 / 128 only)
-                        if (t_idx < NKB * NCB) {
+                        const int t_idx = tile_of(ti);   // DK = 192: (w % NKB, w / NKB + (4 / NKB) ti), not w + 4 ti
+                        if (tile_ok(ti)) {
                             const int kb_ = t_idx / NCB, cb_ = t_idx - kb_ * NCB;
                             float* dcol = P.out_direct + head * DK + 32 * cb_ + j;
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
-                                const int key = 32 * kb_ + (r & 3) + 8 * (r >> 2) + 4 * hf;
+                                const int key = 32 * kb_ + (r & 3) + 8 * (r >> 2) + 4 * hfo;
                                 if (key < P.k) dcol[(int64_t)key * ld] = acc_o[ti][r];
                             }
                         }
@@ -743,7 +759,7 @@ __global__ __launch_bounds__(512) void sparse_attn_mfma_kernel(AttnParams PA) {
 // VL: varlen launch -- the descriptor preamble of the main kernel (the same table: a bag's tile geometry depends on n and h only),
 // stats_out[(a * n_stride + row0 + row) * 2 + {0, 1}] over the packed rows.
 template <int DK, int NKB, typename QT, bool VL = false>
-__global__ __launch_bounds__(256, 1) void sparse_attn_stats_kernel(AttnParams PA) {
+__global__ __launch_bounds__(256, 1) void SNF_ATTN_STATS_KERNEL(AttnParams PA) {
     constexpr int NKS = DK / 16;
     AttnParams P = PA;
     int bid = blockIdx.x;
@@ -908,9 +924,10 @@ __global__ __launch_bounds__(64) void reduce_partials_kernel(const float* __rest
 
 
 
-inline bool make_plan(int64_t n, int k, int h, int dk, Plan* pl, bool packed = false) {
+// packed = the plan of a bag inside a varlen launch.  make_plan answers for the varlen entry points of dk = 64 / 128; the varlen forms at
+// dk = 192 have entry points and a planner of their own (sparse_attn_mfma_varlen_dk192.hip), which call make_plan_any.
+inline bool make_plan_any(int64_t n, int k, int h, int dk, Plan* pl, bool packed) {
     if (k < 1 || k > attn_kmax(dk)) return false;   // LDS: Kp + P + V images
-    if (packed && dk == 192) return false;          // the varlen kernels are built for dk = 64 / 128 only
     int nkb = (k + 31) / 32;
     // instantiated key-block counts
     const int opts[] = {1, 2, 4, 6, 7, 8};
@@ -925,12 +942,16 @@ inline bool make_plan(int64_t n, int k, int h, int dk, Plan* pl, bool packed = f
     pl->nkb = sel;
     return snf_attn::make_tile_plan(n, h, TILE_ROWS, /*small_bag_tiles=*/8, packed, pl);
 }
+inline bool make_plan(int64_t n, int k, int h, int dk, Plan* pl, bool packed = false) {
+    if (packed && dk == 192) return false;
+    return make_plan_any(n, k, h, dk, pl, packed);
+}
 
 template <int DK, int NKB, typename QT, bool AUX, bool EXT = false, int TAILP = 8, bool VL = false>
 int launch_variant(const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
     constexpr int NKS = DK / 16;
     const size_t lds = (size_t)(NKB * NKS) * 1024 + (size_t)TILE_ROWS * (p_row_bytes(NKB) + 2 * DK);
-    auto kern = sparse_attn_mfma_kernel<DK, NKB, QT, AUX, EXT, TAILP, VL>;
+    auto kern = SNF_ATTN_MFMA_KERNEL<DK, NKB, QT, AUX, EXT, TAILP, VL>;
     static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
     if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "sparse_attn_mfma")) return rc;
     hipLaunchKernelGGL(kern, dim3(pl.num_wg), dim3(512), lds, s, P);
@@ -1056,7 +1077,7 @@ inline size_t mfma_workspace_bytes(const Plan& pl, int dk) {
 template <int DK, int NKB, typename QT, bool VL = false>
 int launch_stats_variant(const AttnParams& P, const Plan& pl, hipStream_t s) {
     constexpr int NKS = DK / 16;
-    hipLaunchKernelGGL((sparse_attn_stats_kernel<DK, NKB, QT, VL>), dim3(pl.num_wg), dim3(256), (size_t)(NKB * NKS) * 1024, s, P);
+    hipLaunchKernelGGL((SNF_ATTN_STATS_KERNEL<DK, NKB, QT, VL>), dim3(pl.num_wg), dim3(256), (size_t)(NKB * NKS) * 1024, s, P);
     return snf::check_launch("sparse_attn_stats_kernel");
 }
 template <int DK, typename QT>

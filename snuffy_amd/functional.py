@@ -633,7 +633,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
         if packed is None or ragged.total != k or not ops.ragged_attn_supported(ragged.kmax, d // h):
             raise SnuffyHipError("ragged packed bags: %d keys (max %d per bag) at head width %d is outside the ragged attention "
                                  "kernel" % (k, ragged.kmax, d // h))
-    elif packed is not None and (kb < 1 or not ops.varlen_attn_chunks_supported(precision, kb, packed_head_pad(d // h) or d // h)):
+    elif packed is not None and (kb < 1 or not (ops.varlen_attn_chunks_supported(precision, kb, packed_head_pad(d // h) or d // h)
+                                               or (precision == "bf16" and d == 192 * h and ops.varlen_attn_dk192_supported(kb)))):
         raise SnuffyHipError("packed bags: %d keys per bag at head width %d is outside the varlen attention kernels" % (kb, d // h))
     n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
     lq, lk, lv, lo = mha.linears
@@ -808,7 +809,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
         ops.layernorm_rows(x2, None, None, n0.eps, out=xhat)
     qv = ops.linear_bf16(xhat, fw["wqv"], fw["bqv_f"], fw["bqv"])                   # [N, 2D] bf16 = [Q | V], bias epilogue
     q, v = qv[:, :dp], qv[:, dp:]                                                   # row-strided views, used in place
-    # dk = 192 (the README's MAE recipe, D = 768 with h = 4; no padded form) has kernel variants of its own, single bags only
+    # dk = 192 (the README's MAE recipe, D = 768 with h = 4; no padded form) has kernel variants of its own; packed bags run their varlen
+    # forms (ops.varlen_attn_dk192_supported, admitted above), whatever MFMA_ATTN_DK192 says about the single bag
     dk192 = (MFMA_ATTN_DK192 and dkp == 192 and ragged is None and packed is None
              and ops.mfma_attn_dk192_supported(k, n, qv.stride(0)))
     if ragged is None and (packed is not None or dk192 or ops.mfma_attn_supported(k, dkp, n, qv.stride(0))):

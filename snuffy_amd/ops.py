@@ -1042,7 +1042,7 @@ class PackedBags:
 
     def plan(self, kind, *shape):
         """(device table int32, workspace bytes) of a segmented launch: kind in {"mfma", "x3", "head"}; the key-chunked attention
-        plans "mfma_chunks" / "x3_chunks" add (chunk count, keys per chunk)."""
+        plans "mfma_chunks" / "x3_chunks" and the head-width-192 plan "mfma_dk192" (shape = (k, h)) add (chunk count, keys per chunk)."""
         import numpy as np
         key = (kind,) + tuple(shape)
         hit = self._plans.get(key)
@@ -1052,8 +1052,8 @@ class PackedBags:
         need, wsb = ctypes.c_size_t(0), ctypes.c_size_t(0)
         fn = {"mfma": lib.snf_sparse_attn_varlen_plan, "x3": lib.snf_sparse_attn_x3_varlen_plan,
               "mfma_chunks": lib.snf_sparse_attn_varlen_chunked_plan, "x3_chunks": lib.snf_sparse_attn_x3_varlen_chunked_plan,
-              "head": lib.snf_ln_mean_head_varlen_plan}[kind]
-        chunks = (ctypes.c_int(0), ctypes.c_int(0)) if kind.endswith("_chunks") else ()
+              "mfma_dk192": lib.snf_sparse_attn_varlen_dk192_plan, "head": lib.snf_ln_mean_head_varlen_plan}[kind]
+        chunks = (ctypes.c_int(0), ctypes.c_int(0)) if kind.endswith("_chunks") or kind == "mfma_dk192" else ()
         extra = tuple(ctypes.byref(c) for c in chunks)
         check(fn(self._host_ptr(), self.bags, *shape, None, 0, ctypes.byref(need), ctypes.byref(wsb), *extra), "varlen plan (%s)" % kind)
         table = np.zeros(need.value, dtype=np.int32)
@@ -1137,6 +1137,12 @@ def varlen_attn_chunks_supported(precision_kind, k, dk):
     return (dk == 128 and 1 <= k <= 8 * 224) or (dk == 64 and 1 <= k <= 8 * 256)
 
 
+def varlen_attn_dk192_supported(k):
+    """The bf16 varlen attention at head width 192 (snf_sparse_attn_fwd_mfma_varlen_dk192; the README's MAE recipe D = 768, h = 4): one
+    launch holds 128 keys, up to 8 key chunks.  The older varlen predicates keep answering for dk = 64 / 128 only."""
+    return 1 <= k <= 8 * 128
+
+
 def topk_segmented(scores, packed, k):
     """Top-k of every bag of a packed score vector in one launch: [B, k] int64 indices INSIDE each bag (descending score, ties
     by ascending index -- the same one-workgroup kernel body as topk(), one workgroup per bag).  A bag with fewer than k rows fills
@@ -1156,7 +1162,8 @@ def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fa
     (bag b's keys in rows b k ..) -> (out [B * k, d] f32, attn [h, T, k] or None, lse [h, T] or None).  A bag's result
     does not depend on what it is packed with (bit for bit); against sparse_attn_fwd_mfma() bag by bag P / lse are identical and
     O differs by the fp32 order of the partial sums only (small bags get more rows per workgroup here).  k above one key chunk
-    (varlen_attn_chunks_supported) runs as the key chunks of sparse_attn_fwd_mfma(), with the same guarantees."""
+    (varlen_attn_chunks_supported) runs as the key chunks of sparse_attn_fwd_mfma(), with the same guarantees.  Head width 192
+    (varlen_attn_dk192_supported) has an entry point of its own, snf_sparse_attn_fwd_mfma_varlen_dk192: 128 keys per chunk."""
     if q.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
         raise TypeError("sparse_attn_fwd_mfma_varlen: q and v must be bfloat16")
     q = _rows16(q, "q")
@@ -1171,13 +1178,18 @@ def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fa
     dk = d // h
     scale = 1.0 / math.sqrt(dk) if scale is None else scale
     chunked = not varlen_attn_supported("bf16", k, dk)
-    table, wsb = packed.plan("mfma_chunks" if chunked else "mfma", k, h, dk)[:2]
+    table, wsb = (packed.plan("mfma_dk192", k, h) if dk == 192 else packed.plan("mfma_chunks" if chunked else "mfma", k, h, dk))[:2]
     ws = _ws(wsb, q.device)
     out = torch.empty(packed.bags * k, d, dtype=torch.float32, device=q.device)
     attn = torch.empty(h, t, k, dtype=torch.float32, device=q.device) if need_attn else None
     lse = torch.empty(h, t, dtype=torch.float32, device=q.device) if need_lse else None
     kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
     lib = _ffi.load()
+    if dk == 192:
+        check(lib.snf_sparse_attn_fwd_mfma_varlen_dk192(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(),
+                                                        packed.bags, k, h, float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws),
+                                                        wsb, _stream()), "snf_sparse_attn_fwd_mfma_varlen_dk192")
+        return out, attn, lse
     fn = lib.snf_sparse_attn_fwd_mfma_varlen_chunked if chunked else lib.snf_sparse_attn_fwd_mfma_varlen
     check(fn(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(), packed.bags, k, h, dk, float(scale), _p(out),
              _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()),

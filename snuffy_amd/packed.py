@@ -23,6 +23,13 @@ PACK_KEY_CHUNKS = True
 # shipped value: on only where the device route is at least level with the host draws at every composition of
 # profiles/packed_device_sampler.txt (tools/packed_sampler_time.py).
 PACK_DEVICE_SAMPLER = True
+# Uniform groups of the bf16 model at head width 192 (the README's MAE recipe: D = 768, h = 4, Lambda = 500 as 250 + 250) on the varlen
+# forms of the dk = 192 kernels (ops.varlen_attn_dk192_supported: up to 8 chunks of 128 keys).  False: such bags take the per-bag loop
+# (or the ragged kernel where it takes them), the routing of before, call for call.  The rule of PACK_KEY_CHUNKS decides the shipped
+# value: on only where the packed route is at least level with the loop at every row of profiles/varlen_dk192.txt
+# (tools/varlen_dk192_time.py).  On: 64 x 1000 patches 7.2 - 9.7x, 64 x 8000 2.07 - 2.57x, the synthetic CAMELYON16-shaped mix
+# 1.84 - 2.26x, host draws and device sampler, return_attention off and on -- no row behind the loop, so no length gate in dk192_ok.
+PACK_DK192 = True
 RAGGED_MAX_ROWS = 4096      # longest bag the ragged (exact fp32, one workgroup per bag and head) attention is meant for
 
 
@@ -32,7 +39,8 @@ def pack_groups(net, bags):
     The packed path covers inference of the binary model with a plain one-logit FCLayer critic.  "uniform" groups (ragged =
     False): every bag has at least Lambda patches, so all select the same K rows, and the head width is one the MFMA kernels
     take -- varlen forms of the bf16 / fp32-class attention kernels (with PACK_KEY_CHUNKS also Lambda above one key chunk and head widths
-    between the kernels', zero-padded).  "ragged" groups: bags shorter than Lambda (they select
+    between the kernels', zero-padded; with PACK_DK192 also the bf16 model at head width 192, up to 8 chunks of 128 keys -- fp32 at that
+    width stays per bag).  "ragged" groups: bags shorter than Lambda (they select
     ALL their rows, snuffy.py:129) or head widths outside the MFMA kernels (the MIL benchmark sets: D = 166 / 230, h = 2) --
     exact-fp32 ragged attention, bags of at most _RAGGED_MAX_ROWS patches.  With a random share the draws of the reference
     sampler must stay in bag order, so only one uniform group over all bags is formed.  With the device sampler
@@ -70,7 +78,8 @@ def pack_groups(net, bags):
         return None
     sizes = [x.shape[-2] for x in bags]
     uniform_dims = (d % 4 == 0 and (SF.ops.varlen_attn_supported(cfg.compute, k1 + k2, d // h)
-                                    or key_chunks_ok(layers, cfg.compute, d, h, k1 + k2, len(bags), sum(sizes)))
+                                    or key_chunks_ok(layers, cfg.compute, d, h, k1 + k2, len(bags), sum(sizes))
+                                    or dk192_ok(cfg.compute, d, h, k1 + k2))
                     and (cfg.compute == "bf16" or SF.FP32_ATTENTION == "x3"))
     on_device = k2 > 0 and device_draws(cfg) and SF.ops.draw_packed_supported(min(max(sizes), 65536), k1, k2, len(layers))
     if k2 > 0 and not on_device:
@@ -91,6 +100,12 @@ def pack_groups(net, bags):
 def device_draws(cfg):
     """The packed path draws the random share with the device sampler (PACK_DEVICE_SAMPLER and configure(sampler="device"))."""
     return PACK_DEVICE_SAMPLER and cfg.sampler == "device"
+
+
+def dk192_ok(compute, d, h, k):
+    """PACK_DK192: the bf16 model at head width 192 with a key count inside the dk = 192 varlen kernels.  precision="fp32" stays per
+    bag whatever the switch: its route at this width is the unfused score / pooling pair, which has no varlen form."""
+    return bool(PACK_DK192 and compute == "bf16" and h >= 1 and d == 192 * h and SF.ops.varlen_attn_dk192_supported(k))
 
 
 def key_chunks_ok(layers, compute, d, h, k, bags, rows):
@@ -153,7 +168,8 @@ def forward_bags(net, bags):
     top-k and head kernels are bit-identical, the attention sums its partial tiles in another order, and the projections
     run over the packed rows (a library / tile choice that depends on the row count): logits move by fp32 / bf16 rounding.
     Bags that select different numbers of rows (shorter than Lambda) or whose head width the MFMA kernels do not take are
-    packed as a second, "ragged" group (pack_groups); whatever cannot be packed (training, multiclass critic, ...) takes
+    packed as a second, "ragged" group (pack_groups); head width 192 (D = 768, h = 4) packs in bf16 behind PACK_DK192 and
+    stays per bag in fp32; whatever cannot be packed (training, multiclass critic, ...) takes
     the per-bag loop."""
     bags = list(bags)
     groups = pack_groups(net, bags)

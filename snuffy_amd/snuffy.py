@@ -448,7 +448,8 @@ class MILNet(nn.Module):
         ~25 launches per bag, not by the GPU).  Same selections as the per-bag forwards bit for bit (random share included), logits
         within fp32 / bf16 rounding of the per-bag forward (and of another batch composition: the projections choose their kernel by
         the packed row count; top-k, attention and head kernels are composition-independent bit for bit); whatever cannot be
-        packed takes the per-bag loop.  See packed.forward_bags."""
+        packed takes the per-bag loop -- head width 192 (D = 768, h = 4) packs in bf16 behind packed.PACK_DK192 and stays per bag in
+        fp32.  See packed.forward_bags."""
         from . import packed
         return packed.forward_bags(self, bags)
 
