@@ -707,6 +707,30 @@ int snf_sparse_attn_fwd_mfma_varlen_dk192(const void* q, int64_t ldq, const void
                                           const int64_t* offsets, int bags, int k, int h, float scale, float* out, float* attn,
                                           float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
                                           snf_stream_t stream);
+/* fp32-class (split-bf16 x 3) attention at HEAD WIDTH 192, FUSED: softmax and P^T V in one kernel, no materialised [h, n, k]
+ * probabilities in between (snf_sparse_attn_fwd_x3u_f32 is the unfused pair).  snf_sparse_attn_fwd_x3 and the x3 plan functions above
+ * keep answering SNF_EUNSUPPORTED at dk = 192; the width has entry points of its own.  One launch holds 128 keys (1, 2 or 4 key blocks;
+ * Q 48 + P 40 + V 48 + statistics 4 KiB of LDS at 4 blocks, the Kp fragments in registers); more keys run as up to 8 chunks of
+ * ceil(k / chunks) keys rounded up to a multiple of 4 (the last chunk shorter; chunked launches run at 2 or 4 key blocks): one
+ * statistics launch per chunk, then the chunks' main launches, each normalising with the statistics of all chunks.  Inference only.
+ *   ..._x3_dk192_workspace_bytes  0 = unsupported (k outside 1 .. 8 x 128, n < 1, h < 1).
+ *   snf_sparse_attn_fwd_x3_dk192  arguments, layouts, alignment rules and error codes of snf_sparse_attn_fwd_x3 without dk.
+ *   snf_sparse_attn_x3_varlen_dk192_plan  as snf_sparse_attn_x3_varlen_chunked_plan without dk: one table for all chunks, descriptor
+ *                      word 3 = b k with the full key count, workspace = partial tiles at the largest chunk's key-block count |
+ *                      statistics [chunks][h][T] (none with one chunk).  SNF_EUNSUPPORTED: k outside 1 .. 8 x 128, an empty bag.
+ *   snf_sparse_attn_fwd_x3_varlen_dk192   arguments and layouts of snf_sparse_attn_fwd_x3_varlen_chunked without dk.  A bag's attn and
+ *                      lse are those of snf_sparse_attn_fwd_x3_dk192 on that bag alone, bit for bit, out within the fp32 order of the
+ *                      partial sums, and nothing depends on what a bag is packed with. */
+size_t snf_sparse_attn_fwd_x3_dk192_workspace_bytes(int64_t n, int k, int h);
+int snf_sparse_attn_fwd_x3_dk192(const float* q, int64_t ldq, const float* v, int64_t ldv, const float* kp, int64_t n, int k, int h,
+                                 float scale, float* out, float* attn, float* lse, void* workspace, size_t workspace_bytes,
+                                 snf_stream_t stream);
+int snf_sparse_attn_x3_varlen_dk192_plan(const int64_t* offsets, int bags, int k, int h, int32_t* table, size_t table_ints,
+                                         size_t* table_ints_needed, size_t* workspace_bytes, int* n_chunks, int* chunk_k);
+int snf_sparse_attn_fwd_x3_varlen_dk192(const float* q, int64_t ldq, const float* v, int64_t ldv, const float* kp,
+                                        const int64_t* offsets, int bags, int k, int h, float scale, float* out, float* attn,
+                                        float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
+                                        snf_stream_t stream);
 /* Ragged form for SMALL bags (exact fp32, any head width, every bag with its own key count: a bag shorter than Lambda selects
  * all of its rows -- snuffy.py:129 `min(ceil(...), n)` -- as the MIL benchmark sets do).  desc_dev [bags][4] int32 in DEVICE
  * memory = (first packed row, rows, first key row, keys) per bag; kp / out [sum of keys, h * dk]; attn [h, T, kmax] nullable

@@ -47,6 +47,11 @@ FP32_SHARED_NORM = True
 # (ops.mfma_attn_dk192_supported); False: such layers make fp32 copies of Q and V for the exact-fp32 kernel, as before.  Ships off: the
 # route has not been timed against the one of before yet (tools/attn_dk192_time.py writes profiles/attn_dk192.txt; on once it wins there)
 MFMA_ATTN_DK192 = False
+# fp32 inference of a single bag at head width 192 on the FUSED fp32-class kernel of that width (ops.x3_attn_dk192_supported: up to 8
+# chunks of 128 keys, no materialised [h, n, k] probabilities); False: the unfused score / pooling pair (ops.sparse_attn_fwd_x3u), as
+# before.  Ships off: on only if no row of profiles/x3_dk192.txt (tools/x3_dk192_time.py) is behind the pair.  The packed route
+# (packed.PACK_X3_DK192) does not consult this switch.
+X3_ATTN_DK192 = False
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -634,7 +639,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             raise SnuffyHipError("ragged packed bags: %d keys (max %d per bag) at head width %d is outside the ragged attention "
                                  "kernel" % (k, ragged.kmax, d // h))
     elif packed is not None and (kb < 1 or not (ops.varlen_attn_chunks_supported(precision, kb, packed_head_pad(d // h) or d // h)
-                                               or (precision == "bf16" and d == 192 * h and ops.varlen_attn_dk192_supported(kb)))):
+                                               or (precision == "bf16" and d == 192 * h and ops.varlen_attn_dk192_supported(kb))
+                                               or (precision == "fp32" and d == 192 * h and ops.varlen_attn_x3_dk192_supported(kb)))):
         raise SnuffyHipError("packed bags: %d keys per bag at head width %d is outside the varlen attention kernels" % (kb, d // h))
     n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
     lq, lk, lv, lo = mha.linears
@@ -716,6 +722,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             o, attn, _ = ops.sparse_attn_fwd_x3_varlen(q, v, kp, packed, kb, h, scale=scale, need_attn=need_attn)
         elif FP32_ATTENTION == "x3" and ops.x3_attn_supported(k, d // h):
             o, attn, _ = ops.sparse_attn_fwd_x3(q, v, kp, h, need_attn=need_attn)    # snuffy.py:160-168
+        elif FP32_ATTENTION == "x3" and X3_ATTN_DK192 and d == 192 * h and ops.x3_attn_dk192_supported(k):
+            o, attn, _ = ops.sparse_attn_fwd_x3_dk192(q, v, kp, h, need_attn=need_attn)   # q, v: halves of the fused projection, in place
         elif FP32_ATTENTION == "x3" and ops.x3u_attn_supported(k, d // h):
             # head widths no pipelined kernel takes (dk = 192: the README recipe D = 768 / h = 4): the unfused fp32-class pair
             o, attn, _ = ops.sparse_attn_fwd_x3u(q, kp, v, h, need_attn=need_attn)      # q, v: halves of the fused projection, in place

@@ -888,6 +888,41 @@ def sparse_attn_fwd_x3(q, v, kp, h, scale=None, need_attn=False, need_lse=False,
     return out, attn, lse
 
 
+def x3_attn_dk192_supported(k):
+    """Shapes of the fused fp32-class attention kernel at head width 192 (snf_sparse_attn_fwd_x3_dk192; the README's MAE recipe D = 768,
+    h = 4): 128 keys per launch, up to 8 key chunks with exact cross-chunk softmax statistics.  x3_attn_supported() keeps answering for
+    dk = 64 / 128 only."""
+    return 1 <= k <= 8 * 128
+
+
+def sparse_attn_fwd_x3_dk192(q, v, kp, h, scale=None, need_attn=False, need_lse=False):
+    """fp32-class sparse attention on the matrix cores at head width 192, fused (snf_sparse_attn_fwd_x3_dk192: no materialised
+    [h, n, k] probabilities between the softmax and P^T V): q, v [n, 192 h] f32 (row-strided views allowed: the halves of a fused
+    [Q | V] projection), kp [k, 192 h] f32 -> (out [k, d], attn [h, n, k] or None, lse [h, n] or None)."""
+    if q.dtype != torch.float32 or v.dtype != torch.float32:
+        raise TypeError("sparse_attn_fwd_x3_dk192: q and v must be float32")
+    q = _rows16(q, "q")
+    v = _rows16(v, "v")
+    kp = _req(kp, torch.float32, "kp", 2)
+    n, d = q.shape
+    k = kp.shape[0]
+    if d != 192 * h or kp.shape[1] != d or v.shape != q.shape:
+        raise ValueError("sparse_attn_fwd_x3_dk192: inconsistent shapes q %s v %s kp %s h %d (d_model must be 192 h)"
+                         % (tuple(q.shape), tuple(v.shape), tuple(kp.shape), h))
+    scale = 1.0 / math.sqrt(192) if scale is None else scale
+    lib = _ffi.load()
+    wsb = lib.snf_sparse_attn_fwd_x3_dk192_workspace_bytes(n, k, h)
+    if wsb == 0:
+        raise ValueError("sparse_attn_fwd_x3_dk192: unsupported shape n=%d k=%d h=%d (1 <= k <= 1024)" % (n, k, h))
+    out = torch.empty(k, d, dtype=torch.float32, device=q.device)
+    attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
+    lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
+    ws = _ws(wsb, q.device)
+    check(lib.snf_sparse_attn_fwd_x3_dk192(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), n, k, h, float(scale), _p(out), _p(attn),
+                                           _p(lse), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_x3_dk192")
+    return out, attn, lse
+
+
 _X3_HL_OK = {}
 
 
@@ -1042,7 +1077,8 @@ class PackedBags:
 
     def plan(self, kind, *shape):
         """(device table int32, workspace bytes) of a segmented launch: kind in {"mfma", "x3", "head"}; the key-chunked attention
-        plans "mfma_chunks" / "x3_chunks" and the head-width-192 plan "mfma_dk192" (shape = (k, h)) add (chunk count, keys per chunk)."""
+        plans "mfma_chunks" / "x3_chunks" and the head-width-192 plans "mfma_dk192" / "x3_dk192" (shape = (k, h)) add (chunk count, keys
+        per chunk)."""
         import numpy as np
         key = (kind,) + tuple(shape)
         hit = self._plans.get(key)
@@ -1052,8 +1088,9 @@ class PackedBags:
         need, wsb = ctypes.c_size_t(0), ctypes.c_size_t(0)
         fn = {"mfma": lib.snf_sparse_attn_varlen_plan, "x3": lib.snf_sparse_attn_x3_varlen_plan,
               "mfma_chunks": lib.snf_sparse_attn_varlen_chunked_plan, "x3_chunks": lib.snf_sparse_attn_x3_varlen_chunked_plan,
-              "mfma_dk192": lib.snf_sparse_attn_varlen_dk192_plan, "head": lib.snf_ln_mean_head_varlen_plan}[kind]
-        chunks = (ctypes.c_int(0), ctypes.c_int(0)) if kind.endswith("_chunks") or kind == "mfma_dk192" else ()
+              "mfma_dk192": lib.snf_sparse_attn_varlen_dk192_plan, "x3_dk192": lib.snf_sparse_attn_x3_varlen_dk192_plan,
+              "head": lib.snf_ln_mean_head_varlen_plan}[kind]
+        chunks = (ctypes.c_int(0), ctypes.c_int(0)) if kind.endswith("_chunks") or kind.endswith("_dk192") else ()
         extra = tuple(ctypes.byref(c) for c in chunks)
         check(fn(self._host_ptr(), self.bags, *shape, None, 0, ctypes.byref(need), ctypes.byref(wsb), *extra), "varlen plan (%s)" % kind)
         table = np.zeros(need.value, dtype=np.int32)
@@ -1143,6 +1180,12 @@ def varlen_attn_dk192_supported(k):
     return 1 <= k <= 8 * 128
 
 
+def varlen_attn_x3_dk192_supported(k):
+    """The fp32-class varlen attention at head width 192 (snf_sparse_attn_fwd_x3_varlen_dk192): one launch holds 128 keys, up to 8 key
+    chunks.  The older varlen predicates keep answering for dk = 64 / 128 only."""
+    return 1 <= k <= 8 * 128
+
+
 def topk_segmented(scores, packed, k):
     """Top-k of every bag of a packed score vector in one launch: [B, k] int64 indices INSIDE each bag (descending score, ties
     by ascending index -- the same one-workgroup kernel body as topk(), one workgroup per bag).  A bag with fewer than k rows fills
@@ -1200,7 +1243,9 @@ def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fa
 def sparse_attn_fwd_x3_varlen(q, v, kp, packed, k, h, scale=None, need_attn=False, need_lse=False):
     """fp32-class sparse attention of B packed bags in one launch (f32 q, v [T, d], kp [B * k, d]); composition-independent bit
     for bit, O within the fp32 summation order of sparse_attn_fwd_x3() bag by bag.  k above one key chunk
-    (varlen_attn_chunks_supported) runs as the key chunks of sparse_attn_fwd_x3(), with the same guarantees."""
+    (varlen_attn_chunks_supported) runs as the key chunks of sparse_attn_fwd_x3(), with the same guarantees.  Head width 192
+    (varlen_attn_x3_dk192_supported) has an entry point of its own, snf_sparse_attn_fwd_x3_varlen_dk192: 128 keys per chunk, the chunks
+    of sparse_attn_fwd_x3_dk192()."""
     if q.dtype != torch.float32 or v.dtype != torch.float32:
         raise TypeError("sparse_attn_fwd_x3_varlen: q and v must be float32")
     q = _rows16(q, "q")
@@ -1213,12 +1258,17 @@ def sparse_attn_fwd_x3_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fals
     dk = d // h
     scale = 1.0 / math.sqrt(dk) if scale is None else scale
     chunked = not varlen_attn_supported("fp32", k, dk)
-    table, wsb = packed.plan("x3_chunks" if chunked else "x3", k, h, dk)[:2]
+    table, wsb = (packed.plan("x3_dk192", k, h) if dk == 192 else packed.plan("x3_chunks" if chunked else "x3", k, h, dk))[:2]
     ws = _ws(wsb, q.device)
     out = torch.empty(packed.bags * k, d, dtype=torch.float32, device=q.device)
     attn = torch.empty(h, t, k, dtype=torch.float32, device=q.device) if need_attn else None
     lse = torch.empty(h, t, dtype=torch.float32, device=q.device) if need_lse else None
     lib = _ffi.load()
+    if dk == 192:
+        check(lib.snf_sparse_attn_fwd_x3_varlen_dk192(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h,
+                                                      float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()),
+              "snf_sparse_attn_fwd_x3_varlen_dk192")
+        return out, attn, lse
     fn = lib.snf_sparse_attn_fwd_x3_varlen_chunked if chunked else lib.snf_sparse_attn_fwd_x3_varlen
     check(fn(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h, dk, float(scale), _p(out), _p(attn),
              _p(lse), _p(table), _p(ws), wsb, _stream()),

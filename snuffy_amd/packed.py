@@ -30,6 +30,12 @@ PACK_DEVICE_SAMPLER = True
 # (tools/varlen_dk192_time.py).  On: 64 x 1000 patches 7.2 - 9.7x, 64 x 8000 2.07 - 2.57x, the synthetic CAMELYON16-shaped mix
 # 1.84 - 2.26x, host draws and device sampler, return_attention off and on -- no row behind the loop, so no length gate in dk192_ok.
 PACK_DK192 = True
+# Uniform groups of the fp32 model at head width 192 on the varlen forms of the fused fp32-class kernel of that width
+# (ops.varlen_attn_x3_dk192_supported: up to 8 chunks of 128 keys).  False: such bags take the per-bag loop (or the ragged kernel where it
+# takes them), the routing of before, call for call.  Ships off; the rule of PACK_KEY_CHUNKS decides a later flip: on only where the
+# packed route is at least level with the loop at every row of profiles/x3_dk192.txt (tools/x3_dk192_time.py).  Independent of
+# functional.X3_ATTN_DK192, which routes the single bag.
+PACK_X3_DK192 = False
 RAGGED_MAX_ROWS = 4096      # longest bag the ragged (exact fp32, one workgroup per bag and head) attention is meant for
 
 
@@ -40,7 +46,7 @@ def pack_groups(net, bags):
     False): every bag has at least Lambda patches, so all select the same K rows, and the head width is one the MFMA kernels
     take -- varlen forms of the bf16 / fp32-class attention kernels (with PACK_KEY_CHUNKS also Lambda above one key chunk and head widths
     between the kernels', zero-padded; with PACK_DK192 also the bf16 model at head width 192, up to 8 chunks of 128 keys -- fp32 at that
-    width stays per bag).  "ragged" groups: bags shorter than Lambda (they select
+    width packs behind PACK_X3_DK192 and stays per bag without it).  "ragged" groups: bags shorter than Lambda (they select
     ALL their rows, snuffy.py:129) or head widths outside the MFMA kernels (the MIL benchmark sets: D = 166 / 230, h = 2) --
     exact-fp32 ragged attention, bags of at most _RAGGED_MAX_ROWS patches.  With a random share the draws of the reference
     sampler must stay in bag order, so only one uniform group over all bags is formed.  With the device sampler
@@ -79,7 +85,7 @@ def pack_groups(net, bags):
     sizes = [x.shape[-2] for x in bags]
     uniform_dims = (d % 4 == 0 and (SF.ops.varlen_attn_supported(cfg.compute, k1 + k2, d // h)
                                     or key_chunks_ok(layers, cfg.compute, d, h, k1 + k2, len(bags), sum(sizes))
-                                    or dk192_ok(cfg.compute, d, h, k1 + k2))
+                                    or dk192_ok(cfg.compute, d, h, k1 + k2) or x3_dk192_ok(cfg.compute, d, h, k1 + k2))
                     and (cfg.compute == "bf16" or SF.FP32_ATTENTION == "x3"))
     on_device = k2 > 0 and device_draws(cfg) and SF.ops.draw_packed_supported(min(max(sizes), 65536), k1, k2, len(layers))
     if k2 > 0 and not on_device:
@@ -104,8 +110,13 @@ def device_draws(cfg):
 
 def dk192_ok(compute, d, h, k):
     """PACK_DK192: the bf16 model at head width 192 with a key count inside the dk = 192 varlen kernels.  precision="fp32" stays per
-    bag whatever the switch: its route at this width is the unfused score / pooling pair, which has no varlen form."""
+    bag whatever THIS switch: its packed route at this width is the fused fp32-class kernel behind PACK_X3_DK192 (x3_dk192_ok)."""
     return bool(PACK_DK192 and compute == "bf16" and h >= 1 and d == 192 * h and SF.ops.varlen_attn_dk192_supported(k))
+
+
+def x3_dk192_ok(compute, d, h, k):
+    """PACK_X3_DK192: the fp32 model at head width 192 with a key count inside the fused fp32-class varlen kernel of that width."""
+    return bool(PACK_X3_DK192 and compute == "fp32" and h >= 1 and d == 192 * h and SF.ops.varlen_attn_x3_dk192_supported(k))
 
 
 def key_chunks_ok(layers, compute, d, h, k, bags, rows):
@@ -169,7 +180,7 @@ def forward_bags(net, bags):
     run over the packed rows (a library / tile choice that depends on the row count): logits move by fp32 / bf16 rounding.
     Bags that select different numbers of rows (shorter than Lambda) or whose head width the MFMA kernels do not take are
     packed as a second, "ragged" group (pack_groups); head width 192 (D = 768, h = 4) packs in bf16 behind PACK_DK192 and
-    stays per bag in fp32; whatever cannot be packed (training, multiclass critic, ...) takes
+    in fp32 behind PACK_X3_DK192 (off: per bag); whatever cannot be packed (training, multiclass critic, ...) takes
     the per-bag loop."""
     bags = list(bags)
     groups = pack_groups(net, bags)
