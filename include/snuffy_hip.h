@@ -779,6 +779,43 @@ int snf_random_share_keys_batched_f32(const void* state, int layer, int b, int64
                                       int pitch, float* keys, snf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * ResNet-18 patch extractor (csrc/resnet.hip): the reference's SimCLR recipe, torchvision resnet18 with InstanceNorm2d (or eval-mode
+ * BatchNorm2d) and fc = Identity; inference only.  Activations are NHWC ([b, h, w, c] row-major), conv outputs fp32.
+ *   snf_conv2d_nhwc_plan      pure host (needs no GPU): output dims, m = b ho wo output pixels, the 128-row x 64-column tile counts and the
+ *                             workspace bytes (0: the statistics are a pass of their own) of a kh x kh / stride convolution with padding
+ *                             kh / 2.  Kernels exist for 3x3 / 1, 3x3 / 2 and 1x1 / 2 over cin, cout in {64, 128, 256, 512} and for the
+ *                             7x7 / 2 stem from 3 to 64 channels; anything else SNF_EUNSUPPORTED.  Output pointers are nullable.
+ *   snf_conv_pack_weight_f32  w [cout, cin, kh, kw] f32 -> image [cout, kp] bf16 in the kernels' K order (tap-major, channel-minor; kp >=
+ *                             kh kw cin, a multiple of 64, zero beyond the taps); lo (nullable) = bf16(w - hi), the second half of the
+ *                             fp32-class operand.  kp = kh kw cin for the body convolutions, 192 for the stem.
+ *   snf_conv2d_nhwc           implicit-GEMM convolution on the matrix cores, no bias, no im2col matrix in memory.  x f32 or bf16
+ *                             (x_dtype = SNF_DT_*); w_lo = NULL: one bf16 product (f32 x is rounded to bf16 on the way in); w_lo given:
+ *                             hi hi + hi lo + lo hi of the split fp32 operands (x must be f32).  out [m, cout] f32.
+ *   snf_conv_stem             the 7x7 / 2 pad-3 stem, 3 -> 64: x is f32 [b, 3, h, w] (src_u8_nhwc = 0) or uint8 [b, h, w, 3]
+ *                             (src_u8_nhwc = 1, value / 255.0f as to_tensor divides: both entries give the same bits).
+ *   snf_instnorm_stats_nhwc   mean [b, c] and rstd [b, c] = 1 / sqrt(var + eps) (biased variance) per (image, channel) of x [b, hw, c] f32,
+ *                             two passes, fixed summation order (no atomics).  c % 64 == 0.
+ *   snf_norm_act_nhwc         out = (x - mean) rstd gamma + beta (+ identity) (ReLU if relu): mean / rstd [b, c] (per_image = 1) or [c]
+ *                             (per_image = 0: eval-mode BatchNorm constants); gamma, beta [c] and identity [b, hw, c] f32 nullable; out
+ *                             f32 or bf16 (out_dtype = SNF_DT_*).
+ *   snf_maxpool3x3s2_nhwc     3x3 / 2 pad-1 max-pool (padding is -inf), x [b, h, w, c] f32 -> [b, (h - 1) / 2 + 1, (w - 1) / 2 + 1, c].
+ *   snf_avgpool_nhwc          x [b, hw, c] f32 -> mean over hw [b, c], fixed summation order.  c % 64 == 0.
+ * Every pointer 16-byte aligned; b <= 65535 per call for the per-image kernels.
+ * --------------------------------------------------------------------------------------------------------- */
+int snf_conv2d_nhwc_plan(int b, int h, int w, int cin, int cout, int kh, int stride, int* ho, int* wo, int64_t* m, int* tiles_m,
+                         int* tiles_n, size_t* workspace_bytes);
+int snf_conv_pack_weight_f32(const float* w, int cout, int cin, int kh, int kw, int kp, void* hi_bf16, void* lo_bf16, snf_stream_t stream);
+int snf_conv2d_nhwc(const void* x, int x_dtype, const void* w_hi, const void* w_lo, int b, int h, int w, int cin, int cout, int kh,
+                    int stride, float* out, snf_stream_t stream);
+int snf_conv_stem(const void* x, int src_u8_nhwc, const void* w_hi, const void* w_lo, int b, int h, int w, float* out,
+                  snf_stream_t stream);
+int snf_instnorm_stats_nhwc(const float* x, int b, int64_t hw, int c, float eps, float* mean, float* rstd, snf_stream_t stream);
+int snf_norm_act_nhwc(const float* x, int b, int64_t hw, int c, const float* mean, const float* rstd, int per_image, const float* gamma,
+                      const float* beta, const float* identity, int relu, void* out, int out_dtype, snf_stream_t stream);
+int snf_maxpool3x3s2_nhwc(const float* x, int b, int h, int w, int c, float* out, snf_stream_t stream);
+int snf_avgpool_nhwc(const float* x, int b, int64_t hw, int c, float* out, snf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Debug hooks -- PROCESS-WIDE state, outside the stateless / re-entrant contract at the top of this header (see there).  Callers:
  * tests/ (cross-checks of kernel variants against each other) and tools/ (A / B timing, traces); nothing in snuffy_amd/ calls them.
  * snf_debug_attn_trace(buf): device buffer of u64 that dev builds of the attention kernels (X3P_TRACE / SNF_ATTN_TRACE defines)

@@ -219,6 +219,16 @@ SIGNATURES = {
     "snf_random_share_draw_segmented_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p,
                                                     c_void_p, c_size_t, c_void_p]),
     "snf_multiclass_select_f32": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "snf_conv2d_nhwc_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    "snf_conv_pack_weight_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "snf_conv2d_nhwc": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "snf_conv_stem": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "snf_instnorm_stats_nhwc": (c_int, [c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "snf_norm_act_nhwc": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                  c_int, c_void_p]),
+    "snf_maxpool3x3s2_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "snf_avgpool_nhwc": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "snf_debug_attn_trace": (None, [c_void_p]),
     "snf_debug_attn_trace_wg": (None, [c_int]),
     "snf_debug_x3p_kbw": (None, [c_int]),

@@ -1,4 +1,4 @@
-"""MI355X-native mirror of the feature-extraction stage (reference compute_feats.py): tile directory -> ViT embedder ->
+"""MI355X-native mirror of the feature-extraction stage (reference compute_feats.py): tile directory -> ViT or ResNet-18 embedder ->
 one CSV of %.4f features per slide.
 
 Kept (same names / meaning): BagDataset, bag_dataset, compute_feats, get_embedder_backbone, get_embedder,
@@ -15,7 +15,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
-from . import vit
+from . import resnet, vit
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -84,9 +84,10 @@ class DecodeOnly:
 
 def device_preprocess(args):
     """Batched on-device tile preprocessing is the default for the ViT backbones; --device_preprocess 0 keeps the reference's
-    per-tile PIL path on the DataLoader workers."""
+    per-tile PIL path on the DataLoader workers.  resnet18 takes the decoded uint8 tiles as they are (its transform is ToTensor alone,
+    which the stem kernel does on the way in)."""
     is_vit = args.backbone in VIT_BACKBONES or args.backbone == 'vitbasetimm'
-    return is_vit and int(getattr(args, 'device_preprocess', 1)) == 1
+    return (is_vit or args.backbone == 'resnet18') and int(getattr(args, 'device_preprocess', 1)) == 1
 
 
 def bag_dataset(args, patches, patch_labels_dict=None):
@@ -94,6 +95,8 @@ def bag_dataset(args, patches, patch_labels_dict=None):
     is_vit = args.backbone in VIT_BACKBONES or args.backbone == 'vitbasetimm'
     if device_preprocess(args):
         tf = DecodeOnly()
+    elif args.backbone == 'resnet18':
+        tf = TileTransform(None, normalize=False)        # the reference's [ToTensor()]: no resize, no normalisation
     else:
         tf = TileTransform(224 if is_vit else None, normalize=(getattr(args, 'transform', 0) == 1))
     ds = BagDataset(files_list=patches, transform=tf, patch_labels_dict=patch_labels_dict)
@@ -101,9 +104,12 @@ def bag_dataset(args, patches, patch_labels_dict=None):
 
 
 def get_embedder_backbone(args):
-    """DINO / DINO-adapter / MAE-adapter ViT (reference compute_feats.py:369-438); parameters frozen."""
+    """DINO / DINO-adapter / MAE-adapter ViT, or the SimCLR ResNet-18 (reference compute_feats.py:369-438); parameters frozen."""
     kind = args.embedder
-    if 'MAE' in kind:
+    if args.backbone == 'resnet18':
+        model = resnet.ResNet18(norm_layer=getattr(args, 'norm_layer', 'instance'))
+        num_feats = 512
+    elif 'MAE' in kind:
         model = vit.mae_adapter_encoder(patch_size=16, embed_dim=768, depth=12, num_heads=12,
                                         adapter_ffn_scalar=str(getattr(args, 'adapter_ffn_scalar', '1.0')),
                                         adapter_ffn_num=getattr(args, 'ffn_num', 64), adapter_d_model=768)
@@ -137,6 +143,10 @@ def _load_model_weights(args, embedder):
         weights = ckpt['teacher']
     elif 'MAE' in args.embedder:
         weights = ckpt['model']
+    elif args.embedder == 'SimCLR':
+        weights = ckpt                                    # reference compute_feats.py:507-518: the last four entries are the
+        for _ in range(4):                                # projection head (l1 / l2 weight and bias)
+            weights.popitem()
     else:
         print('Didnt load any weights for the embedder!')
         return None
@@ -209,6 +219,11 @@ def compute_feats(args, bags_list, embedder, save_path, patch_labels_dict=None):
                     u8 = batch['input'].to(device, non_blocking=True)
                     norm = getattr(args, 'transform', 0) == 1
                     fe = getattr(embedder, 'feature_extractor', None)
+                    if hasattr(fe, 'forward_u8'):   # resnet18: no resize, no normalisation; the stem reads the uint8 tiles
+                        feats.append(fe.forward_u8(u8).view(u8.shape[0], -1))
+                        labels.extend(np.atleast_1d(batch['label'].squeeze().tolist()).tolist())
+                        positions.extend(batch['position'])
+                        continue
                     if (getattr(fe, 'precision', None) == 'bf16' and hasattr(fe, 'forward_cols')
                             and min(u8.shape[1], u8.shape[2]) >= 224 and u8.shape[1] == u8.shape[2]):
                         # bf16 extractor: the kernel writes the patch-embedding GEMM operand directly (no fp32 image, no patchify)

@@ -2172,3 +2172,139 @@ VIT_MFMA_MAX_T = 4096    # SNF_VIT_MFMA_MAX_T of include/snuffy_hip.h
 
 def vit_mfma_attention_supported(t, dk):
     return dk == 64 and t <= VIT_MFMA_MAX_T
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# ResNet-18 patch extractor (csrc/resnet.hip): NHWC activations, implicit-GEMM convolutions on the matrix cores
+# ----------------------------------------------------------------------------------------------------------------------
+CONV_STEM_KP = 192       # 7 * 7 * 3 = 147 taps x channels of the stem, zero-padded to three 64-deep K steps
+
+
+def conv2d_plan(b, h, w, cin, cout, kh, stride):
+    """(ho, wo, m, tiles_m, tiles_n, workspace_bytes) of a kh x kh / stride convolution (padding kh // 2); pure host, needs no GPU.
+    Raises SnuffyHipError for a shape no kernel covers."""
+    ho, wo, tm, tn = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    m, ws = ctypes.c_int64(), ctypes.c_size_t()
+    check(_ffi.load().snf_conv2d_nhwc_plan(int(b), int(h), int(w), int(cin), int(cout), int(kh), int(stride), ctypes.byref(ho),
+                                           ctypes.byref(wo), ctypes.byref(m), ctypes.byref(tm), ctypes.byref(tn), ctypes.byref(ws)),
+          "snf_conv2d_nhwc_plan")
+    return ho.value, wo.value, m.value, tm.value, tn.value, ws.value
+
+
+def conv2d_supported(b, h, w, cin, cout, kh, stride):
+    """True when snf_conv2d_nhwc (or, for 7x7 / 2 from 3 to 64 channels, snf_conv_stem) has a kernel for the shape."""
+    return _ffi.load().snf_conv2d_nhwc_plan(int(b), int(h), int(w), int(cin), int(cout), int(kh), int(stride), None, None, None, None,
+                                            None, None) == _ffi.SNF_OK
+
+
+def conv_pack_weight(weight, split=False, kp=None):
+    """weight [cout, cin, kh, kw] f32 -> (hi, lo) bf16 images [cout, kp] in the conv kernels' K order; lo is None unless split."""
+    weight = _req(weight, torch.float32, "weight", 4)
+    cout, cin, kh, kw = weight.shape
+    kp = int(kp) if kp is not None else kh * kw * cin
+    hi = torch.empty(cout, kp, dtype=torch.bfloat16, device=weight.device)
+    lo = torch.empty_like(hi) if split else None
+    check(_ffi.load().snf_conv_pack_weight_f32(_p(weight), cout, cin, kh, kw, kp, _p(hi), _p(lo), _stream()), "snf_conv_pack_weight_f32")
+    return hi, lo
+
+
+def _req_image(t, name, cout):
+    t = _req(t, torch.bfloat16, name, 2)
+    if t.shape[0] != cout:
+        raise ValueError("%s has %d rows, the convolution %d output channels" % (name, t.shape[0], cout))
+    return t
+
+
+def conv2d_nhwc(x, w_hi, w_lo, kh, stride):
+    """x [b, h, w, cin] f32 or bf16 (NHWC) * packed weights -> [b, ho, wo, cout] f32.  w_lo given: the fp32-class product (x f32)."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("x must be a float32 or bfloat16 tensor")
+    x = _req(x, x.dtype, "x", 4)
+    b, h, w, cin = x.shape
+    cout = w_hi.shape[0]
+    w_hi = _req_image(w_hi, "w_hi", cout)
+    if w_lo is not None:
+        w_lo = _req_image(w_lo, "w_lo", cout)
+    if w_hi.shape[1] != kh * kh * cin or (w_lo is not None and w_lo.shape != w_hi.shape):
+        raise ValueError("weight image %s does not belong to a %dx%d convolution over %d channels" % (tuple(w_hi.shape), kh, kh, cin))
+    ho, wo = conv2d_plan(b, h, w, cin, cout, kh, stride)[:2]
+    out = torch.empty(b, ho, wo, cout, dtype=torch.float32, device=x.device)
+    check(_ffi.load().snf_conv2d_nhwc(_p(x), DT_F32 if x.dtype == torch.float32 else DT_BF16, _p(w_hi), _p(w_lo), b, h, w, cin, cout,
+                                      int(kh), int(stride), _p(out), _stream()), "snf_conv2d_nhwc")
+    return out
+
+
+def conv_stem(x, w_hi, w_lo=None):
+    """The 7x7 / 2 pad-3 stem: x [b, 3, h, w] f32 (NCHW) or [b, h, w, 3] uint8 (decoded tiles, value / 255) -> [b, ho, wo, 64] f32."""
+    if isinstance(x, torch.Tensor) and x.dtype == torch.uint8:
+        x = _req(x, torch.uint8, "x", 4)
+        b, h, w, c = x.shape
+        u8 = 1
+    else:
+        x = _req(x, torch.float32, "x", 4)
+        b, c, h, w = x.shape
+        u8 = 0
+    if c != 3:
+        raise ValueError("conv_stem: 3 channels expected, got shape %s" % (tuple(x.shape),))
+    w_hi = _req_image(w_hi, "w_hi", 64)
+    if w_lo is not None:
+        w_lo = _req_image(w_lo, "w_lo", 64)
+    if w_hi.shape[1] != CONV_STEM_KP or (w_lo is not None and w_lo.shape != w_hi.shape):
+        raise ValueError("conv_stem: weight image must be [64, %d] (conv_pack_weight(w, kp=CONV_STEM_KP))" % CONV_STEM_KP)
+    ho, wo = conv2d_plan(b, h, w, 3, 64, 7, 2)[:2]
+    out = torch.empty(b, ho, wo, 64, dtype=torch.float32, device=x.device)
+    check(_ffi.load().snf_conv_stem(_p(x), u8, _p(w_hi), _p(w_lo), b, h, w, _p(out), _stream()), "snf_conv_stem")
+    return out
+
+
+def instnorm_stats_nhwc(x, eps=1e-5):
+    """mean, rstd [b, c] per (image, channel) of x [b, h, w, c] f32 (biased variance, InstanceNorm2d)."""
+    x = _req(x, torch.float32, "x", 4)
+    b, h, w, c = x.shape
+    mean = torch.empty(b, c, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    check(_ffi.load().snf_instnorm_stats_nhwc(_p(x), b, h * w, c, float(eps), _p(mean), _p(rstd), _stream()), "snf_instnorm_stats_nhwc")
+    return mean, rstd
+
+
+def norm_act_nhwc(x, mean, rstd, gamma=None, beta=None, identity=None, relu=False, out_dtype=torch.float32):
+    """(x - mean) rstd gamma + beta (+ identity) (ReLU) over x [b, h, w, c] f32; mean / rstd [b, c] (measured) or [c] (constants)."""
+    x = _req(x, torch.float32, "x", 4)
+    b, h, w, c = x.shape
+    mean = _req(mean, torch.float32, "mean")
+    rstd = _req(rstd, torch.float32, "rstd")
+    if mean.shape != rstd.shape or tuple(mean.shape) not in ((b, c), (c,)):
+        raise ValueError("mean / rstd must be [%d, %d] or [%d], got %s / %s" % (b, c, c, tuple(mean.shape), tuple(rstd.shape)))
+    if gamma is not None:
+        gamma = _req(gamma, torch.float32, "gamma", 1)
+    if beta is not None:
+        beta = _req(beta, torch.float32, "beta", 1)
+    if identity is not None:
+        identity = _req(identity, torch.float32, "identity", 4)
+        if identity.shape != x.shape:
+            raise ValueError("identity is %s, x %s" % (tuple(identity.shape), tuple(x.shape)))
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("out_dtype must be float32 or bfloat16")
+    out = torch.empty(b, h, w, c, dtype=out_dtype, device=x.device)
+    check(_ffi.load().snf_norm_act_nhwc(_p(x), b, h * w, c, _p(mean), _p(rstd), int(mean.dim() == 2), _p(gamma), _p(beta), _p(identity),
+                                        int(bool(relu)), _p(out), DT_F32 if out_dtype == torch.float32 else DT_BF16, _stream()),
+          "snf_norm_act_nhwc")
+    return out
+
+
+def maxpool3x3s2_nhwc(x):
+    """3x3 / 2 pad-1 max-pool of x [b, h, w, c] f32 (padding is -inf)."""
+    x = _req(x, torch.float32, "x", 4)
+    b, h, w, c = x.shape
+    out = torch.empty(b, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c, dtype=torch.float32, device=x.device)
+    check(_ffi.load().snf_maxpool3x3s2_nhwc(_p(x), b, h, w, c, _p(out), _stream()), "snf_maxpool3x3s2_nhwc")
+    return out
+
+
+def avgpool_nhwc(x):
+    """Global average pool: x [b, h, w, c] f32 -> [b, c]."""
+    x = _req(x, torch.float32, "x", 4)
+    b, h, w, c = x.shape
+    out = torch.empty(b, c, dtype=torch.float32, device=x.device)
+    check(_ffi.load().snf_avgpool_nhwc(_p(x), b, h * w, c, _p(out), _stream()), "snf_avgpool_nhwc")
+    return out
