@@ -1,5 +1,7 @@
-// Launch geometry shared by the two tiled sparse-attention families (bf16: sparse_attn_mfma_impl.h, fp32-class: sparse_attn_x3.hip):
-// how the (head, row-tile) work items of a bag are cut into workgroups, and the descriptor table of a varlen (many bags) launch.
+// Launch geometry shared by the tiled sparse-attention families at every head width (bf16: sparse_attn_mfma_impl.h at dk = 64 / 128 / 192;
+// fp32-class: sparse_attn_x3_impl.h at 64 / 128, sparse_attn_x3_dk192_impl.h at 192; the fragment-image form sparse_attn_x3p plans for
+// itself): how the (head, row-tile) work items of a bag are cut into workgroups, and the descriptor table of a varlen (many bags)
+// launch.  The host driver built on it -- chunks, workspace carve, operand checks, the pass-by-chunk loop -- is attn_drive.h.
 #pragma once
 #include "common.h"
 

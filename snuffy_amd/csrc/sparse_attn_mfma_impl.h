@@ -3,7 +3,8 @@
 // (implementation header: compiled once per head width by sparse_attn_mfma.hip (dk = 128 + the C entry points),
 // sparse_attn_mfma_dk64.hip and sparse_attn_mfma_dk192.hip, so the kernel variants of the three widths build in parallel; the varlen
 // variants live in sparse_attn_mfma_varlen*.hip, their key-chunked forms in sparse_attn_mfma_varlen_chunks*.hip, every varlen form of
-// dk = 192 with its entry points in sparse_attn_mfma_varlen_dk192.hip)
+// dk = 192 with its entry points in sparse_attn_mfma_varlen_dk192.hip.  The host driver of the entry points is attn_drive.h: this header
+// keeps the family's chunk rule, planner and kernel switches)
 //
 //   per head a:   P_a = softmax_j(Q_a Kp_a^T * scale)  [n, k]      O_a = P_a^T V_a  [k, dk]        (snuffy.py:160-168)
 //
@@ -32,7 +33,7 @@
 
 #include <type_traits>
 
-#include "attn_plan.h"
+#include "attn_drive.h"
 #include "mfma.h"
 #include "philox.h"
 
@@ -92,6 +93,7 @@ using Plan = TilePlan;   // make_plan below; the varlen table (VL_DESC, make_var
 
 namespace {
 using snf_attn::AttnParams;
+using snf_attn::Chunks;
 using snf_attn::Plan;
 using snf_attn::VL_DESC;
 using snf_attn::VarlenPlan;
@@ -958,7 +960,7 @@ int launch_variant(const AttnParams& P, const Plan& pl, float* out, hipStream_t 
     int rc = snf::check_launch("sparse_attn_mfma_kernel");
     if (rc) return rc;
     constexpr int TILES = NKB * (DK / 32);
-    if (VL && P.out_direct && pl.tiles_per_head == -1) return SNF_OK;   // every bag stored its heads itself (make_varlen_plan)
+    if (VL && P.out_direct && pl.tiles_per_head == -1) return SNF_OK;   // every bag stored its heads itself (varlen_tile_plan)
     // varlen: pl.num_wg is the whole grid (all bags), one reduction slice (blockIdx.z) per bag
     hipLaunchKernelGGL((reduce_partials_kernel<DK, NKB>), dim3(TILES * 4, P.h, VL ? P.vl_bags : 1), dim3(64), 0, s, P.partial,
                        pl.num_wg, pl.seg_count, pl.tiles_per_head, pl.tiles_per_wg, pl.total_tiles, P.k, P.h, out,
@@ -994,13 +996,6 @@ int launch_nkb_varlen(const AttnParams& P, const Plan& pl, float* out, hipStream
 #undef SNF_ATTN_VL_CASE
     snf::set_error("sparse_attn_mfma (varlen): key-block count %d not built", pl.nkb);
     return SNF_EUNSUPPORTED;
-}
-
-// Geometry of a varlen launch: every bag keeps the plan of its own launch (make_plan), the grids are concatenated.
-inline bool make_varlen_plan(const int64_t* offsets, int bags, int k, int h, int dk, VarlenPlan* vp, int32_t* table,
-                             size_t table_ints) {
-    return snf_attn::make_varlen_table(offsets, bags, k, vp, table, table_ints,
-                                       [&](int64_t n, Plan* pl) { return make_plan(n, k, h, dk, pl, true); });
 }
 
 #define SNF_ATTN_CASE(NB, EXT)                                                                     \
@@ -1069,10 +1064,6 @@ int launch_nkb(const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
 }
 #undef SNF_ATTN_CASE
 #undef SNF_ATTN_CASE8
-
-inline size_t mfma_workspace_bytes(const Plan& pl, int dk) {
-    return (size_t)pl.num_wg * pl.seg_count * (size_t)(pl.nkb * (dk / 32)) * 1024 * sizeof(float);
-}
 
 template <int DK, int NKB, typename QT, bool VL = false>
 int launch_stats_variant(const AttnParams& P, const Plan& pl, hipStream_t s) {
@@ -1148,30 +1139,42 @@ __global__ __launch_bounds__(256) void kp_to_bf16_kernel(const float* __restrict
     if (g >= groups) return;
     *reinterpret_cast<u32x4*>(dst + g * 8) = __builtin_bit_cast(u32x4, load_frag(src + g * 8));
 }
-inline size_t kp_staging_bytes(int k, int h, int dk) { return ((size_t)k * h * dk * 2 + 255) / 256 * 256; }
-
 constexpr int MAX_CHUNKS = 8;
-struct ChunkPlan {
-    int n_chunks, chunk_k;   // chunk c covers keys [c * chunk_k, min(k, (c + 1) * chunk_k))
-};
-inline bool make_chunks(int k, int dk, ChunkPlan* cp) {
+inline bool make_chunks(int k, int dk, Chunks* cp) {
     const int kmax = attn_kmax(dk);
     if (!kmax || k < 1) return false;
     const int nc = (k + kmax - 1) / kmax;
     if (nc > MAX_CHUNKS) return false;
-    cp->n_chunks = nc;
-    cp->chunk_k = (k + nc - 1) / nc;
+    cp->count = nc;
+    cp->size = (k + nc - 1) / nc;
     return true;
 }
-// bytes of the partial-accumulator area (largest chunk) and of the statistics area behind it
-inline bool chunked_workspace(int64_t n, int k, int h, int dk, size_t* partial_bytes, size_t* stats_bytes) {
-    ChunkPlan cp;
-    Plan pl;
-    if (!make_chunks(k, dk, &cp) || !make_plan(n, cp.chunk_k, h, dk, &pl)) return false;
-    *partial_bytes = (mfma_workspace_bytes(pl, dk) + 255) / 256 * 256;
-    *stats_bytes = cp.n_chunks > 1 ? (size_t)cp.n_chunks * h * n * 2 * sizeof(float) : 0;
-    return true;
-}
+
+// What every bf16 driver shares of its family description (attn_drive.h lists the members)
+struct MfmaDrive {
+    using Params = AttnParams;
+    using Kp = unsigned short;
+    static constexpr size_t ROUND = 256;
+    static constexpr bool STAGE_KP = true, OFFSETS32 = true, BAG_NKB_OF_LARGEST = false;
+    static constexpr const char* DK_TEXT = "dk";
+    // the kernels read Kp as bf16 (half the bytes of the cold prologue burst every workgroup starts with); an f32 Kp is rounded once
+    // here, to the same values the kernels used to produce in flight
+    static int kp(const void* kp, bool f32, int64_t elems, void* stage, hipStream_t s, const unsigned short** kp16) {
+        *kp16 = reinterpret_cast<const unsigned short*>(f32 ? stage : kp);
+        if (!f32) return SNF_OK;
+        const int64_t groups = elems / 8;
+        hipLaunchKernelGGL(kp_to_bf16_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float*>(kp),
+                           reinterpret_cast<unsigned short*>(stage), groups);
+        return snf::check_launch("kp_to_bf16_kernel");
+    }
+    // statistics [count][h][n_stride][2]: a statistics pass writes its chunk's plane, a main pass of a chunked launch reads them all
+    static void chunk(AttnParams& P, bool stats_pass, int c, int k0, int count, void* stats_area) {
+        float* stats = reinterpret_cast<float*>(stats_area);
+        P.key0 = k0, P.n_chunks = count;
+        P.stats = (stats_pass || count == 1) ? nullptr : stats;
+        P.stats_out = stats_pass ? stats + (size_t)c * P.h * P.n_stride * 2 : nullptr;
+    }
+};
 
 }  // namespace
 

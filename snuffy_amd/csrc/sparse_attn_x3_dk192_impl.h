@@ -453,9 +453,6 @@ inline bool x3w_chunks(int k, X3Chunks* c) {
     return c->size <= X3W_KMAX;
 }
 constexpr bool x3w_chunk_built(int nkb) { return nkb == 2 || nkb == 4; }
-inline size_t x3w_workspace(const X3Plan& pl) {
-    return (size_t)pl.num_wg * pl.seg_count * (size_t)(pl.nkb * (X3W_DK / 32)) * 1024 * sizeof(float);
-}
 
 template <int NKB, bool AUX, int MODE, bool VL>
 int x3w_launch(const X3Params& P, const X3Plan& pl, float* out, hipStream_t s) {

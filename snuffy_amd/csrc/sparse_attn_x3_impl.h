@@ -1,6 +1,7 @@
 #pragma once
 // (implementation header: compiled by sparse_attn_x3.hip -- the single-bag and single-chunk varlen variants and the C entry points -- and
-// by sparse_attn_x3_varlen_chunks.hip, the key-chunked varlen variants)
+// by sparse_attn_x3_varlen_chunks.hip, the key-chunked varlen variants; included by sparse_attn_x3_dk192_impl.h.  The host driver of
+// the entry points is attn_drive.h: this header keeps the family's chunk rule, planner and kernel switches)
 // K7 (fp32-class form on the matrix cores): Snuffy's sparse attention with SPLIT-bf16 operands.
 //
 //   per head a:   P_a = softmax_j(Q_a Kp_a^T * scale)  [n, k]      O_a = P_a^T V_a  [k, dk]        (snuffy.py:160-168)
@@ -28,7 +29,7 @@
 // LDS at dk = 128, 224 keys: Q hi+lo 32 KiB | P hi+lo 56 KiB | V 2 x (hi+lo) 64 KiB | row statistics 4 KiB = 156 KiB.
 #include <math.h>
 
-#include "attn_plan.h"
+#include "attn_drive.h"
 #include "mfma.h"
 #include "philox.h"
 
@@ -65,7 +66,7 @@ using snf_attn::VL_DESC;
 using snf_attn::X3Params;
 using snf_attn::p_row_bytes;
 using X3Plan = snf_attn::TilePlan;
-using X3VarlenPlan = snf_attn::VarlenPlan;
+using X3Chunks = snf_attn::Chunks;   // x3_chunks / x3w_chunks: count chunks of size keys
 
 constexpr int TROWS = 64;   // query rows per step (two 32-row blocks)
 
@@ -528,7 +529,6 @@ inline bool x3_plan(int64_t n, int k, int h, int dk, X3Plan* pl, bool packed = f
     // a bag inside a packed (varlen) launch: at least 16 tiles (1024 rows) per workgroup
     return snf_attn::make_tile_plan(n, h, TROWS, /*small_bag_tiles=*/16, packed, pl);
 }
-inline size_t x3_workspace(const X3Plan& pl, int dk) { return (size_t)pl.num_wg * pl.seg_count * (size_t)(pl.nkb * (dk / 32)) * 1024 * sizeof(float); }
 
 template <int DK, int NKB, bool AUX, int MODE, bool VL = false, bool DROP = false>
 int x3_launch(const X3Params& P, const X3Plan& pl, float* out, hipStream_t s) {
@@ -542,7 +542,7 @@ int x3_launch(const X3Params& P, const X3Plan& pl, float* out, hipStream_t s) {
     int rc = snf::check_launch("sparse_attn_x3_kernel");
     if (rc || MODE == 1) return rc;
     constexpr int TILES = NKB * (DK / 32);
-    if (VL && P.out_direct && pl.tiles_per_head == -1) return SNF_OK;   // every bag stored its heads itself (x3_varlen_plan)
+    if (VL && P.out_direct && pl.tiles_per_head == -1) return SNF_OK;   // every bag stored its heads itself (varlen_tile_plan)
     hipLaunchKernelGGL((x3_reduce_kernel<DK, NKB>), dim3(TILES * 4, P.h, VL ? P.vl_bags : 1), dim3(64), 0, s, P.partial, pl.num_wg,
                        pl.seg_count, pl.tiles_per_head, pl.tiles_per_wg, P.k, P.h, out, VL ? P.vl : nullptr,
                        (VL && P.out_direct) ? 1 : 0);
@@ -570,7 +570,7 @@ int x3_dispatch_varlen(const X3Params& P, const X3Plan& pl, float* out, hipStrea
 // key-block counts the key-chunked varlen launches are built for.  From x3_chunks: count >= 2 chunks of size = ceil(k / count) rounded up
 // to a multiple of 4, with k > (count - 1) kmax, so size > kmax / 2 (dk = 128: 116 .. 224, dk = 64: 132 .. 256) and the last chunk
 // k - (count - 1) size >= k / count - 4 (count - 1) > kmax (count - 1) / count - 4 (count - 1) >= kmax / 2 - 4 (108 / 124 keys at least):
-// every chunk needs 4 .. 7 (dk = 64: 8) key blocks, which x3_plan serves with 4, 7 (and 8).  x3_varlen_chunks checks every chunk of a
+// every chunk needs 4 .. 7 (dk = 64: 8) key blocks, which x3_plan serves with 4, 7 (and 8).  plan_varlen (attn_drive.h) checks every chunk of a
 // launch against this set, and tests/test_varlen_chunks_host.py walks every k.
 constexpr bool x3_varlen_chunk_built(int dk, int nkb) { return nkb == 4 || nkb == 7 || (nkb == 8 && dk == 64); }
 template <int DK>
@@ -594,14 +594,6 @@ int x3_dispatch_varlen_chunk(const X3Params& P, const X3Plan& pl, float* out, hi
 #undef SNF_X3_VLC_CASE
     snf::set_error("sparse_attn_x3 (varlen, key chunks): key-block count %d not built", pl.nkb);
     return SNF_EUNSUPPORTED;
-}
-inline bool x3_varlen_plan(const int64_t* offsets, int bags, int k, int h, int dk, X3VarlenPlan* vp, int32_t* table, size_t table_ints) {
-    if (bags < 1 || k > (dk == 128 ? 224 : 256)) {   // single key chunk only
-        vp->total_wg = 0, vp->partial_slots = 0, vp->nkb = 0, vp->all_direct = true;
-        return false;
-    }
-    return snf_attn::make_varlen_table(offsets, bags, k, vp, table, table_ints,
-                                       [&](int64_t n, X3Plan* pl) { return x3_plan(n, k, h, dk, pl, true); });
 }
 template <int DK, int NB>
 int x3_modes(const X3Params& P, const X3Plan& pl, float* out, hipStream_t s, int mode) {
@@ -640,9 +632,6 @@ int x3_dispatch(const X3Params& P, const X3Plan& pl, float* out, hipStream_t s, 
 }
 
 // keys per launch: one LDS image holds kmax keys; more keys run as up to 8 chunks of equal size (a multiple of 4)
-struct X3Chunks {
-    int count, size;
-};
 inline bool x3_chunks(int k, int dk, X3Chunks* c) {
     const int kmax = dk == 128 ? 224 : 256;
     if (!(dk == 64 || dk == 128) || k < 1 || k > 8 * kmax) return false;
@@ -650,6 +639,20 @@ inline bool x3_chunks(int k, int dk, X3Chunks* c) {
     c->size = c->count == 1 ? k : ((k + c->count - 1) / c->count + 3) & ~3;
     return c->size <= kmax;
 }
+
+
+// What every fp32-class driver shares of its family description (attn_drive.h lists the members)
+struct X3Drive {
+    using Params = X3Params;
+    using Kp = float;
+    static constexpr size_t ROUND = 1;
+    static constexpr bool STAGE_KP = false, OFFSETS32 = false;
+    static int kp(const float* kp, bool, int64_t, void*, hipStream_t, const float** used) { return *used = kp, SNF_OK; }
+    // statistics [count][h][n_stride] of (max, sum) pairs: MODE 1 writes plane `chunk`, MODE 2 reads them all, MODE 0 none
+    static void chunk(X3Params& P, bool, int c, int, int count, void* stats_area) {
+        P.stats = reinterpret_cast<f32x2*>(stats_area), P.nchunks = count, P.chunk = c;
+    }
+};
 
 }  // namespace
 

@@ -516,7 +516,9 @@ def test_sparse_attn_mfma_online_max_spike():
 @pytest.mark.parametrize("n,k,h,dk", [(1000, 200, 6, 128), (4097, 224, 3, 128), (33, 7, 2, 128), (1, 1, 1, 64), (700, 256, 6, 64),
                                       (2500, 150, 6, 64), (5000, 100, 2, 128), (31, 40, 4, 64), (300, 33, 1, 128),
                                       # more keys than one LDS image: key chunks with exact cross-chunk statistics
-                                      (3000, 512, 6, 128), (700, 225, 2, 128), (1500, 601, 3, 64), (257, 1790, 1, 128), (100, 2048, 2, 64)])
+                                      (3000, 512, 6, 128), (700, 225, 2, 128), (1500, 601, 3, 64), (257, 1790, 1, 128), (100, 2048, 2, 64),
+                                      # chunks of 132 and 125 keys (7 and 4 key blocks): both launch at the larger count
+                                      (300, 257, 2, 128)])
 def test_sparse_attn_x3_fp32_class(n, k, h, dk):
     """snf_sparse_attn_fwd_x3 (split-bf16 x 3 on the matrix cores) against the fp64 oracle on the UNROUNDED operands: the
     reference's own arithmetic class (fp32), not the bf16 one.  Measured: P <= 3.5e-6, O <= 1e-5 of its scale (the exact
