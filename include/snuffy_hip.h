@@ -731,6 +731,23 @@ int snf_sparse_attn_fwd_x3_varlen_dk192(const float* q, int64_t ldq, const float
                                         const int64_t* offsets, int bags, int k, int h, float scale, float* out, float* attn,
                                         float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
                                         snf_stream_t stream);
+/* The same at HEAD WIDTH 256 (D = 512, h = 2: the SimCLR ResNet-18 recipe, Lambda = 900): the protocol, arguments, layouts, alignment
+ * rules and error codes of the four _x3_dk192 entry points above, with kp / out rows of h * 256 floats.  The plan functions of
+ * dk = 64 / 128 and of 192 keep answering SNF_EUNSUPPORTED at dk = 256.  One launch holds 128 keys (1, 2 or 4 key blocks); a workgroup
+ * is four waves (the Kp fragments of a key block are 128 registers per lane) over 32-row tiles: Q 32 + P 20 + V 2 x 32 + statistics
+ * 1 KiB of LDS at 4 blocks.  More keys run as up to 8 chunks of ceil(k / chunks) keys rounded up to a multiple of 4 (the last chunk
+ * shorter; chunked launches run at 2 or 4 key blocks), so 1 <= k <= 8 x 128, the key range of snf_sparse_attn_fwd_x3u_f32.
+ * Inference only. */
+size_t snf_sparse_attn_fwd_x3_dk256_workspace_bytes(int64_t n, int k, int h);
+int snf_sparse_attn_fwd_x3_dk256(const float* q, int64_t ldq, const float* v, int64_t ldv, const float* kp, int64_t n, int k, int h,
+                                 float scale, float* out, float* attn, float* lse, void* workspace, size_t workspace_bytes,
+                                 snf_stream_t stream);
+int snf_sparse_attn_x3_varlen_dk256_plan(const int64_t* offsets, int bags, int k, int h, int32_t* table, size_t table_ints,
+                                         size_t* table_ints_needed, size_t* workspace_bytes, int* n_chunks, int* chunk_k);
+int snf_sparse_attn_fwd_x3_varlen_dk256(const float* q, int64_t ldq, const float* v, int64_t ldv, const float* kp,
+                                        const int64_t* offsets, int bags, int k, int h, float scale, float* out, float* attn,
+                                        float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
+                                        snf_stream_t stream);
 /* Ragged form for SMALL bags (exact fp32, any head width, every bag with its own key count: a bag shorter than Lambda selects
  * all of its rows -- snuffy.py:129 `min(ceil(...), n)` -- as the MIL benchmark sets do).  desc_dev [bags][4] int32 in DEVICE
  * memory = (first packed row, rows, first key row, keys) per bag; kp / out [sum of keys, h * dk]; attn [h, T, kmax] nullable

@@ -52,6 +52,12 @@ MFMA_ATTN_DK192 = False
 # before.  Ships off: on only if no row of profiles/x3_dk192.txt (tools/x3_dk192_time.py) is behind the pair.  The packed route
 # (packed.PACK_X3_DK192) does not consult this switch.
 X3_ATTN_DK192 = False
+# fp32 inference of a single bag at head width 256 (D = 512 with h = 2, the README's SimCLR ResNet-18 recipe) on the FUSED fp32-class
+# kernel of that width (ops.x3_attn_dk256_supported: up to 8 chunks of 128 keys); False: the unfused score / pooling pair
+# (ops.sparse_attn_fwd_x3u), as before.  Ships off under the rule "on only if no row is behind": profiles/x3_dk256.txt
+# (tools/x3_dk256_time.py) has the fused kernel at 0.76 - 0.88x the pair at N = 8000 / 32768 (eight key chunks at Lambda = 900, GEMM1
+# run twice).  The packed route (packed.PACK_X3_DK256) does not consult this switch.
+X3_ATTN_DK256 = False
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -640,7 +646,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
                                  "kernel" % (k, ragged.kmax, d // h))
     elif packed is not None and (kb < 1 or not (ops.varlen_attn_chunks_supported(precision, kb, packed_head_pad(d // h) or d // h)
                                                or (precision == "bf16" and d == 192 * h and ops.varlen_attn_dk192_supported(kb))
-                                               or (precision == "fp32" and d == 192 * h and ops.varlen_attn_x3_dk192_supported(kb)))):
+                                               or (precision == "fp32" and d == 192 * h and ops.varlen_attn_x3_dk192_supported(kb))
+                                               or (precision == "fp32" and d == 256 * h and ops.varlen_attn_x3_dk256_supported(kb)))):
         raise SnuffyHipError("packed bags: %d keys per bag at head width %d is outside the varlen attention kernels" % (kb, d // h))
     n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
     lq, lk, lv, lo = mha.linears
@@ -724,6 +731,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             o, attn, _ = ops.sparse_attn_fwd_x3(q, v, kp, h, need_attn=need_attn)    # snuffy.py:160-168
         elif FP32_ATTENTION == "x3" and X3_ATTN_DK192 and d == 192 * h and ops.x3_attn_dk192_supported(k):
             o, attn, _ = ops.sparse_attn_fwd_x3_dk192(q, v, kp, h, need_attn=need_attn)   # q, v: halves of the fused projection, in place
+        elif FP32_ATTENTION == "x3" and X3_ATTN_DK256 and d == 256 * h and ops.x3_attn_dk256_supported(k):
+            o, attn, _ = ops.sparse_attn_fwd_x3_dk256(q, v, kp, h, need_attn=need_attn)   # q, v: halves of the fused projection, in place
         elif FP32_ATTENTION == "x3" and ops.x3u_attn_supported(k, d // h):
             # head widths no pipelined kernel takes (dk = 192: the README recipe D = 768 / h = 4): the unfused fp32-class pair
             o, attn, _ = ops.sparse_attn_fwd_x3u(q, kp, v, h, need_attn=need_attn)      # q, v: halves of the fused projection, in place

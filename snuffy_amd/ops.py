@@ -923,6 +923,41 @@ def sparse_attn_fwd_x3_dk192(q, v, kp, h, scale=None, need_attn=False, need_lse=
     return out, attn, lse
 
 
+def x3_attn_dk256_supported(k):
+    """Shapes of the fused fp32-class attention kernel at head width 256 (snf_sparse_attn_fwd_x3_dk256; the README's SimCLR ResNet-18
+    recipe D = 512, h = 2, Lambda = 900): 128 keys per launch, up to 8 key chunks with exact cross-chunk softmax statistics -- the key
+    range of the unfused pair (x3u_attn_supported).  x3_attn_supported() keeps answering for dk = 64 / 128 only."""
+    return 1 <= k <= 8 * 128
+
+
+def sparse_attn_fwd_x3_dk256(q, v, kp, h, scale=None, need_attn=False, need_lse=False):
+    """fp32-class sparse attention on the matrix cores at head width 256, fused (snf_sparse_attn_fwd_x3_dk256: no materialised
+    [h, n, k] probabilities between the softmax and P^T V): q, v [n, 256 h] f32 (row-strided views allowed: the halves of a fused
+    [Q | V] projection), kp [k, 256 h] f32 -> (out [k, d], attn [h, n, k] or None, lse [h, n] or None)."""
+    if q.dtype != torch.float32 or v.dtype != torch.float32:
+        raise TypeError("sparse_attn_fwd_x3_dk256: q and v must be float32")
+    q = _rows16(q, "q")
+    v = _rows16(v, "v")
+    kp = _req(kp, torch.float32, "kp", 2)
+    n, d = q.shape
+    k = kp.shape[0]
+    if d != 256 * h or kp.shape[1] != d or v.shape != q.shape:
+        raise ValueError("sparse_attn_fwd_x3_dk256: inconsistent shapes q %s v %s kp %s h %d (d_model must be 256 h)"
+                         % (tuple(q.shape), tuple(v.shape), tuple(kp.shape), h))
+    scale = 1.0 / math.sqrt(256) if scale is None else scale
+    lib = _ffi.load()
+    wsb = lib.snf_sparse_attn_fwd_x3_dk256_workspace_bytes(n, k, h)
+    if wsb == 0:
+        raise ValueError("sparse_attn_fwd_x3_dk256: unsupported shape n=%d k=%d h=%d (1 <= k <= 1024)" % (n, k, h))
+    out = torch.empty(k, d, dtype=torch.float32, device=q.device)
+    attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
+    lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
+    ws = _ws(wsb, q.device)
+    check(lib.snf_sparse_attn_fwd_x3_dk256(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), n, k, h, float(scale), _p(out), _p(attn),
+                                           _p(lse), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_x3_dk256")
+    return out, attn, lse
+
+
 _X3_HL_OK = {}
 
 
@@ -1077,8 +1112,8 @@ class PackedBags:
 
     def plan(self, kind, *shape):
         """(device table int32, workspace bytes) of a segmented launch: kind in {"mfma", "x3", "head"}; the key-chunked attention
-        plans "mfma_chunks" / "x3_chunks" and the head-width-192 plans "mfma_dk192" / "x3_dk192" (shape = (k, h)) add (chunk count, keys
-        per chunk)."""
+        plans "mfma_chunks" / "x3_chunks", the head-width-192 plans "mfma_dk192" / "x3_dk192" and the head-width-256 plan "x3_dk256"
+        (shape = (k, h)) add (chunk count, keys per chunk)."""
         import numpy as np
         key = (kind,) + tuple(shape)
         hit = self._plans.get(key)
@@ -1089,8 +1124,8 @@ class PackedBags:
         fn = {"mfma": lib.snf_sparse_attn_varlen_plan, "x3": lib.snf_sparse_attn_x3_varlen_plan,
               "mfma_chunks": lib.snf_sparse_attn_varlen_chunked_plan, "x3_chunks": lib.snf_sparse_attn_x3_varlen_chunked_plan,
               "mfma_dk192": lib.snf_sparse_attn_varlen_dk192_plan, "x3_dk192": lib.snf_sparse_attn_x3_varlen_dk192_plan,
-              "head": lib.snf_ln_mean_head_varlen_plan}[kind]
-        chunks = (ctypes.c_int(0), ctypes.c_int(0)) if kind.endswith("_chunks") or kind.endswith("_dk192") else ()
+              "x3_dk256": lib.snf_sparse_attn_x3_varlen_dk256_plan, "head": lib.snf_ln_mean_head_varlen_plan}[kind]
+        chunks = (ctypes.c_int(0), ctypes.c_int(0)) if kind.endswith(("_chunks", "_dk192", "_dk256")) else ()
         extra = tuple(ctypes.byref(c) for c in chunks)
         check(fn(self._host_ptr(), self.bags, *shape, None, 0, ctypes.byref(need), ctypes.byref(wsb), *extra), "varlen plan (%s)" % kind)
         table = np.zeros(need.value, dtype=np.int32)
@@ -1186,6 +1221,12 @@ def varlen_attn_x3_dk192_supported(k):
     return 1 <= k <= 8 * 128
 
 
+def varlen_attn_x3_dk256_supported(k):
+    """The fp32-class varlen attention at head width 256 (snf_sparse_attn_fwd_x3_varlen_dk256): one launch holds 128 keys, up to 8 key
+    chunks.  The older varlen predicates keep answering for dk = 64 / 128 (and 192) only."""
+    return 1 <= k <= 8 * 128
+
+
 def topk_segmented(scores, packed, k):
     """Top-k of every bag of a packed score vector in one launch: [B, k] int64 indices INSIDE each bag (descending score, ties
     by ascending index -- the same one-workgroup kernel body as topk(), one workgroup per bag).  A bag with fewer than k rows fills
@@ -1245,7 +1286,7 @@ def sparse_attn_fwd_x3_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fals
     for bit, O within the fp32 summation order of sparse_attn_fwd_x3() bag by bag.  k above one key chunk
     (varlen_attn_chunks_supported) runs as the key chunks of sparse_attn_fwd_x3(), with the same guarantees.  Head width 192
     (varlen_attn_x3_dk192_supported) has an entry point of its own, snf_sparse_attn_fwd_x3_varlen_dk192: 128 keys per chunk, the chunks
-    of sparse_attn_fwd_x3_dk192()."""
+    of sparse_attn_fwd_x3_dk192(); head width 256 (varlen_attn_x3_dk256_supported) likewise, snf_sparse_attn_fwd_x3_varlen_dk256."""
     if q.dtype != torch.float32 or v.dtype != torch.float32:
         raise TypeError("sparse_attn_fwd_x3_varlen: q and v must be float32")
     q = _rows16(q, "q")
@@ -1258,7 +1299,8 @@ def sparse_attn_fwd_x3_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fals
     dk = d // h
     scale = 1.0 / math.sqrt(dk) if scale is None else scale
     chunked = not varlen_attn_supported("fp32", k, dk)
-    table, wsb = (packed.plan("x3_dk192", k, h) if dk == 192 else packed.plan("x3_chunks" if chunked else "x3", k, h, dk))[:2]
+    table, wsb = (packed.plan("x3_dk%d" % dk, k, h) if dk in (192, 256)
+                  else packed.plan("x3_chunks" if chunked else "x3", k, h, dk))[:2]
     ws = _ws(wsb, q.device)
     out = torch.empty(packed.bags * k, d, dtype=torch.float32, device=q.device)
     attn = torch.empty(h, t, k, dtype=torch.float32, device=q.device) if need_attn else None
@@ -1268,6 +1310,11 @@ def sparse_attn_fwd_x3_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fals
         check(lib.snf_sparse_attn_fwd_x3_varlen_dk192(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h,
                                                       float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()),
               "snf_sparse_attn_fwd_x3_varlen_dk192")
+        return out, attn, lse
+    if dk == 256:
+        check(lib.snf_sparse_attn_fwd_x3_varlen_dk256(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h,
+                                                      float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()),
+              "snf_sparse_attn_fwd_x3_varlen_dk256")
         return out, attn, lse
     fn = lib.snf_sparse_attn_fwd_x3_varlen_chunked if chunked else lib.snf_sparse_attn_fwd_x3_varlen
     check(fn(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h, dk, float(scale), _p(out), _p(attn),
