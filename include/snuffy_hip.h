@@ -748,6 +748,33 @@ int snf_sparse_attn_fwd_x3_varlen_dk256(const float* q, int64_t ldq, const float
                                         const int64_t* offsets, int bags, int k, int h, float scale, float* out, float* attn,
                                         float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
                                         snf_stream_t stream);
+/* The bf16 family at HEAD WIDTH 256 (the same recipe in precision="bf16"), inference only: q and v are bf16 ONLY (row pitches ldq / ldv
+ * in elements, so the two halves of one [N, 2D] projection are passed in place), kp is f32 or bf16 (kp_dtype; an f32 Kp is rounded to
+ * bf16 once, round to nearest even, into the workspace: both give the same bits), out / attn / lse are f32.  snf_sparse_attn_fwd_mfma and
+ * the varlen plan functions of dk = 64 / 128 and of 192 keep answering SNF_EUNSUPPORTED at dk = 256.  One launch holds 128 keys (1, 2 or
+ * 4 key blocks); a workgroup is four waves (the Kp fragments of a key block stay in 64 registers per lane for a whole head) over 32-row
+ * tiles: Q 16 + P 10 + V 2 x 16 + statistics 1 KiB of LDS at 4 blocks.  More keys run as up to 8 near-equal chunks of
+ * ceil(k / chunks) keys (the family's rule; chunked launches run at 2 or 4 key blocks): a statistics pass per chunk into
+ * [chunks][h][n][2], then the main passes, which combine the chunks' statistics exactly.  So 1 <= k <= 8 x 128.
+ *   ..._mfma_dk256_workspace_bytes  partial tiles | statistics | bf16 copy of an f32 Kp; 0 = unsupported (k outside 1 .. 1024, n < 1 or
+ *                      above 0xffff00, h < 1).
+ *   snf_sparse_attn_fwd_mfma_dk256  alignment rules and error codes of snf_sparse_attn_fwd_mfma (16-byte aligned q / v / kp and row
+ *                      pitches of a multiple of 8 elements: SNF_EINVAL; pitches of 2^24 elements or n * pitch of 2^31 - 1 elements and
+ *                      more: SNF_EUNSUPPORTED; a short workspace: SNF_EWORKSPACE).  A repeated call is bit-identical (no atomics).
+ *   snf_sparse_attn_varlen_dk256_plan / snf_sparse_attn_fwd_mfma_varlen_dk256  signatures and protocol of the two _dk192 entry points
+ *                      above.  SNF_EUNSUPPORTED: k outside 1 .. 1024, h < 1, an empty bag.  A bag's attn and lse are those of
+ *                      snf_sparse_attn_fwd_mfma_dk256 on that bag alone, bit for bit, out within the fp32 order of the partial sums, and
+ *                      nothing depends on what a bag is packed with. */
+size_t snf_sparse_attn_fwd_mfma_dk256_workspace_bytes(int64_t n, int k, int h);
+int snf_sparse_attn_fwd_mfma_dk256(const void* q, int64_t ldq, const void* v, int64_t ldv, const void* kp, int kp_dtype, int64_t n, int k,
+                                   int h, float scale, float* out, float* attn, float* lse, void* workspace, size_t workspace_bytes,
+                                   snf_stream_t stream);
+int snf_sparse_attn_varlen_dk256_plan(const int64_t* offsets, int bags, int k, int h, int32_t* table, size_t table_ints,
+                                      size_t* table_ints_needed, size_t* workspace_bytes, int* n_chunks, int* chunk_k);
+int snf_sparse_attn_fwd_mfma_varlen_dk256(const void* q, int64_t ldq, const void* v, int64_t ldv, const void* kp, int kp_dtype,
+                                          const int64_t* offsets, int bags, int k, int h, float scale, float* out, float* attn,
+                                          float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
+                                          snf_stream_t stream);
 /* Ragged form for SMALL bags (exact fp32, any head width, every bag with its own key count: a bag shorter than Lambda selects
  * all of its rows -- snuffy.py:129 `min(ceil(...), n)` -- as the MIL benchmark sets do).  desc_dev [bags][4] int32 in DEVICE
  * memory = (first packed row, rows, first key row, keys) per bag; kp / out [sum of keys, h * dk]; attn [h, T, kmax] nullable

@@ -208,6 +208,14 @@ SIGNATURES = {
                                                      c_void_p]),
     "snf_sparse_attn_fwd_x3_varlen_dk256": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int,
                                                     c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "snf_sparse_attn_fwd_mfma_dk256_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "snf_sparse_attn_fwd_mfma_dk256": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_float,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "snf_sparse_attn_varlen_dk256_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
+    "snf_sparse_attn_fwd_mfma_varlen_dk256": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
+                                                      c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                      c_void_p]),
     "snf_sparse_attn_fwd_ragged_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
                                                c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "snf_ln_mean_head_varlen_plan": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),

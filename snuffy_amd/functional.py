@@ -47,6 +47,13 @@ FP32_SHARED_NORM = True
 # (ops.mfma_attn_dk192_supported); False: such layers make fp32 copies of Q and V for the exact-fp32 kernel, as before.  Ships off: the
 # route has not been timed against the one of before yet (tools/attn_dk192_time.py writes profiles/attn_dk192.txt; on once it wins there)
 MFMA_ATTN_DK192 = False
+# bf16 inference of a single bag at head width 256 (the README's SimCLR ResNet-18 recipe: D = 512, h = 2, Lambda = 900) on the bf16
+# MFMA kernel of that width (ops.mfma_attn_dk256_supported: up to 8 chunks of 128 keys); False: such layers make fp32 copies of Q and V
+# for the exact-fp32 kernel, as before.  Ships off under the rule "on only if no row is behind": profiles/attn_dk256.txt
+# (tools/attn_dk256_time.py) has the whole forward at 0.81 - 0.84x that route at N = 8000 (eight key chunks at Lambda = 900: a statistics
+# and a main launch each, on 500 row tiles) and at 1.06 - 1.15x at N = 32768.  The packed route (packed.PACK_DK256) does not consult this
+# switch.
+MFMA_ATTN_DK256 = False
 # fp32 inference of a single bag at head width 192 on the FUSED fp32-class kernel of that width (ops.x3_attn_dk192_supported: up to 8
 # chunks of 128 keys, no materialised [h, n, k] probabilities); False: the unfused score / pooling pair (ops.sparse_attn_fwd_x3u), as
 # before.  Ships off: on only if no row of profiles/x3_dk192.txt (tools/x3_dk192_time.py) is behind the pair.  The packed route
@@ -646,6 +653,7 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
                                  "kernel" % (k, ragged.kmax, d // h))
     elif packed is not None and (kb < 1 or not (ops.varlen_attn_chunks_supported(precision, kb, packed_head_pad(d // h) or d // h)
                                                or (precision == "bf16" and d == 192 * h and ops.varlen_attn_dk192_supported(kb))
+                                               or (precision == "bf16" and d == 256 * h and ops.varlen_attn_dk256_supported(kb))
                                                or (precision == "fp32" and d == 192 * h and ops.varlen_attn_x3_dk192_supported(kb))
                                                or (precision == "fp32" and d == 256 * h and ops.varlen_attn_x3_dk256_supported(kb)))):
         raise SnuffyHipError("packed bags: %d keys per bag at head width %d is outside the varlen attention kernels" % (kb, d // h))
@@ -830,7 +838,11 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
     # forms (ops.varlen_attn_dk192_supported, admitted above), whatever MFMA_ATTN_DK192 says about the single bag
     dk192 = (MFMA_ATTN_DK192 and dkp == 192 and ragged is None and packed is None
              and ops.mfma_attn_dk192_supported(k, n, qv.stride(0)))
-    if ragged is None and (packed is not None or dk192 or ops.mfma_attn_supported(k, dkp, n, qv.stride(0))):
+    # dk = 256 (the README's SimCLR ResNet-18 recipe, D = 512 with h = 2) likewise: a kernel of its own behind MFMA_ATTN_DK256, the varlen
+    # forms (ops.varlen_attn_dk256_supported) for packed bags whatever that switch says
+    dk256 = (MFMA_ATTN_DK256 and dkp == 256 and ragged is None and packed is None
+             and ops.mfma_attn_dk256_supported(k, n, qv.stride(0)))
+    if ragged is None and (packed is not None or dk192 or dk256 or ops.mfma_attn_supported(k, dkp, n, qv.stride(0))):
         # keys = RAW selected rows: the gather also leaves them in bf16, the projection runs like Q | V (bf16 operands,
         # fp32 accumulate, bf16 out) and the attention kernel reads Kp as it is
         xs, slot, xs16 = ops.gather_slot_map(x2, sel, bf16_copy=True)               # snuffy.py:131,145-147 (+ row -> slot map)
@@ -844,6 +856,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             kp = torch.addmm(fw["bk"], xs16, fw["wk"].t())
         if packed is not None:
             o, attn, _ = ops.sparse_attn_fwd_mfma_varlen(q, v, kp, packed, kb, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
+        elif dk256:
+            o, attn, _ = ops.sparse_attn_fwd_mfma_dk256(q, v, kp, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
         else:
             o, attn, _ = ops.sparse_attn_fwd_mfma(q, v, kp, n, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
     else:

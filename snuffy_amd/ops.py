@@ -761,6 +761,48 @@ def mfma_attn_dk192_supported(k, n=None, ld=None):
     return True
 
 
+def mfma_attn_dk256_supported(k, n=None, ld=None):
+    """Shapes the bf16 MFMA attention takes at head width 256 (snf_sparse_attn_fwd_mfma_dk256; the README's SimCLR ResNet-18 recipe:
+    D = 512, h = 2, Lambda = 900), forward only: one launch holds 128 keys, up to 8 key chunks.  n / ld as in mfma_attn_supported.
+    mfma_attn_supported() keeps answering for dk = 64 / 128 only."""
+    if not 1 <= k <= 8 * 128:
+        return False
+    if n is not None and (n > 0xffff00 or (ld is not None and (ld >= (1 << 24) or n * ld >= 0x7fffffff))):
+        return False
+    return True
+
+
+def sparse_attn_fwd_mfma_dk256(q, v, kp, h, scale=None, need_attn=False, need_lse=False):
+    """bf16 sparse attention on the matrix cores at head width 256 (snf_sparse_attn_fwd_mfma_dk256): q, v [n, 256 h] bf16 (row-strided
+    views allowed: the halves of a fused [Q | V] projection), kp [k, 256 h] f32 or bf16 (the same bits either way)
+    -> (out [k, d] f32, attn [h, n, k] or None, lse [h, n] or None).  Inference only."""
+    if q.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise TypeError("sparse_attn_fwd_mfma_dk256: q and v must be bfloat16")
+    q = _rows16(q, "q")
+    v = _rows16(v, "v")
+    if kp.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("sparse_attn_fwd_mfma_dk256: kp must be float32 or bfloat16")
+    kp = _req(kp, kp.dtype, "kp", 2)
+    n, d = q.shape
+    k = kp.shape[0]
+    if h < 1 or d != 256 * h or kp.shape[1] != d or v.shape != q.shape:
+        raise _ffi.SnuffyHipError("sparse_attn_fwd_mfma_dk256: inconsistent shapes q %s v %s kp %s h %d (d_model must be 256 h)"
+                                  % (tuple(q.shape), tuple(v.shape), tuple(kp.shape), h))
+    scale = 1.0 / math.sqrt(256) if scale is None else scale
+    lib = _ffi.load()
+    wsb = lib.snf_sparse_attn_fwd_mfma_dk256_workspace_bytes(n, k, h)
+    if wsb == 0:
+        raise _ffi.SnuffyHipError("sparse_attn_fwd_mfma_dk256: unsupported shape n=%d k=%d h=%d (1 <= k <= 1024)" % (n, k, h))
+    out = torch.empty(k, d, dtype=torch.float32, device=q.device)
+    attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
+    lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
+    ws = _ws(wsb, q.device)
+    kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
+    check(lib.snf_sparse_attn_fwd_mfma_dk256(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, n, k, h, float(scale), _p(out), _p(attn),
+                                             _p(lse), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_mfma_dk256")
+    return out, attn, lse
+
+
 def mfma_attn_dropout_supported(k, dk):
     """One key chunk of the in-kernel Philox dropout (forward and the single-launch MFMA backward); more keys, up to 8 chunks:
     mfma_attn_train_chunks_supported."""
@@ -1112,8 +1154,8 @@ class PackedBags:
 
     def plan(self, kind, *shape):
         """(device table int32, workspace bytes) of a segmented launch: kind in {"mfma", "x3", "head"}; the key-chunked attention
-        plans "mfma_chunks" / "x3_chunks", the head-width-192 plans "mfma_dk192" / "x3_dk192" and the head-width-256 plan "x3_dk256"
-        (shape = (k, h)) add (chunk count, keys per chunk)."""
+        plans "mfma_chunks" / "x3_chunks", the head-width-192 plans "mfma_dk192" / "x3_dk192" and the head-width-256 plans "mfma_dk256" /
+        "x3_dk256" (shape = (k, h)) add (chunk count, keys per chunk)."""
         import numpy as np
         key = (kind,) + tuple(shape)
         hit = self._plans.get(key)
@@ -1124,7 +1166,7 @@ class PackedBags:
         fn = {"mfma": lib.snf_sparse_attn_varlen_plan, "x3": lib.snf_sparse_attn_x3_varlen_plan,
               "mfma_chunks": lib.snf_sparse_attn_varlen_chunked_plan, "x3_chunks": lib.snf_sparse_attn_x3_varlen_chunked_plan,
               "mfma_dk192": lib.snf_sparse_attn_varlen_dk192_plan, "x3_dk192": lib.snf_sparse_attn_x3_varlen_dk192_plan,
-              "x3_dk256": lib.snf_sparse_attn_x3_varlen_dk256_plan, "head": lib.snf_ln_mean_head_varlen_plan}[kind]
+              "mfma_dk256": lib.snf_sparse_attn_varlen_dk256_plan, "x3_dk256": lib.snf_sparse_attn_x3_varlen_dk256_plan, "head": lib.snf_ln_mean_head_varlen_plan}[kind]
         chunks = (ctypes.c_int(0), ctypes.c_int(0)) if kind.endswith(("_chunks", "_dk192", "_dk256")) else ()
         extra = tuple(ctypes.byref(c) for c in chunks)
         check(fn(self._host_ptr(), self.bags, *shape, None, 0, ctypes.byref(need), ctypes.byref(wsb), *extra), "varlen plan (%s)" % kind)
@@ -1215,6 +1257,12 @@ def varlen_attn_dk192_supported(k):
     return 1 <= k <= 8 * 128
 
 
+def varlen_attn_dk256_supported(k):
+    """The bf16 varlen attention at head width 256 (snf_sparse_attn_fwd_mfma_varlen_dk256; the README's SimCLR ResNet-18 recipe D = 512,
+    h = 2): one launch holds 128 keys, up to 8 key chunks.  The older varlen predicates keep answering for dk = 64 / 128 only."""
+    return 1 <= k <= 8 * 128
+
+
 def varlen_attn_x3_dk192_supported(k):
     """The fp32-class varlen attention at head width 192 (snf_sparse_attn_fwd_x3_varlen_dk192): one launch holds 128 keys, up to 8 key
     chunks.  The older varlen predicates keep answering for dk = 64 / 128 only."""
@@ -1247,7 +1295,8 @@ def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fa
     does not depend on what it is packed with (bit for bit); against sparse_attn_fwd_mfma() bag by bag P / lse are identical and
     O differs by the fp32 order of the partial sums only (small bags get more rows per workgroup here).  k above one key chunk
     (varlen_attn_chunks_supported) runs as the key chunks of sparse_attn_fwd_mfma(), with the same guarantees.  Head width 192
-    (varlen_attn_dk192_supported) has an entry point of its own, snf_sparse_attn_fwd_mfma_varlen_dk192: 128 keys per chunk."""
+    (varlen_attn_dk192_supported) has an entry point of its own, snf_sparse_attn_fwd_mfma_varlen_dk192: 128 keys per chunk; head width
+    256 (varlen_attn_dk256_supported) likewise, snf_sparse_attn_fwd_mfma_varlen_dk256, the chunks of sparse_attn_fwd_mfma_dk256()."""
     if q.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
         raise TypeError("sparse_attn_fwd_mfma_varlen: q and v must be bfloat16")
     q = _rows16(q, "q")
@@ -1262,7 +1311,7 @@ def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fa
     dk = d // h
     scale = 1.0 / math.sqrt(dk) if scale is None else scale
     chunked = not varlen_attn_supported("bf16", k, dk)
-    table, wsb = (packed.plan("mfma_dk192", k, h) if dk == 192 else packed.plan("mfma_chunks" if chunked else "mfma", k, h, dk))[:2]
+    table, wsb = (packed.plan("mfma_dk%d" % dk, k, h) if dk in (192, 256) else packed.plan("mfma_chunks" if chunked else "mfma", k, h, dk))[:2]
     ws = _ws(wsb, q.device)
     out = torch.empty(packed.bags * k, d, dtype=torch.float32, device=q.device)
     attn = torch.empty(h, t, k, dtype=torch.float32, device=q.device) if need_attn else None
@@ -1273,6 +1322,11 @@ def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fa
         check(lib.snf_sparse_attn_fwd_mfma_varlen_dk192(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(),
                                                         packed.bags, k, h, float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws),
                                                         wsb, _stream()), "snf_sparse_attn_fwd_mfma_varlen_dk192")
+        return out, attn, lse
+    if dk == 256:
+        check(lib.snf_sparse_attn_fwd_mfma_varlen_dk256(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(),
+                                                        packed.bags, k, h, float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws),
+                                                        wsb, _stream()), "snf_sparse_attn_fwd_mfma_varlen_dk256")
         return out, attn, lse
     fn = lib.snf_sparse_attn_fwd_mfma_varlen_chunked if chunked else lib.snf_sparse_attn_fwd_mfma_varlen
     check(fn(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(), packed.bags, k, h, dk, float(scale), _p(out),

@@ -43,6 +43,14 @@ PACK_X3_DK192 = False
 # CAMELYON16-shaped mix 1.14 - 1.23x, host draws and device sampler, return_attention off and on -- no row behind the loop, so no length
 # gate in x3_dk256_ok.  Independent of functional.X3_ATTN_DK256, which routes the single bag (and stays off).
 PACK_X3_DK256 = True
+# Uniform groups of the bf16 model at head width 256 (the same recipe in precision="bf16", one encoder layer) on the varlen forms of the
+# bf16 kernel of that width (ops.varlen_attn_dk256_supported: up to 8 chunks of 128 keys).  False: such bags take the per-bag loop (or the
+# ragged kernel where it takes them), the routing of before, call for call.  The rule of PACK_KEY_CHUNKS decides the value: on only where
+# the packed route is at least level with the loop at every row of profiles/attn_dk256.txt (tools/attn_dk256_time.py).  On: 64 x 1000
+# patches 5.80 - 6.74x, 64 x 8000 1.58 - 1.78x, the synthetic CAMELYON16-shaped mix 1.51 - 1.71x, host draws and device sampler,
+# return_attention off and on -- no row behind the loop, so no length gate in dk256_ok.  Independent of functional.MFMA_ATTN_DK256, which
+# routes the single bag (and stays off), and of PACK_X3_DK256 (fp32).
+PACK_DK256 = True
 RAGGED_MAX_ROWS = 4096      # longest bag the ragged (exact fp32, one workgroup per bag and head) attention is meant for
 
 
@@ -53,7 +61,7 @@ def pack_groups(net, bags):
     False): every bag has at least Lambda patches, so all select the same K rows, and the head width is one the MFMA kernels
     take -- varlen forms of the bf16 / fp32-class attention kernels (with PACK_KEY_CHUNKS also Lambda above one key chunk and head widths
     between the kernels', zero-padded; with PACK_DK192 also the bf16 model at head width 192, up to 8 chunks of 128 keys -- fp32 at that
-    width packs behind PACK_X3_DK192, fp32 at head width 256 behind PACK_X3_DK256, and stays per bag without it).  "ragged" groups: bags shorter than Lambda (they select
+    width packs behind PACK_X3_DK192, fp32 at head width 256 behind PACK_X3_DK256, bf16 at that width behind PACK_DK256, and stays per bag without it).  "ragged" groups: bags shorter than Lambda (they select
     ALL their rows, snuffy.py:129) or head widths outside the MFMA kernels (the MIL benchmark sets: D = 166 / 230, h = 2) --
     exact-fp32 ragged attention, bags of at most _RAGGED_MAX_ROWS patches.  With a random share the draws of the reference
     sampler must stay in bag order, so only one uniform group over all bags is formed.  With the device sampler
@@ -93,7 +101,7 @@ def pack_groups(net, bags):
     uniform_dims = (d % 4 == 0 and (SF.ops.varlen_attn_supported(cfg.compute, k1 + k2, d // h)
                                     or key_chunks_ok(layers, cfg.compute, d, h, k1 + k2, len(bags), sum(sizes))
                                     or dk192_ok(cfg.compute, d, h, k1 + k2) or x3_dk192_ok(cfg.compute, d, h, k1 + k2)
-                                    or x3_dk256_ok(cfg.compute, d, h, k1 + k2))
+                                    or dk256_ok(cfg.compute, d, h, k1 + k2) or x3_dk256_ok(cfg.compute, d, h, k1 + k2))
                     and (cfg.compute == "bf16" or SF.FP32_ATTENTION == "x3"))
     on_device = k2 > 0 and device_draws(cfg) and SF.ops.draw_packed_supported(min(max(sizes), 65536), k1, k2, len(layers))
     if k2 > 0 and not on_device:
@@ -120,6 +128,12 @@ def dk192_ok(compute, d, h, k):
     """PACK_DK192: the bf16 model at head width 192 with a key count inside the dk = 192 varlen kernels.  precision="fp32" stays per
     bag whatever THIS switch: its packed route at this width is the fused fp32-class kernel behind PACK_X3_DK192 (x3_dk192_ok)."""
     return bool(PACK_DK192 and compute == "bf16" and h >= 1 and d == 192 * h and SF.ops.varlen_attn_dk192_supported(k))
+
+
+def dk256_ok(compute, d, h, k):
+    """PACK_DK256: the bf16 model at head width 256 with a key count inside the dk = 256 bf16 varlen kernels.  precision="fp32" is not
+    THIS switch's: its packed route at this width is the fused fp32-class kernel behind PACK_X3_DK256 (x3_dk256_ok)."""
+    return bool(PACK_DK256 and compute == "bf16" and h >= 1 and d == 256 * h and SF.ops.varlen_attn_dk256_supported(k))
 
 
 def x3_dk192_ok(compute, d, h, k):
@@ -193,7 +207,7 @@ def forward_bags(net, bags):
     run over the packed rows (a library / tile choice that depends on the row count): logits move by fp32 / bf16 rounding.
     Bags that select different numbers of rows (shorter than Lambda) or whose head width the MFMA kernels do not take are
     packed as a second, "ragged" group (pack_groups); head width 192 (D = 768, h = 4) packs in bf16 behind PACK_DK192 and
-    in fp32 behind PACK_X3_DK192 (off: per bag), head width 256 (D = 512, h = 2) in fp32 behind PACK_X3_DK256; whatever cannot be packed (training, multiclass critic, ...) takes
+    in fp32 behind PACK_X3_DK192 (off: per bag), head width 256 (D = 512, h = 2) in fp32 behind PACK_X3_DK256 and in bf16 behind PACK_DK256; whatever cannot be packed (training, multiclass critic, ...) takes
     the per-bag loop."""
     bags = list(bags)
     groups = pack_groups(net, bags)
