@@ -184,36 +184,9 @@ SIGNATURES = {
     "snf_sparse_attn_fwd_mfma_varlen_chunked": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
                                                         c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                         c_size_t, c_void_p]),
-    "snf_sparse_attn_varlen_dk192_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
-                                                  c_void_p]),
-    "snf_sparse_attn_fwd_mfma_varlen_dk192": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
-                                                      c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                                      c_void_p]),
     "snf_sparse_attn_x3_varlen_chunked_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                                        c_void_p, c_void_p]),
     "snf_sparse_attn_fwd_x3_varlen_chunked": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int,
-                                                      c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                                      c_void_p]),
-    "snf_sparse_attn_fwd_x3_dk192_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
-    "snf_sparse_attn_fwd_x3_dk192": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_float,
-                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "snf_sparse_attn_x3_varlen_dk192_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
-                                                     c_void_p]),
-    "snf_sparse_attn_fwd_x3_varlen_dk192": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int,
-                                                    c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "snf_sparse_attn_fwd_x3_dk256_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
-    "snf_sparse_attn_fwd_x3_dk256": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_float,
-                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "snf_sparse_attn_x3_varlen_dk256_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
-                                                     c_void_p]),
-    "snf_sparse_attn_fwd_x3_varlen_dk256": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int,
-                                                    c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "snf_sparse_attn_fwd_mfma_dk256_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
-    "snf_sparse_attn_fwd_mfma_dk256": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_float,
-                                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "snf_sparse_attn_varlen_dk256_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
-                                                  c_void_p]),
-    "snf_sparse_attn_fwd_mfma_varlen_dk256": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
                                                       c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                                       c_void_p]),
     "snf_sparse_attn_fwd_ragged_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
@@ -251,6 +224,26 @@ SIGNATURES = {
     "snf_vit_attention_mfma": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "snf_vit_attention_x3_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
 }
+
+# The entry points of the native head widths (csrc/attn_width.h): one workspace and one varlen-plan signature for both families, one
+# single-bag and one varlen forward per family (the bf16 ones take the Kp dtype).  bf16 at 192 has the varlen pair only: its single
+# bag goes through snf_sparse_attn_fwd_mfma.
+_WIDE_WORKSPACE = (c_size_t, [c_int64, c_int, c_int])
+_WIDE_PLAN = (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p])
+_WIDE_TAIL = [c_float, c_void_p, c_void_p, c_void_p]                                       # scale, out, attn, lse
+_WIDE_BAG = [c_int64, c_int, c_int] + _WIDE_TAIL + [c_void_p, c_size_t, c_void_p]          # n, k, h, ..., workspace, bytes, stream
+_WIDE_VARLEN = [c_void_p, c_int, c_int, c_int] + _WIDE_TAIL + [c_void_p, c_void_p, c_size_t, c_void_p]   # offsets, bags, k, h, ..., table
+_WIDE_QVKP = [c_void_p, c_int64, c_void_p, c_int64, c_void_p]
+for _dk in (192, 256):
+    SIGNATURES.update({
+        "snf_sparse_attn_fwd_x3_dk%d_workspace_bytes" % _dk: _WIDE_WORKSPACE,
+        "snf_sparse_attn_fwd_x3_dk%d" % _dk: (c_int, _WIDE_QVKP + _WIDE_BAG),
+        "snf_sparse_attn_x3_varlen_dk%d_plan" % _dk: _WIDE_PLAN,
+        "snf_sparse_attn_fwd_x3_varlen_dk%d" % _dk: (c_int, _WIDE_QVKP + _WIDE_VARLEN),
+        "snf_sparse_attn_varlen_dk%d_plan" % _dk: _WIDE_PLAN,
+        "snf_sparse_attn_fwd_mfma_varlen_dk%d" % _dk: (c_int, _WIDE_QVKP + [c_int] + _WIDE_VARLEN)})
+SIGNATURES.update({"snf_sparse_attn_fwd_mfma_dk256_workspace_bytes": _WIDE_WORKSPACE,
+                   "snf_sparse_attn_fwd_mfma_dk256": (c_int, _WIDE_QVKP + [c_int] + _WIDE_BAG)})
 
 _lib = None
 

@@ -6,7 +6,7 @@
 // is a member of the family description F (a plain struct, no virtual call, nothing on the heap):
 //   using Params, Kp        AttnParams | X3Params; element type of the Kp the kernels read (bf16 bits | float)
 //   int dk                  head width
-//   chunks(k, Chunks*)      the family's chunk rule (make_chunks | x3_chunks | x3w_chunks: they differ on purpose)
+//   chunks(k, Chunks*)      the family's chunk rule (make_chunks | x3_chunks | width_chunks of attn_width.h: they differ on purpose)
 //   plan(n, kc, pl, packed) geometry of one launch of kc keys over n rows (packed: a bag inside a varlen launch)
 //   built(chunked, nkb)     is a varlen launch at this key-block count instantiated?  64/128: asked of chunked launches only;
 //                           bf16 192: asked of a single chunk too

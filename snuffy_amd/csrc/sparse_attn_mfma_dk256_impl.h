@@ -34,12 +34,16 @@
 //            tiles ahead into registers and written one tile ahead while the current tile's P is published.
 // Register and scratch figures of every form: DESIGN.md section 4, tests/test_attn_dk256_host.py.
 #include "sparse_attn_mfma_impl.h"
+#include "attn_width.h"
+
+namespace snf {
+// sparse_attn_mfma_dk256_chunks.hip: one chunk's statistics pass (mode 1) or main pass (mode 2), single bag (P.vl null) or varlen
+int attn_dk256_launch_chunk(int mode, const snf_attn::AttnParams& P, const snf_attn::TilePlan& pl, float* out, hipStream_t s);
+}  // namespace snf
 
 namespace {
 
-constexpr int A256_DK = 256;
-constexpr int A256_KMAX = 128;        // keys per launch
-constexpr int A256_MAX_CHUNKS = 8;
+constexpr int A256_DK = 256;          // 128 keys per launch, up to 8 chunks: A256 below
 constexpr int A256_ROWS = 32;         // query rows per tile (one 32-row block)
 constexpr int A256_WAVES = 4, A256_THREADS = 64 * A256_WAVES;
 
@@ -387,59 +391,40 @@ __global__ __launch_bounds__(A256_THREADS, 1) void sparse_attn_mfma_dk256_kernel
     if constexpr (MODE != 1) flush(cur_head);
 }
 
-// geometry of one launch of kc <= 128 keys: key blocks 1, 2, 4; 32-row tiles.  A bag inside a packed launch takes 32 tiles (1024 rows)
-// per workgroup WHATEVER its length, as at the fp32-class kernel of this width: a workgroup's partial tiles are 128 KiB per head segment
-// and key chunk (4 key blocks, fp32 whatever the operands), written once and read once by the reduction, while the bf16 Q and V rows of a
-// tile are 32 KiB -- half the fp32-class figure, so the balance is worse here: at 1024 rows the partial traffic is a quarter of the
-// operand traffic, at the single-bag plan (two tiles per workgroup at 8000 rows) it would be four times the operand traffic.
-inline bool a256_plan(int64_t n, int kc, int h, Plan* pl, bool packed = false) {
-    if (kc < 1 || kc > A256_KMAX || n < 1 || h < 1) return false;
-    if (n > 0xffff00ll) return false;   // the family's row limit (32-bit element offsets)
-    const int need = (kc + 31) / 32;
-    pl->nkb = need <= 1 ? 1 : need <= 2 ? 2 : 4;
-    constexpr int PACKED_TILES = 1024 / A256_ROWS;
-    if (!snf_attn::make_tile_plan(n, h, A256_ROWS, PACKED_TILES, packed, pl)) return false;
-    if (packed) {
-        const int tph = pl->tiles_per_head, tpw = tph < PACKED_TILES ? tph : PACKED_TILES;
-        pl->tiles_per_wg = tpw;
-        pl->num_wg = (pl->total_tiles + tpw - 1) / tpw;
-        pl->seg_count = (tpw + tph - 1) / tph + 1;
+// The width as attn_width.h sees it: 32-row tiles, the family's chunk rule (make_chunks: ceil(k / 128) near-equal chunks, no rounding)
+// at 128 keys per launch.  count >= 2: k > 128 (count - 1), so size >= 65 (3 or 4 blocks -> 4) and the last chunk k - (count - 1) size
+// holds more than 64 - count keys (2, 3 or 4 blocks -> 2 or 4): chunked launches run at 2 or 4 key blocks.
+// A bag inside a packed launch takes 32 tiles (1024 rows) per workgroup WHATEVER its length, as at the fp32-class kernel of this width:
+// a workgroup's partial tiles are 128 KiB per head segment and key chunk (4 key blocks, fp32 whatever the operands), written once and
+// read once by the reduction, while the bf16 Q and V rows of a tile are 32 KiB -- half the fp32-class figure, so the balance is worse
+// here: at 1024 rows the partial traffic is a quarter of the operand traffic, at the single-bag plan (two tiles per workgroup at 8000
+// rows) it would be four times the operand traffic.
+struct A256 {
+    using Drive = MfmaDrive;
+    static constexpr int DK = A256_DK, ROWS = A256_ROWS, THREADS = A256_THREADS;
+    static constexpr int KMAX = 128, MAX_CHUNKS = 8, CHUNK_MULTIPLE = 1;
+    static constexpr int64_t MAX_ROWS = 0xffff00ll;   // the family's row limit (32-bit element offsets)
+    static constexpr int PACKED_TILES = 1024 / A256_ROWS;
+    static constexpr bool PACKED_FORCED = true;
+    static constexpr const char *DK_TEXT = "256", *NAME = "sparse_attn_mfma_dk256", *KERNEL = "sparse_attn_mfma_dk256_kernel";
+    static constexpr int lds_bytes(int nkb) { return a256_lds_bytes(nkb); }
+    template <int NKB, bool AUX, int MODE, bool VL>
+    static auto kernel() { return sparse_attn_mfma_dk256_kernel<NKB, AUX, MODE, VL>; }
+    static int launch_chunk(int mode, const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
+        return snf::attn_dk256_launch_chunk(mode, P, pl, out, s);
     }
-    return true;
-}
-// the family's chunk rule (make_chunks) at 128 keys per launch: count = ceil(k / 128) near-equal chunks of ceil(k / count) keys.
-// count >= 2: k > 128 (count - 1), so size >= 65 (3 or 4 blocks -> 4) and the last chunk k - (count - 1) size holds more than
-// 64 - count keys (2, 3 or 4 blocks -> 2 or 4): chunked launches run at 2 or 4 key blocks
-inline bool a256_chunks(int k, Chunks* c) {
-    if (k < 1 || k > A256_MAX_CHUNKS * A256_KMAX) return false;
-    c->count = (k + A256_KMAX - 1) / A256_KMAX;
-    c->size = (k + c->count - 1) / c->count;
-    return true;
-}
-constexpr bool a256_built(bool chunked, int nkb) { return nkb == 2 || nkb == 4 || (nkb == 1 && !chunked); }
-
-template <int NKB, bool AUX, int MODE, bool VL>
-int a256_launch(const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
-    constexpr int DK = A256_DK;
-    constexpr int lds = a256_lds_bytes(NKB);
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = sparse_attn_mfma_dk256_kernel<NKB, AUX, MODE, VL>;
-    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "sparse_attn_mfma_dk256")) return rc;
-    hipLaunchKernelGGL(kern, dim3(pl.num_wg), dim3(A256_THREADS), lds, s, P);
-    int rc = snf::check_launch("sparse_attn_mfma_dk256_kernel");
-    if (rc || MODE == 1) return rc;
-    constexpr int TILES = NKB * (DK / 32);
-    if (VL && P.out_direct && pl.tiles_per_head == -1) return SNF_OK;   // every bag stored its heads itself
-    hipLaunchKernelGGL((reduce_partials_kernel<DK, NKB>), dim3(TILES * 4, P.h, VL ? P.vl_bags : 1), dim3(64), 0, s, P.partial, pl.num_wg,
-                       pl.seg_count, pl.tiles_per_head, pl.tiles_per_wg, pl.total_tiles, P.k, P.h, out, VL ? P.vl : nullptr,
-                       (VL && P.out_direct) ? 1 : 0);
-    return snf::check_launch("reduce_partials_kernel");
-}
+    // the wording of the entry points: k < 1, h < 1 are an unsupported shape to the varlen plan, which words the refusal of a short
+    // table itself
+    static constexpr bool SHORT_TABLE_UNSUPPORTED = true;
+    static bool plan_args_ok(int bags, int, int) { return bags >= 1; }
+    static bool varlen_shape_ok(int bags, int k, int h) { return bags >= 1 && k >= 1 && h >= 1; }
+    static void refuse_bag(const char* me, int64_t n, int k) {
+        snf::set_error("%s: unsupported shape n=%lld k=%d (k <= %d = %d chunks of %d)", me, (long long)n, k, MAX_CHUNKS * KMAX, MAX_CHUNKS, KMAX);
+    }
+    static void refuse_plan(const char* me, int bags, int k, int h) {
+        snf::set_error("%s: unsupported shape (bags=%d k=%d h=%d: need 1 <= k <= %d = %d chunks of %d, h >= 1, non-empty bags)", me, bags, k, h,
+                       MAX_CHUNKS * KMAX, MAX_CHUNKS, KMAX);
+    }
+};
 
 }  // namespace
-
-namespace snf {
-// sparse_attn_mfma_dk256_chunks.hip: one chunk's statistics pass (mode 1) or main pass (mode 2), single bag (P.vl null) or varlen
-int attn_dk256_launch_chunk(int mode, const snf_attn::AttnParams& P, const snf_attn::TilePlan& pl, float* out, hipStream_t s);
-}  // namespace snf

@@ -1174,6 +1174,23 @@ struct MfmaDrive {
         P.stats = (stats_pass || count == 1) ? nullptr : stats;
         P.stats_out = stats_pass ? stats + (size_t)c * P.h * P.n_stride * 2 : nullptr;
     }
+    // ---- what the native-width shell (attn_width.h) asks of a family ----
+    using In = void;                        // Q | V bf16 bits, Kp f32 | bf16 by kp_dtype
+    static constexpr int ROW_ALIGN = 8;     // elements per 16 bytes of a Q | V row
+    // the Kp dtype of an inference entry point: no dropout, no trace
+    static int open(const char* me, int kp_dtype, AttnParams& P, bool* kp_f32) {
+        SNF_REQUIRE(kp_dtype == SNF_DT_F32 || kp_dtype == SNF_DT_BF16, "%s: bad kp dtype %d", me, kp_dtype);
+        P.trace = nullptr, P.trace_wg = 0, P.drop = snf::make_dropout(0.f, 0, 0);
+        return *kp_f32 = kp_dtype == SNF_DT_F32, SNF_OK;
+    }
+    // the reduction pass behind a main launch
+    template <int DK, int NKB>
+    static int reduce(const AttnParams& P, const Plan& pl, float* out, bool vl, hipStream_t s) {
+        hipLaunchKernelGGL((reduce_partials_kernel<DK, NKB>), dim3(NKB * (DK / 32) * 4, P.h, vl ? P.vl_bags : 1), dim3(64), 0, s, P.partial,
+                           pl.num_wg, pl.seg_count, pl.tiles_per_head, pl.tiles_per_wg, pl.total_tiles, P.k, P.h, out, vl ? P.vl : nullptr,
+                           (vl && P.out_direct) ? 1 : 0);
+        return snf::check_launch("reduce_partials_kernel");
+    }
 };
 
 }  // namespace

@@ -6,10 +6,11 @@
 #define SNF_ATTN_MFMA_KERNEL sparse_attn_mfma_vl192_kernel
 #define SNF_ATTN_STATS_KERNEL sparse_attn_stats_vl192_kernel
 #include "sparse_attn_mfma_impl.h"
+#include "attn_width.h"
 
 namespace {
 
-using namespace snf_attn;   // the driver (attn_drive.h)
+using namespace snf_attn;   // the driver (attn_drive.h) and the entry bodies (attn_width.h)
 constexpr int DK = 192;
 using QT = unsigned short;   // bf16 Q | V
 
@@ -63,19 +64,31 @@ struct Vl192 : MfmaDrive {
     bool built(bool chunked, int nkb) const { return vl192_built(chunked, nkb); }   // asked of a single chunk too
 };
 
+// What the entry bodies of attn_width.h ask: the family, the kernel switch above and the wording of the two entry points
+struct E {
+    using Family = Vl192;
+    static constexpr int MAX_CHUNKS = ::MAX_CHUNKS;
+    static constexpr bool SHORT_TABLE_UNSUPPORTED = false;
+    static bool plan_args_ok(int bags, int k, int h) { return bags >= 1 && k >= 1 && h >= 1; }
+    static bool varlen_shape_ok(int, int k, int h) { return k >= 1 && h >= 1; }
+    static void refuse_plan(const char* me, int bags, int k, int) {
+        snf::set_error("%s: unsupported shape (bags=%d k=%d: need k <= %d = %d chunks of %d, non-empty bags)", me, bags, k,
+                       MAX_CHUNKS * attn_kmax(DK), MAX_CHUNKS, attn_kmax(DK));
+    }
+    template <bool VL>
+    static int pass(bool, bool stats_pass, const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
+        return launch_nkb_vl192(stats_pass, P, pl, out, s);
+    }
+};
+
 }  // namespace
 
 extern "C" {
 
 int snf_sparse_attn_varlen_dk192_plan(const int64_t* offsets, int bags, int k, int h, int32_t* table, size_t table_ints,
                                       size_t* table_ints_needed, size_t* workspace_bytes, int* n_chunks, int* chunk_k) {
-    const char* me = "snf_sparse_attn_varlen_dk192_plan";
-    if (int rc = require(me, offsets && bags >= 1 && k >= 1 && h >= 1, "bad arguments")) return rc;
-    return varlen_plan_reply(me, Vl192{{}, h}, offsets, bags, k, h, MAX_CHUNKS, table, table_ints, table_ints_needed, workspace_bytes, n_chunks,
-                             chunk_k, [&] {
-        snf::set_error("snf_sparse_attn_varlen_dk192_plan: unsupported shape (bags=%d k=%d: need k <= %d = %d chunks of %d, non-empty "
-                       "bags)", bags, k, MAX_CHUNKS * attn_kmax(DK), MAX_CHUNKS, attn_kmax(DK));
-    });
+    return entry_varlen_plan<E>("snf_sparse_attn_varlen_dk192_plan", offsets, bags, k, h, table, table_ints, table_ints_needed,
+                                workspace_bytes, n_chunks, chunk_k);
 }
 
 // layouts as snf_sparse_attn_fwd_mfma_varlen at dk = 192; table_dev / workspace from snf_sparse_attn_varlen_dk192_plan
@@ -83,23 +96,8 @@ int snf_sparse_attn_fwd_mfma_varlen_dk192(const void* q, int64_t ldq, const void
                                           const int64_t* offsets, int bags, int k, int h, float scale, float* out, float* attn,
                                           float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
                                           snf_stream_t stream) {
-    const char* me = "snf_sparse_attn_fwd_mfma_varlen_dk192";
-    if (int rc = require(me, q && v && kp && out && offsets && table_dev, "null pointer")) return rc;
-    SNF_REQUIRE(kp_dtype == SNF_DT_F32 || kp_dtype == SNF_DT_BF16, "snf_sparse_attn_fwd_mfma_varlen_dk192: bad kp dtype %d", kp_dtype);
-    if (int rc = require(me, k >= 1 && h >= 1, "bad shape")) return rc;
-    const Vl192 f{{}, h};
-    VarlenLaunch vl;
-    if (!plan_varlen(f, offsets, bags, k, h, MAX_CHUNKS, &vl, nullptr, 0)) {
-        snf::set_error("snf_sparse_attn_fwd_mfma_varlen_dk192: unsupported shape (bags=%d k=%d)", bags, k);
-        return SNF_EUNSUPPORTED;
-    }
-    AttnParams P;
-    P.trace = nullptr, P.trace_wg = 0, P.drop = snf::make_dropout(0.f, 0, 0);
-    const Operands<void, void> o{q, v, ldq, ldv, 8, kp, kp_dtype == SNF_DT_F32, k, h, scale, out, attn, lse, workspace, workspace_bytes,
-                                 snf::as_stream(stream)};
-    return forward_varlen(me, f, vl, o, offsets, bags, table_dev, P, [&](bool stats_pass, AttnParams& P, const Plan& pl, float* out_c) {
-        return launch_nkb_vl192(stats_pass, P, pl, out_c, o.stream);
-    });
+    return entry_forward_varlen<E>("snf_sparse_attn_fwd_mfma_varlen_dk192", q, ldq, v, ldv, kp, kp_dtype, offsets, bags, k, h, scale, out,
+                                   attn, lse, table_dev, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

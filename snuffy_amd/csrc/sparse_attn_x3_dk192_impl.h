@@ -22,12 +22,16 @@
 //            the softmax and GEMM2 and out of the registers during GEMM1 (the statistics pass, which has the room, fetches two tiles
 //            ahead as the 64 / 128 body does).  Scratch figures of every form: DESIGN.md section 4, tests/test_x3_dk192_host.py.
 #include "sparse_attn_x3_impl.h"
+#include "attn_width.h"
+
+namespace snf {
+// sparse_attn_x3_dk192_chunks.hip: one chunk's statistics pass (mode 1) or main pass (mode 2), single bag (P.vl null) or varlen
+int x3_dk192_launch_chunk(int mode, const snf_attn::X3Params& P, const snf_attn::TilePlan& pl, float* out, hipStream_t s);
+}  // namespace snf
 
 namespace {
 
-constexpr int X3W_DK = 192;
-constexpr int X3W_KMAX = 128;        // keys per launch
-constexpr int X3W_MAX_CHUNKS = 8;
+constexpr int X3W_DK = 192;          // 128 keys per launch, up to 8 chunks: X3Wide
 
 template <int NKB, bool AUX, int MODE, bool VL = false>
 __global__ __launch_bounds__(512, 1) void sparse_attn_x3_dk192_kernel(X3Params PA) {
@@ -436,47 +440,21 @@ __global__ __launch_bounds__(512, 1) void sparse_attn_x3_dk192_kernel(X3Params P
     if constexpr (MODE != 1) flush(cur_head);
 }
 
-// geometry of one launch of kc <= 128 keys: key blocks 1, 2, 4; a bag inside a packed launch takes at least 16 tiles (1024 rows) per
-// workgroup, as in x3_plan
-inline bool x3w_plan(int64_t n, int kc, int h, X3Plan* pl, bool packed = false) {
-    if (kc < 1 || kc > X3W_KMAX || n < 1 || h < 1) return false;
-    const int need = (kc + 31) / 32;
-    pl->nkb = need <= 1 ? 1 : need <= 2 ? 2 : 4;
-    return snf_attn::make_tile_plan(n, h, TROWS, /*small_bag_tiles=*/16, packed, pl);
-}
-// keys per launch: up to 8 chunks of equal size (a multiple of 4).  count >= 2: k > 128 (count - 1), so size >= 68 (3 or 4 blocks -> 4)
-// and the last chunk k - (count - 1) size holds 61 keys at least (2, 3 or 4 blocks -> 2 or 4): chunked launches run at 2 or 4 key blocks
-inline bool x3w_chunks(int k, X3Chunks* c) {
-    if (k < 1 || k > X3W_MAX_CHUNKS * X3W_KMAX) return false;
-    c->count = (k + X3W_KMAX - 1) / X3W_KMAX;
-    c->size = c->count == 1 ? k : ((k + c->count - 1) / c->count + 3) & ~3;
-    return c->size <= X3W_KMAX;
-}
-constexpr bool x3w_chunk_built(int nkb) { return nkb == 2 || nkb == 4; }
-
-template <int NKB, bool AUX, int MODE, bool VL>
-int x3w_launch(const X3Params& P, const X3Plan& pl, float* out, hipStream_t s) {
-    constexpr int DK = X3W_DK, NKS = DK / 16;
-    constexpr int q_bytes = (TROWS / 32) * NKS * 1024, p_bytes = TROWS * p_row_bytes(NKB), v_bytes = TROWS * 2 * DK;
-    constexpr int lds = 2 * q_bytes + 2 * p_bytes + 2 * v_bytes + 8 * TROWS * 8;   // Q hi|lo, P hi|lo, V hi|lo, statistics
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = sparse_attn_x3_dk192_kernel<NKB, AUX, MODE, VL>;
-    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "sparse_attn_x3_dk192")) return rc;
-    hipLaunchKernelGGL(kern, dim3(pl.num_wg), dim3(512), lds, s, P);
-    int rc = snf::check_launch("sparse_attn_x3_dk192_kernel");
-    if (rc || MODE == 1) return rc;
-    constexpr int TILES = NKB * (DK / 32);
-    if (VL && P.out_direct && pl.tiles_per_head == -1) return SNF_OK;   // every bag stored its heads itself
-    hipLaunchKernelGGL((x3_reduce_kernel<DK, NKB>), dim3(TILES * 4, P.h, VL ? P.vl_bags : 1), dim3(64), 0, s, P.partial, pl.num_wg,
-                       pl.seg_count, pl.tiles_per_head, pl.tiles_per_wg, P.k, P.h, out, VL ? P.vl : nullptr,
-                       (VL && P.out_direct) ? 1 : 0);
-    return snf::check_launch("x3_reduce_kernel");
-}
+// The width as attn_width.h sees it.  A bag inside a packed launch takes at least 16 tiles (1024 rows) per workgroup, as in x3_plan
+struct X3W : X3Wide {
+    static constexpr int DK = X3W_DK, ROWS = TROWS, THREADS = 512;
+    static constexpr int PACKED_TILES = 16;
+    static constexpr bool PACKED_FORCED = false;
+    static constexpr const char *DK_TEXT = "192", *NAME = "sparse_attn_x3_dk192", *KERNEL = "sparse_attn_x3_dk192_kernel";
+    // Q hi|lo, P hi|lo, V hi|lo, statistics
+    static constexpr int lds_bytes(int nkb) {
+        return 2 * (TROWS / 32) * (DK / 16) * 1024 + 2 * TROWS * p_row_bytes(nkb) + 2 * TROWS * 2 * DK + 8 * TROWS * 8;
+    }
+    template <int NKB, bool AUX, int MODE, bool VL>
+    static auto kernel() { return sparse_attn_x3_dk192_kernel<NKB, AUX, MODE, VL>; }
+    static int launch_chunk(int mode, const X3Params& P, const X3Plan& pl, float* out, hipStream_t s) {
+        return snf::x3_dk192_launch_chunk(mode, P, pl, out, s);
+    }
+};
 
 }  // namespace
-
-namespace snf {
-// sparse_attn_x3_dk192_chunks.hip: one chunk's statistics pass (mode 1) or main pass (mode 2), single bag (P.vl null) or varlen
-int x3_dk192_launch_chunk(int mode, const snf_attn::X3Params& P, const snf_attn::TilePlan& pl, float* out, hipStream_t s);
-}  // namespace snf

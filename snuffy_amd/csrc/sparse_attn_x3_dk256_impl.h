@@ -31,12 +31,16 @@
 //            one tile ahead while the current tile's P is published; three workgroup barriers per tile.
 // Register and scratch figures of every form: DESIGN.md section 4, tests/test_x3_dk256_host.py.
 #include "sparse_attn_x3_impl.h"
+#include "attn_width.h"
+
+namespace snf {
+// sparse_attn_x3_dk256_chunks.hip: one chunk's statistics pass (mode 1) or main pass (mode 2), single bag (P.vl null) or varlen
+int x3_dk256_launch_chunk(int mode, const snf_attn::X3Params& P, const snf_attn::TilePlan& pl, float* out, hipStream_t s);
+}  // namespace snf
 
 namespace {
 
-constexpr int X3Y_DK = 256;
-constexpr int X3Y_KMAX = 128;        // keys per launch
-constexpr int X3Y_MAX_CHUNKS = 8;
+constexpr int X3Y_DK = 256;          // 128 keys per launch, up to 8 chunks: X3Wide
 constexpr int X3Y_ROWS = 32;         // query rows per tile (one 32-row block)
 constexpr int X3Y_WAVES = 4, X3Y_THREADS = 64 * X3Y_WAVES;
 
@@ -408,57 +412,22 @@ __global__ __launch_bounds__(X3Y_THREADS, 1) void sparse_attn_x3_dk256_kernel(X3
     if constexpr (MODE != 1) flush(cur_head);
 }
 
-// geometry of one launch of kc <= 128 keys: key blocks 1, 2, 4; 32-row tiles.  A bag inside a packed launch takes 32 tiles (1024 rows,
-// as in x3_plan) per workgroup WHATEVER its length: a workgroup's partial tiles are 128 KiB per head segment and key chunk at this width
-// (4 key blocks), written once and read once by the reduction -- as much as the Q and V rows of 32 tiles.  The single-bag plan of
-// make_tile_plan (every CU busy: two tiles per workgroup at 8000 rows) moved eight times the bag's own bytes in partial tiles per chunk
-// when 64 such bags shared a launch; a bag alone keeps that plan, its tiles have the chip to themselves.
-inline bool x3y_plan(int64_t n, int kc, int h, X3Plan* pl, bool packed = false) {
-    if (kc < 1 || kc > X3Y_KMAX || n < 1 || h < 1) return false;
-    const int need = (kc + 31) / 32;
-    pl->nkb = need <= 1 ? 1 : need <= 2 ? 2 : 4;
-    constexpr int PACKED_TILES = 1024 / X3Y_ROWS;
-    if (!snf_attn::make_tile_plan(n, h, X3Y_ROWS, PACKED_TILES, packed, pl)) return false;
-    if (packed) {
-        const int tph = pl->tiles_per_head, tpw = tph < PACKED_TILES ? tph : PACKED_TILES;
-        pl->tiles_per_wg = tpw;
-        pl->num_wg = (pl->total_tiles + tpw - 1) / tpw;
-        pl->seg_count = (tpw + tph - 1) / tph + 1;
+// The width as attn_width.h sees it: 32-row tiles.  A bag inside a packed launch takes 32 tiles (1024 rows, as in x3_plan) per
+// workgroup WHATEVER its length: a workgroup's partial tiles are 128 KiB per head segment and key chunk at this width (4 key blocks),
+// written once and read once by the reduction -- as much as the Q and V rows of 32 tiles.  The single-bag plan of make_tile_plan (every
+// CU busy: two tiles per workgroup at 8000 rows) moved eight times the bag's own bytes in partial tiles per chunk when 64 such bags
+// shared a launch; a bag alone keeps that plan, its tiles have the chip to themselves.
+struct X3Y : X3Wide {
+    static constexpr int DK = X3Y_DK, ROWS = X3Y_ROWS, THREADS = X3Y_THREADS;
+    static constexpr int PACKED_TILES = 1024 / X3Y_ROWS;
+    static constexpr bool PACKED_FORCED = true;
+    static constexpr const char *DK_TEXT = "256", *NAME = "sparse_attn_x3_dk256", *KERNEL = "sparse_attn_x3_dk256_kernel";
+    static constexpr int lds_bytes(int nkb) { return x3y_lds_bytes(nkb); }
+    template <int NKB, bool AUX, int MODE, bool VL>
+    static auto kernel() { return sparse_attn_x3_dk256_kernel<NKB, AUX, MODE, VL>; }
+    static int launch_chunk(int mode, const X3Params& P, const X3Plan& pl, float* out, hipStream_t s) {
+        return snf::x3_dk256_launch_chunk(mode, P, pl, out, s);
     }
-    return true;
-}
-// keys per launch: up to 8 chunks of equal size (a multiple of 4).  count >= 2: k > 128 (count - 1), so size >= 68 (3 or 4 blocks -> 4)
-// and the last chunk k - (count - 1) size holds 61 keys at least (2, 3 or 4 blocks -> 2 or 4): chunked launches run at 2 or 4 key blocks
-inline bool x3y_chunks(int k, X3Chunks* c) {
-    if (k < 1 || k > X3Y_MAX_CHUNKS * X3Y_KMAX) return false;
-    c->count = (k + X3Y_KMAX - 1) / X3Y_KMAX;
-    c->size = c->count == 1 ? k : ((k + c->count - 1) / c->count + 3) & ~3;
-    return c->size <= X3Y_KMAX;
-}
-constexpr bool x3y_chunk_built(int nkb) { return nkb == 2 || nkb == 4; }
-
-template <int NKB, bool AUX, int MODE, bool VL>
-int x3y_launch(const X3Params& P, const X3Plan& pl, float* out, hipStream_t s) {
-    constexpr int DK = X3Y_DK;
-    constexpr int lds = x3y_lds_bytes(NKB);
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = sparse_attn_x3_dk256_kernel<NKB, AUX, MODE, VL>;
-    static thread_local unsigned long long attr_set_mask = 0;   // devices (bit = device id) that have the opt-in
-    if (int rc = snf::lds_opt_in(reinterpret_cast<const void*>(kern), lds, &attr_set_mask, "sparse_attn_x3_dk256")) return rc;
-    hipLaunchKernelGGL(kern, dim3(pl.num_wg), dim3(X3Y_THREADS), lds, s, P);
-    int rc = snf::check_launch("sparse_attn_x3_dk256_kernel");
-    if (rc || MODE == 1) return rc;
-    constexpr int TILES = NKB * (DK / 32);
-    if (VL && P.out_direct && pl.tiles_per_head == -1) return SNF_OK;   // every bag stored its heads itself
-    hipLaunchKernelGGL((x3_reduce_kernel<DK, NKB>), dim3(TILES * 4, P.h, VL ? P.vl_bags : 1), dim3(64), 0, s, P.partial, pl.num_wg,
-                       pl.seg_count, pl.tiles_per_head, pl.tiles_per_wg, P.k, P.h, out, VL ? P.vl : nullptr,
-                       (VL && P.out_direct) ? 1 : 0);
-    return snf::check_launch("x3_reduce_kernel");
-}
+};
 
 }  // namespace
-
-namespace snf {
-// sparse_attn_x3_dk256_chunks.hip: one chunk's statistics pass (mode 1) or main pass (mode 2), single bag (P.vl null) or varlen
-int x3_dk256_launch_chunk(int mode, const snf_attn::X3Params& P, const snf_attn::TilePlan& pl, float* out, hipStream_t s);
-}  // namespace snf

@@ -66,7 +66,7 @@ using snf_attn::VL_DESC;
 using snf_attn::X3Params;
 using snf_attn::p_row_bytes;
 using X3Plan = snf_attn::TilePlan;
-using X3Chunks = snf_attn::Chunks;   // x3_chunks / x3w_chunks: count chunks of size keys
+using X3Chunks = snf_attn::Chunks;   // x3_chunks / width_chunks: count chunks of size keys
 
 constexpr int TROWS = 64;   // query rows per step (two 32-row blocks)
 
@@ -651,6 +651,38 @@ struct X3Drive {
     // statistics [count][h][n_stride] of (max, sum) pairs: MODE 1 writes plane `chunk`, MODE 2 reads them all, MODE 0 none
     static void chunk(X3Params& P, bool, int c, int, int count, void* stats_area) {
         P.stats = reinterpret_cast<f32x2*>(stats_area), P.nchunks = count, P.chunk = c;
+    }
+    // ---- what the native-width shell (attn_width.h) asks of a family ----
+    using In = float;                       // Q | V | Kp as the entry points take them
+    static constexpr int ROW_ALIGN = 4;     // elements per 16 bytes of a Q | V row
+    // the entry points take no Kp dtype: Kp is f32 and read as given
+    static int open(const char*, int, X3Params&, bool* kp_f32) { return *kp_f32 = false, SNF_OK; }
+    // the reduction pass behind a main launch
+    template <int DK, int NKB>
+    static int reduce(const X3Params& P, const X3Plan& pl, float* out, bool vl, hipStream_t s) {
+        hipLaunchKernelGGL((x3_reduce_kernel<DK, NKB>), dim3(NKB * (DK / 32) * 4, P.h, vl ? P.vl_bags : 1), dim3(64), 0, s, P.partial, pl.num_wg,
+                           pl.seg_count, pl.tiles_per_head, pl.tiles_per_wg, P.k, P.h, out, vl ? P.vl : nullptr, (vl && P.out_direct) ? 1 : 0);
+        return snf::check_launch("x3_reduce_kernel");
+    }
+};
+
+// What the native-width kernels of the family (192: sparse_attn_x3_dk192_impl.h, 256: sparse_attn_x3_dk256_impl.h) share of their width
+// description: 128 keys per launch in up to 8 chunks of equal size (a multiple of 4), and how their entry points word a refusal.
+// count >= 2: k > 128 (count - 1), so size >= 68 (3 or 4 blocks -> 4) and the last chunk k - (count - 1) size holds 61 keys at least
+// (2, 3 or 4 blocks -> 2 or 4): chunked launches run at 2 or 4 key blocks
+struct X3Wide {
+    using Drive = X3Drive;
+    static constexpr int KMAX = 128, MAX_CHUNKS = 8, CHUNK_MULTIPLE = 4;
+    static constexpr int64_t MAX_ROWS = INT64_MAX;   // no row limit of the family's own
+    static constexpr bool SHORT_TABLE_UNSUPPORTED = false;
+    static bool plan_args_ok(int bags, int, int h) { return bags >= 1 && h >= 1; }   // k < 1: an unsupported shape there
+    static bool varlen_shape_ok(int bags, int, int h) { return bags >= 1 && h >= 1; }
+    static void refuse_bag(const char* me, int64_t, int k) {
+        snf::set_error("%s: unsupported shape k=%d (k <= %d x %d)", me, k, MAX_CHUNKS, KMAX);
+    }
+    static void refuse_plan(const char* me, int bags, int k, int) {
+        snf::set_error("%s: unsupported shape (bags=%d k=%d: need 1 <= k <= %d = %d chunks of %d, non-empty bags)", me, bags, k,
+                       MAX_CHUNKS * KMAX, MAX_CHUNKS, KMAX);
     }
 };
 

@@ -65,6 +65,27 @@ X3_ATTN_DK192 = False
 # (tools/x3_dk256_time.py) has the fused kernel at 0.76 - 0.88x the pair at N = 8000 / 32768 (eight key chunks at Lambda = 900, GEMM1
 # run twice).  The packed route (packed.PACK_X3_DK256) does not consult this switch.
 X3_ATTN_DK256 = False
+# The native head widths: (precision, head width, switch of the single-bag route, its predicate, its op, predicate of the packed route),
+# all by name -- the switches and ops are looked up when a layer runs.  bf16 at 192 has no op of its own: ops.sparse_attn_fwd_mfma
+# takes the width.  A packed bag asks the last column only (its switches are packed.PACK_*).
+_WIDE = (("fp32", 192, "X3_ATTN_DK192", "x3_attn_dk192_supported", "sparse_attn_fwd_x3_dk192", "varlen_attn_x3_dk192_supported"),
+         ("fp32", 256, "X3_ATTN_DK256", "x3_attn_dk256_supported", "sparse_attn_fwd_x3_dk256", "varlen_attn_x3_dk256_supported"),
+         ("bf16", 192, "MFMA_ATTN_DK192", "mfma_attn_dk192_supported", None, "varlen_attn_dk192_supported"),
+         ("bf16", 256, "MFMA_ATTN_DK256", "mfma_attn_dk256_supported", "sparse_attn_fwd_mfma_dk256", "varlen_attn_dk256_supported"))
+
+
+def _wide_single(precision, d, h, *shape):
+    """The row of _WIDE a single bag of d = width * h takes: its switch is on and its predicate takes shape = (k[, n, ld]); or None."""
+    for row in _WIDE:
+        prec, width, switch, supported = row[:4]
+        if prec == precision and globals()[switch] and d == width * h and getattr(ops, supported)(*shape):
+            return row
+    return None
+
+
+def _wide_varlen_supported(precision, d, h, kb):
+    """A packed bag of kb keys is inside the varlen kernel of a native head width."""
+    return any(prec == precision and d == width * h and getattr(ops, supported)(kb) for prec, width, _, _, _, supported in _WIDE)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -652,10 +673,7 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             raise SnuffyHipError("ragged packed bags: %d keys (max %d per bag) at head width %d is outside the ragged attention "
                                  "kernel" % (k, ragged.kmax, d // h))
     elif packed is not None and (kb < 1 or not (ops.varlen_attn_chunks_supported(precision, kb, packed_head_pad(d // h) or d // h)
-                                               or (precision == "bf16" and d == 192 * h and ops.varlen_attn_dk192_supported(kb))
-                                               or (precision == "bf16" and d == 256 * h and ops.varlen_attn_dk256_supported(kb))
-                                               or (precision == "fp32" and d == 192 * h and ops.varlen_attn_x3_dk192_supported(kb))
-                                               or (precision == "fp32" and d == 256 * h and ops.varlen_attn_x3_dk256_supported(kb)))):
+                                               or _wide_varlen_supported(precision, d, h, kb))):
         raise SnuffyHipError("packed bags: %d keys per bag at head width %d is outside the varlen attention kernels" % (kb, d // h))
     n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
     lq, lk, lv, lo = mha.linears
@@ -737,10 +755,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             o, attn, _ = ops.sparse_attn_fwd_x3_varlen(q, v, kp, packed, kb, h, scale=scale, need_attn=need_attn)
         elif FP32_ATTENTION == "x3" and ops.x3_attn_supported(k, d // h):
             o, attn, _ = ops.sparse_attn_fwd_x3(q, v, kp, h, need_attn=need_attn)    # snuffy.py:160-168
-        elif FP32_ATTENTION == "x3" and X3_ATTN_DK192 and d == 192 * h and ops.x3_attn_dk192_supported(k):
-            o, attn, _ = ops.sparse_attn_fwd_x3_dk192(q, v, kp, h, need_attn=need_attn)   # q, v: halves of the fused projection, in place
-        elif FP32_ATTENTION == "x3" and X3_ATTN_DK256 and d == 256 * h and ops.x3_attn_dk256_supported(k):
-            o, attn, _ = ops.sparse_attn_fwd_x3_dk256(q, v, kp, h, need_attn=need_attn)   # q, v: halves of the fused projection, in place
+        elif FP32_ATTENTION == "x3" and (wide := _wide_single("fp32", d, h, k)) is not None:
+            o, attn, _ = getattr(ops, wide[4])(q, v, kp, h, need_attn=need_attn)   # q, v: halves of the fused projection, in place
         elif FP32_ATTENTION == "x3" and ops.x3u_attn_supported(k, d // h):
             # head widths no pipelined kernel takes (dk = 192: the README recipe D = 768 / h = 4): the unfused fp32-class pair
             o, attn, _ = ops.sparse_attn_fwd_x3u(q, kp, v, h, need_attn=need_attn)      # q, v: halves of the fused projection, in place
@@ -836,13 +852,10 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
     q, v = qv[:, :dp], qv[:, dp:]                                                   # row-strided views, used in place
     # dk = 192 (the README's MAE recipe, D = 768 with h = 4; no padded form) has kernel variants of its own; packed bags run their varlen
     # forms (ops.varlen_attn_dk192_supported, admitted above), whatever MFMA_ATTN_DK192 says about the single bag
-    dk192 = (MFMA_ATTN_DK192 and dkp == 192 and ragged is None and packed is None
-             and ops.mfma_attn_dk192_supported(k, n, qv.stride(0)))
     # dk = 256 (the README's SimCLR ResNet-18 recipe, D = 512 with h = 2) likewise: a kernel of its own behind MFMA_ATTN_DK256, the varlen
     # forms (ops.varlen_attn_dk256_supported) for packed bags whatever that switch says
-    dk256 = (MFMA_ATTN_DK256 and dkp == 256 and ragged is None and packed is None
-             and ops.mfma_attn_dk256_supported(k, n, qv.stride(0)))
-    if ragged is None and (packed is not None or dk192 or dk256 or ops.mfma_attn_supported(k, dkp, n, qv.stride(0))):
+    wide = _wide_single("bf16", dp, h, k, n, qv.stride(0)) if ragged is None and packed is None else None
+    if ragged is None and (packed is not None or wide is not None or ops.mfma_attn_supported(k, dkp, n, qv.stride(0))):
         # keys = RAW selected rows: the gather also leaves them in bf16, the projection runs like Q | V (bf16 operands,
         # fp32 accumulate, bf16 out) and the attention kernel reads Kp as it is
         xs, slot, xs16 = ops.gather_slot_map(x2, sel, bf16_copy=True)               # snuffy.py:131,145-147 (+ row -> slot map)
@@ -856,8 +869,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             kp = torch.addmm(fw["bk"], xs16, fw["wk"].t())
         if packed is not None:
             o, attn, _ = ops.sparse_attn_fwd_mfma_varlen(q, v, kp, packed, kb, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
-        elif dk256:
-            o, attn, _ = ops.sparse_attn_fwd_mfma_dk256(q, v, kp, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
+        elif wide is not None and wide[4] is not None:
+            o, attn, _ = getattr(ops, wide[4])(q, v, kp, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
         else:
             o, attn, _ = ops.sparse_attn_fwd_mfma(q, v, kp, n, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
     else:

@@ -750,57 +750,67 @@ def mfma_attn_supported(k, dk, n=None, ld=None):
     return True
 
 
-def mfma_attn_dk192_supported(k, n=None, ld=None):
-    """Shapes the MFMA attention takes at head width 192 (the README's MAE recipe: D = 768, h = 4), forward -- with or without in-kernel
-    dropout -- and backward (ops.sparse_attn_fwd_mfma / sparse_attn_bwd_mfma): one launch holds 128 keys (Kp 48 + P 40 + V 48 KiB of
-    LDS), up to 8 key chunks.  n / ld as in mfma_attn_supported.  The older predicates keep answering for dk = 64 / 128 only."""
-    if not 1 <= k <= 8 * 128:
+WIDE_KEYS = 8 * 128      # the native head widths (192, 256), both families: one launch holds 128 keys, up to 8 key chunks
+
+
+def _wide_attn_supported(k, n=None, ld=None):
+    """The key range of the native head widths; n / ld (bf16 only) as in mfma_attn_supported."""
+    if not 1 <= k <= WIDE_KEYS:
         return False
     if n is not None and (n > 0xffff00 or (ld is not None and (ld >= (1 << 24) or n * ld >= 0x7fffffff))):
         return False
     return True
+
+
+def mfma_attn_dk192_supported(k, n=None, ld=None):
+    """Shapes the MFMA attention takes at head width 192 (the README's MAE recipe: D = 768, h = 4), forward -- with or without in-kernel
+    dropout -- and backward (ops.sparse_attn_fwd_mfma / sparse_attn_bwd_mfma): one launch holds 128 keys (Kp 48 + P 40 + V 48 KiB of
+    LDS), up to 8 key chunks.  n / ld as in mfma_attn_supported.  The older predicates keep answering for dk = 64 / 128 only."""
+    return _wide_attn_supported(k, n, ld)
 
 
 def mfma_attn_dk256_supported(k, n=None, ld=None):
     """Shapes the bf16 MFMA attention takes at head width 256 (snf_sparse_attn_fwd_mfma_dk256; the README's SimCLR ResNet-18 recipe:
     D = 512, h = 2, Lambda = 900), forward only: one launch holds 128 keys, up to 8 key chunks.  n / ld as in mfma_attn_supported.
     mfma_attn_supported() keeps answering for dk = 64 / 128 only."""
-    if not 1 <= k <= 8 * 128:
-        return False
-    if n is not None and (n > 0xffff00 or (ld is not None and (ld >= (1 << 24) or n * ld >= 0x7fffffff))):
-        return False
-    return True
+    return _wide_attn_supported(k, n, ld)
+
+
+def _sparse_attn_fwd_mfma_wide(dk, q, v, kp, h, scale, need_attn, need_lse):
+    """The bf16 single-bag forward of a native head width (snf_sparse_attn_fwd_mfma_dk<dk>)."""
+    me = "sparse_attn_fwd_mfma_dk%d" % dk
+    if q.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise TypeError("%s: q and v must be bfloat16" % me)
+    q = _rows16(q, "q")
+    v = _rows16(v, "v")
+    if kp.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("%s: kp must be float32 or bfloat16" % me)
+    kp = _req(kp, kp.dtype, "kp", 2)
+    n, d = q.shape
+    k = kp.shape[0]
+    if h < 1 or d != dk * h or kp.shape[1] != d or v.shape != q.shape:
+        raise _ffi.SnuffyHipError("%s: inconsistent shapes q %s v %s kp %s h %d (d_model must be %d h)"
+                                  % (me, tuple(q.shape), tuple(v.shape), tuple(kp.shape), h, dk))
+    scale = 1.0 / math.sqrt(dk) if scale is None else scale
+    lib = _ffi.load()
+    wsb = getattr(lib, "snf_%s_workspace_bytes" % me)(n, k, h)
+    if wsb == 0:
+        raise _ffi.SnuffyHipError("%s: unsupported shape n=%d k=%d h=%d (1 <= k <= %d)" % (me, n, k, h, WIDE_KEYS))
+    out = torch.empty(k, d, dtype=torch.float32, device=q.device)
+    attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
+    lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
+    ws = _ws(wsb, q.device)
+    kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
+    check(getattr(lib, "snf_" + me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, n, k, h, float(scale), _p(out), _p(attn), _p(lse),
+                                    _p(ws), wsb, _stream()), "snf_" + me)
+    return out, attn, lse
 
 
 def sparse_attn_fwd_mfma_dk256(q, v, kp, h, scale=None, need_attn=False, need_lse=False):
     """bf16 sparse attention on the matrix cores at head width 256 (snf_sparse_attn_fwd_mfma_dk256): q, v [n, 256 h] bf16 (row-strided
     views allowed: the halves of a fused [Q | V] projection), kp [k, 256 h] f32 or bf16 (the same bits either way)
     -> (out [k, d] f32, attn [h, n, k] or None, lse [h, n] or None).  Inference only."""
-    if q.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
-        raise TypeError("sparse_attn_fwd_mfma_dk256: q and v must be bfloat16")
-    q = _rows16(q, "q")
-    v = _rows16(v, "v")
-    if kp.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("sparse_attn_fwd_mfma_dk256: kp must be float32 or bfloat16")
-    kp = _req(kp, kp.dtype, "kp", 2)
-    n, d = q.shape
-    k = kp.shape[0]
-    if h < 1 or d != 256 * h or kp.shape[1] != d or v.shape != q.shape:
-        raise _ffi.SnuffyHipError("sparse_attn_fwd_mfma_dk256: inconsistent shapes q %s v %s kp %s h %d (d_model must be 256 h)"
-                                  % (tuple(q.shape), tuple(v.shape), tuple(kp.shape), h))
-    scale = 1.0 / math.sqrt(256) if scale is None else scale
-    lib = _ffi.load()
-    wsb = lib.snf_sparse_attn_fwd_mfma_dk256_workspace_bytes(n, k, h)
-    if wsb == 0:
-        raise _ffi.SnuffyHipError("sparse_attn_fwd_mfma_dk256: unsupported shape n=%d k=%d h=%d (1 <= k <= 1024)" % (n, k, h))
-    out = torch.empty(k, d, dtype=torch.float32, device=q.device)
-    attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
-    lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
-    ws = _ws(wsb, q.device)
-    kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
-    check(lib.snf_sparse_attn_fwd_mfma_dk256(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, n, k, h, float(scale), _p(out), _p(attn),
-                                             _p(lse), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_mfma_dk256")
-    return out, attn, lse
+    return _sparse_attn_fwd_mfma_wide(256, q, v, kp, h, scale, need_attn, need_lse)
 
 
 def mfma_attn_dropout_supported(k, dk):
@@ -934,70 +944,53 @@ def x3_attn_dk192_supported(k):
     """Shapes of the fused fp32-class attention kernel at head width 192 (snf_sparse_attn_fwd_x3_dk192; the README's MAE recipe D = 768,
     h = 4): 128 keys per launch, up to 8 key chunks with exact cross-chunk softmax statistics.  x3_attn_supported() keeps answering for
     dk = 64 / 128 only."""
-    return 1 <= k <= 8 * 128
-
-
-def sparse_attn_fwd_x3_dk192(q, v, kp, h, scale=None, need_attn=False, need_lse=False):
-    """fp32-class sparse attention on the matrix cores at head width 192, fused (snf_sparse_attn_fwd_x3_dk192: no materialised
-    [h, n, k] probabilities between the softmax and P^T V): q, v [n, 192 h] f32 (row-strided views allowed: the halves of a fused
-    [Q | V] projection), kp [k, 192 h] f32 -> (out [k, d], attn [h, n, k] or None, lse [h, n] or None)."""
-    if q.dtype != torch.float32 or v.dtype != torch.float32:
-        raise TypeError("sparse_attn_fwd_x3_dk192: q and v must be float32")
-    q = _rows16(q, "q")
-    v = _rows16(v, "v")
-    kp = _req(kp, torch.float32, "kp", 2)
-    n, d = q.shape
-    k = kp.shape[0]
-    if d != 192 * h or kp.shape[1] != d or v.shape != q.shape:
-        raise ValueError("sparse_attn_fwd_x3_dk192: inconsistent shapes q %s v %s kp %s h %d (d_model must be 192 h)"
-                         % (tuple(q.shape), tuple(v.shape), tuple(kp.shape), h))
-    scale = 1.0 / math.sqrt(192) if scale is None else scale
-    lib = _ffi.load()
-    wsb = lib.snf_sparse_attn_fwd_x3_dk192_workspace_bytes(n, k, h)
-    if wsb == 0:
-        raise ValueError("sparse_attn_fwd_x3_dk192: unsupported shape n=%d k=%d h=%d (1 <= k <= 1024)" % (n, k, h))
-    out = torch.empty(k, d, dtype=torch.float32, device=q.device)
-    attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
-    lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
-    ws = _ws(wsb, q.device)
-    check(lib.snf_sparse_attn_fwd_x3_dk192(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), n, k, h, float(scale), _p(out), _p(attn),
-                                           _p(lse), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_x3_dk192")
-    return out, attn, lse
+    return _wide_attn_supported(k)
 
 
 def x3_attn_dk256_supported(k):
     """Shapes of the fused fp32-class attention kernel at head width 256 (snf_sparse_attn_fwd_x3_dk256; the README's SimCLR ResNet-18
     recipe D = 512, h = 2, Lambda = 900): 128 keys per launch, up to 8 key chunks with exact cross-chunk softmax statistics -- the key
     range of the unfused pair (x3u_attn_supported).  x3_attn_supported() keeps answering for dk = 64 / 128 only."""
-    return 1 <= k <= 8 * 128
+    return _wide_attn_supported(k)
 
 
-def sparse_attn_fwd_x3_dk256(q, v, kp, h, scale=None, need_attn=False, need_lse=False):
-    """fp32-class sparse attention on the matrix cores at head width 256, fused (snf_sparse_attn_fwd_x3_dk256: no materialised
-    [h, n, k] probabilities between the softmax and P^T V): q, v [n, 256 h] f32 (row-strided views allowed: the halves of a fused
-    [Q | V] projection), kp [k, 256 h] f32 -> (out [k, d], attn [h, n, k] or None, lse [h, n] or None)."""
+def _sparse_attn_fwd_x3_wide(dk, q, v, kp, h, scale, need_attn, need_lse):
+    """The fp32-class single-bag forward of a native head width (snf_sparse_attn_fwd_x3_dk<dk>)."""
+    me = "sparse_attn_fwd_x3_dk%d" % dk
     if q.dtype != torch.float32 or v.dtype != torch.float32:
-        raise TypeError("sparse_attn_fwd_x3_dk256: q and v must be float32")
+        raise TypeError("%s: q and v must be float32" % me)
     q = _rows16(q, "q")
     v = _rows16(v, "v")
     kp = _req(kp, torch.float32, "kp", 2)
     n, d = q.shape
     k = kp.shape[0]
-    if d != 256 * h or kp.shape[1] != d or v.shape != q.shape:
-        raise ValueError("sparse_attn_fwd_x3_dk256: inconsistent shapes q %s v %s kp %s h %d (d_model must be 256 h)"
-                         % (tuple(q.shape), tuple(v.shape), tuple(kp.shape), h))
-    scale = 1.0 / math.sqrt(256) if scale is None else scale
+    if d != dk * h or kp.shape[1] != d or v.shape != q.shape:
+        raise ValueError("%s: inconsistent shapes q %s v %s kp %s h %d (d_model must be %d h)"
+                         % (me, tuple(q.shape), tuple(v.shape), tuple(kp.shape), h, dk))
+    scale = 1.0 / math.sqrt(dk) if scale is None else scale
     lib = _ffi.load()
-    wsb = lib.snf_sparse_attn_fwd_x3_dk256_workspace_bytes(n, k, h)
+    wsb = getattr(lib, "snf_%s_workspace_bytes" % me)(n, k, h)
     if wsb == 0:
-        raise ValueError("sparse_attn_fwd_x3_dk256: unsupported shape n=%d k=%d h=%d (1 <= k <= 1024)" % (n, k, h))
+        raise ValueError("%s: unsupported shape n=%d k=%d h=%d (1 <= k <= %d)" % (me, n, k, h, WIDE_KEYS))
     out = torch.empty(k, d, dtype=torch.float32, device=q.device)
     attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
     lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
     ws = _ws(wsb, q.device)
-    check(lib.snf_sparse_attn_fwd_x3_dk256(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), n, k, h, float(scale), _p(out), _p(attn),
-                                           _p(lse), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_x3_dk256")
+    check(getattr(lib, "snf_" + me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), n, k, h, float(scale), _p(out), _p(attn), _p(lse),
+                                    _p(ws), wsb, _stream()), "snf_" + me)
     return out, attn, lse
+
+
+def sparse_attn_fwd_x3_dk192(q, v, kp, h, scale=None, need_attn=False, need_lse=False):
+    """fp32-class sparse attention on the matrix cores at head width 192, fused (snf_sparse_attn_fwd_x3_dk192: no materialised
+    [h, n, k] probabilities between the softmax and P^T V): q, v [n, 192 h] f32 (row-strided views allowed: the halves of a fused
+    [Q | V] projection), kp [k, 192 h] f32 -> (out [k, d], attn [h, n, k] or None, lse [h, n] or None)."""
+    return _sparse_attn_fwd_x3_wide(192, q, v, kp, h, scale, need_attn, need_lse)
+
+
+def sparse_attn_fwd_x3_dk256(q, v, kp, h, scale=None, need_attn=False, need_lse=False):
+    """As sparse_attn_fwd_x3_dk192() at head width 256 (snf_sparse_attn_fwd_x3_dk256): q, v [n, 256 h] f32, kp [k, 256 h] f32."""
+    return _sparse_attn_fwd_x3_wide(256, q, v, kp, h, scale, need_attn, need_lse)
 
 
 _X3_HL_OK = {}
@@ -1163,10 +1156,12 @@ class PackedBags:
             return hit
         lib = _ffi.load()
         need, wsb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        fn = {"mfma": lib.snf_sparse_attn_varlen_plan, "x3": lib.snf_sparse_attn_x3_varlen_plan,
-              "mfma_chunks": lib.snf_sparse_attn_varlen_chunked_plan, "x3_chunks": lib.snf_sparse_attn_x3_varlen_chunked_plan,
-              "mfma_dk192": lib.snf_sparse_attn_varlen_dk192_plan, "x3_dk192": lib.snf_sparse_attn_x3_varlen_dk192_plan,
-              "mfma_dk256": lib.snf_sparse_attn_varlen_dk256_plan, "x3_dk256": lib.snf_sparse_attn_x3_varlen_dk256_plan, "head": lib.snf_ln_mean_head_varlen_plan}[kind]
+        names = {"mfma": "snf_sparse_attn_varlen_plan", "x3": "snf_sparse_attn_x3_varlen_plan",
+                 "mfma_chunks": "snf_sparse_attn_varlen_chunked_plan", "x3_chunks": "snf_sparse_attn_x3_varlen_chunked_plan",
+                 "head": "snf_ln_mean_head_varlen_plan"}
+        for dk in (192, 256):
+            names.update({"mfma_dk%d" % dk: "snf_sparse_attn_varlen_dk%d_plan" % dk, "x3_dk%d" % dk: "snf_sparse_attn_x3_varlen_dk%d_plan" % dk})
+        fn = getattr(lib, names[kind])
         chunks = (ctypes.c_int(0), ctypes.c_int(0)) if kind.endswith(("_chunks", "_dk192", "_dk256")) else ()
         extra = tuple(ctypes.byref(c) for c in chunks)
         check(fn(self._host_ptr(), self.bags, *shape, None, 0, ctypes.byref(need), ctypes.byref(wsb), *extra), "varlen plan (%s)" % kind)
@@ -1254,25 +1249,25 @@ def varlen_attn_chunks_supported(precision_kind, k, dk):
 def varlen_attn_dk192_supported(k):
     """The bf16 varlen attention at head width 192 (snf_sparse_attn_fwd_mfma_varlen_dk192; the README's MAE recipe D = 768, h = 4): one
     launch holds 128 keys, up to 8 key chunks.  The older varlen predicates keep answering for dk = 64 / 128 only."""
-    return 1 <= k <= 8 * 128
+    return _wide_attn_supported(k)
 
 
 def varlen_attn_dk256_supported(k):
     """The bf16 varlen attention at head width 256 (snf_sparse_attn_fwd_mfma_varlen_dk256; the README's SimCLR ResNet-18 recipe D = 512,
     h = 2): one launch holds 128 keys, up to 8 key chunks.  The older varlen predicates keep answering for dk = 64 / 128 only."""
-    return 1 <= k <= 8 * 128
+    return _wide_attn_supported(k)
 
 
 def varlen_attn_x3_dk192_supported(k):
     """The fp32-class varlen attention at head width 192 (snf_sparse_attn_fwd_x3_varlen_dk192): one launch holds 128 keys, up to 8 key
     chunks.  The older varlen predicates keep answering for dk = 64 / 128 only."""
-    return 1 <= k <= 8 * 128
+    return _wide_attn_supported(k)
 
 
 def varlen_attn_x3_dk256_supported(k):
     """The fp32-class varlen attention at head width 256 (snf_sparse_attn_fwd_x3_varlen_dk256): one launch holds 128 keys, up to 8 key
     chunks.  The older varlen predicates keep answering for dk = 64 / 128 (and 192) only."""
-    return 1 <= k <= 8 * 128
+    return _wide_attn_supported(k)
 
 
 def topk_segmented(scores, packed, k):
@@ -1318,15 +1313,10 @@ def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fa
     lse = torch.empty(h, t, dtype=torch.float32, device=q.device) if need_lse else None
     kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
     lib = _ffi.load()
-    if dk == 192:
-        check(lib.snf_sparse_attn_fwd_mfma_varlen_dk192(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(),
-                                                        packed.bags, k, h, float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws),
-                                                        wsb, _stream()), "snf_sparse_attn_fwd_mfma_varlen_dk192")
-        return out, attn, lse
-    if dk == 256:
-        check(lib.snf_sparse_attn_fwd_mfma_varlen_dk256(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(),
-                                                        packed.bags, k, h, float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws),
-                                                        wsb, _stream()), "snf_sparse_attn_fwd_mfma_varlen_dk256")
+    if dk in (192, 256):
+        me = "snf_sparse_attn_fwd_mfma_varlen_dk%d" % dk
+        check(getattr(lib, me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(), packed.bags, k, h, float(scale),
+                               _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()), me)
         return out, attn, lse
     fn = lib.snf_sparse_attn_fwd_mfma_varlen_chunked if chunked else lib.snf_sparse_attn_fwd_mfma_varlen
     check(fn(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(), packed.bags, k, h, dk, float(scale), _p(out),
@@ -1360,15 +1350,10 @@ def sparse_attn_fwd_x3_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fals
     attn = torch.empty(h, t, k, dtype=torch.float32, device=q.device) if need_attn else None
     lse = torch.empty(h, t, dtype=torch.float32, device=q.device) if need_lse else None
     lib = _ffi.load()
-    if dk == 192:
-        check(lib.snf_sparse_attn_fwd_x3_varlen_dk192(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h,
-                                                      float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()),
-              "snf_sparse_attn_fwd_x3_varlen_dk192")
-        return out, attn, lse
-    if dk == 256:
-        check(lib.snf_sparse_attn_fwd_x3_varlen_dk256(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h,
-                                                      float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()),
-              "snf_sparse_attn_fwd_x3_varlen_dk256")
+    if dk in (192, 256):
+        me = "snf_sparse_attn_fwd_x3_varlen_dk%d" % dk
+        check(getattr(lib, me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h, float(scale),
+                               _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()), me)
         return out, attn, lse
     fn = lib.snf_sparse_attn_fwd_x3_varlen_chunked if chunked else lib.snf_sparse_attn_fwd_x3_varlen
     check(fn(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h, dk, float(scale), _p(out), _p(attn),

@@ -124,26 +124,31 @@ def device_draws(cfg):
     return PACK_DEVICE_SAMPLER and cfg.sampler == "device"
 
 
+def _wide_ok(switch, precision, dk, supported, compute, d, h, k):
+    """A native head width packs: its switch is on, the model computes in the kernel's precision, and the key count is the kernel's."""
+    return bool(switch and compute == precision and h >= 1 and d == dk * h and supported(k))
+
+
 def dk192_ok(compute, d, h, k):
     """PACK_DK192: the bf16 model at head width 192 with a key count inside the dk = 192 varlen kernels.  precision="fp32" stays per
     bag whatever THIS switch: its packed route at this width is the fused fp32-class kernel behind PACK_X3_DK192 (x3_dk192_ok)."""
-    return bool(PACK_DK192 and compute == "bf16" and h >= 1 and d == 192 * h and SF.ops.varlen_attn_dk192_supported(k))
+    return _wide_ok(PACK_DK192, "bf16", 192, SF.ops.varlen_attn_dk192_supported, compute, d, h, k)
 
 
 def dk256_ok(compute, d, h, k):
     """PACK_DK256: the bf16 model at head width 256 with a key count inside the dk = 256 bf16 varlen kernels.  precision="fp32" is not
     THIS switch's: its packed route at this width is the fused fp32-class kernel behind PACK_X3_DK256 (x3_dk256_ok)."""
-    return bool(PACK_DK256 and compute == "bf16" and h >= 1 and d == 256 * h and SF.ops.varlen_attn_dk256_supported(k))
+    return _wide_ok(PACK_DK256, "bf16", 256, SF.ops.varlen_attn_dk256_supported, compute, d, h, k)
 
 
 def x3_dk192_ok(compute, d, h, k):
     """PACK_X3_DK192: the fp32 model at head width 192 with a key count inside the fused fp32-class varlen kernel of that width."""
-    return bool(PACK_X3_DK192 and compute == "fp32" and h >= 1 and d == 192 * h and SF.ops.varlen_attn_x3_dk192_supported(k))
+    return _wide_ok(PACK_X3_DK192, "fp32", 192, SF.ops.varlen_attn_x3_dk192_supported, compute, d, h, k)
 
 
 def x3_dk256_ok(compute, d, h, k):
     """PACK_X3_DK256: the fp32 model at head width 256 with a key count inside the fused fp32-class varlen kernel of that width."""
-    return bool(PACK_X3_DK256 and compute == "fp32" and h >= 1 and d == 256 * h and SF.ops.varlen_attn_x3_dk256_supported(k))
+    return _wide_ok(PACK_X3_DK256, "fp32", 256, SF.ops.varlen_attn_x3_dk256_supported, compute, d, h, k)
 
 
 def key_chunks_ok(layers, compute, d, h, k, bags, rows):

@@ -1,6 +1,6 @@
 """The host answers of the tiled sparse-attention forward, pinned: tools/record_attn_plans.py replayed against the built library and compared
-field by field with tests/golden/attn_plans.npz, which was recorded from the build before the drivers moved into csrc/attn_drive.h.  Pure
-host code (cu_count() falls back to the MI355X's 256 without a device)."""
+field by field with tests/golden/attn_plans.npz, which was recorded from the build before the drivers moved into csrc/attn_drive.h and
+again, with the 256 entry points added, from the build before the width shells moved into csrc/attn_width.h.  Pure host code (cu_count() falls back to the MI355X's 256 without a device)."""
 import os
 import sys
 

@@ -1,5 +1,5 @@
-"""Everything the host-only entry points of the tiled sparse-attention forward return, for a fixed list of cases: the six varlen plan
-functions (return code, both sizes, chunk count and size, the whole table, the snf_last_error() text of a refusal) and the three
+"""Everything the host-only entry points of the tiled sparse-attention forward return, for a fixed list of cases: the eight varlen plan
+functions (return code, both sizes, chunk count and size, the whole table, the snf_last_error() text of a refusal) and the five
 single-bag workspace functions.  tests/test_attn_plan_golden.py replays the same cases against the built library and compares field
 by field with tests/golden/attn_plans.npz.
 
@@ -16,19 +16,24 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "attn_plans.npz")
 
-# (entry point, takes dk, reports chunks, widths to ask for)
+# (entry point, takes dk, reports chunks, widths to ask for); new rows go at the END of both lists: the recorded cases keep their order
 PLANS = [("snf_sparse_attn_varlen_plan", True, False, (64, 128, 192, 83)),
          ("snf_sparse_attn_varlen_chunked_plan", True, True, (64, 128, 192, 83)),
          ("snf_sparse_attn_varlen_dk192_plan", False, True, (192,)),
          ("snf_sparse_attn_x3_varlen_plan", True, False, (64, 128, 192, 83)),
          ("snf_sparse_attn_x3_varlen_chunked_plan", True, True, (64, 128, 192, 83)),
-         ("snf_sparse_attn_x3_varlen_dk192_plan", False, True, (192,))]
-KMAX = {64: 256, 128: 224, 192: 128, 83: 224}
+         ("snf_sparse_attn_x3_varlen_dk192_plan", False, True, (192,)),
+         ("snf_sparse_attn_x3_varlen_dk256_plan", False, True, (256,)),
+         ("snf_sparse_attn_varlen_dk256_plan", False, True, (256,))]
+KMAX = {64: 256, 128: 224, 192: 128, 256: 128, 83: 224}
 LONG = 256 * 16 * 128 + 1                                  # more than 256 * 16 tiles of either family (128 | 64 rows)
 BATCH = [200, 1100, 2100]
 BAGS = [[1], [1024], [1025], [1, 1024, 1025], [LONG], [300, LONG, 7], None]    # None: an empty bag, offsets [0, 100, 100]
-WORKSPACES = [("snf_sparse_attn_fwd_workspace_bytes", True, (1,)), ("snf_sparse_attn_fwd_x3_workspace_bytes", True, ()),
-              ("snf_sparse_attn_fwd_x3_dk192_workspace_bytes", False, ())]
+# (entry point, takes dk, further arguments, the width of an entry point that takes none)
+WORKSPACES = [("snf_sparse_attn_fwd_workspace_bytes", True, (1,), None), ("snf_sparse_attn_fwd_x3_workspace_bytes", True, (), None),
+              ("snf_sparse_attn_fwd_x3_dk192_workspace_bytes", False, (), 192),
+              ("snf_sparse_attn_fwd_x3_dk256_workspace_bytes", False, (), 256),
+              ("snf_sparse_attn_fwd_mfma_dk256_workspace_bytes", False, (), 256)]
 
 
 def _keys(dk):
@@ -66,7 +71,7 @@ def run(lib):
     lib.snf_last_error.restype = ctypes.c_char_p
     for name, _, _, _ in PLANS:
         getattr(lib, name).restype = ctypes.c_int
-    for name, _, _ in WORKSPACES:
+    for name, _, _, _ in WORKSPACES:
         getattr(lib, name).restype = ctypes.c_size_t
     case, rc_, need_, ws_, nc_, ck_, err_, short_rc, short_err, tab_len, tabs = [], [], [], [], [], [], [], [], [], [], []
     for name, has_dk, has_chunks, dk, h, k, sizes in plan_cases():
@@ -98,9 +103,9 @@ def run(lib):
            "plan_short_table_rc": np.array(short_rc, dtype=np.int64), "plan_short_table_error": np.array(short_err),
            "plan_table_len": np.array(tab_len, dtype=np.int64), "plan_tables": np.concatenate(tabs)}
     case, bytes_ = [], []
-    for name, has_dk, extra in WORKSPACES:
+    for name, has_dk, extra, width in WORKSPACES:
         fn = getattr(lib, name)
-        for dk in ((64, 128, 192, 83) if has_dk else (192,)):
+        for dk in ((64, 128, 192, 83) if has_dk else (width,)):
             for h in (1, 6):
                 for n in (1, 300, 1024, 1025, LONG):
                     for k in _keys(dk):
