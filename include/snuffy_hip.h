@@ -425,7 +425,9 @@ int snf_sparse_attn_bwd_mfma_ex(const void* q, int64_t ldq, const void* v, int64
  * leave as bf16; fp32 dq / dv are summed in place).  One chunk: forwards to snf_sparse_attn_bwd_mfma_ex (workspace may be NULL).
  * dk == 192 with k <= 8 x 128 (the forward's domain there) exists in this form only: chunks of up to 192 keys (two images of 144 KiB),
  * one launch per series even for a single chunk (the workspace is always needed); snf_sparse_attn_bwd_mfma[_ex] refuse dk == 192.
- * There dS = (bf16(P o M) o dPd - P D) * scale, the rounded factor being the one D was summed with: rows of dS sum to 0 in fp32. */
+ * There dS = (bf16(P o M) o dPd - P D) * scale, the rounded factor being the one D was summed with: rows of dS sum to 0 in fp32.
+ * dk == 256 with k <= 8 x 128 is the same case: chunks of up to 128 keys (two images of 128 KiB), this form only, the dS of dk == 192;
+ * snf_sparse_attn_bwd_mfma[_ex] refuse dk == 256. */
 size_t snf_sparse_attn_bwd_mfma_chunked_workspace_bytes(int64_t n, int k, int h, int dk, int dqv_dtype);
 int snf_sparse_attn_bwd_mfma_chunked(const void* q, int64_t ldq, const void* v, int64_t ldv, int qv_dtype, const float* kp,
                                      const float* dout, const float* lse, const float* mask, float dropout_p, uint64_t seed,
@@ -748,7 +750,7 @@ int snf_sparse_attn_fwd_x3_varlen_dk256(const float* q, int64_t ldq, const float
                                         const int64_t* offsets, int bags, int k, int h, float scale, float* out, float* attn,
                                         float* lse, const int32_t* table_dev, void* workspace, size_t workspace_bytes,
                                         snf_stream_t stream);
-/* The bf16 family at HEAD WIDTH 256 (the same recipe in precision="bf16"), inference only: q and v are bf16 ONLY (row pitches ldq / ldv
+/* The bf16 family at HEAD WIDTH 256 (the same recipe in precision="bf16"; the training form is ..._dk256_dropout below): q and v are bf16 ONLY (row pitches ldq / ldv
  * in elements, so the two halves of one [N, 2D] projection are passed in place), kp is f32 or bf16 (kp_dtype; an f32 Kp is rounded to
  * bf16 once, round to nearest even, into the workspace: both give the same bits), out / attn / lse are f32.  snf_sparse_attn_fwd_mfma and
  * the varlen plan functions of dk = 64 / 128 and of 192 keep answering SNF_EUNSUPPORTED at dk = 256.  One launch holds 128 keys (1, 2 or
@@ -769,6 +771,15 @@ size_t snf_sparse_attn_fwd_mfma_dk256_workspace_bytes(int64_t n, int k, int h);
 int snf_sparse_attn_fwd_mfma_dk256(const void* q, int64_t ldq, const void* v, int64_t ldv, const void* kp, int kp_dtype, int64_t n, int k,
                                    int h, float scale, float* out, float* attn, float* lse, void* workspace, size_t workspace_bytes,
                                    snf_stream_t stream);
+/* Training form: snf_sparse_attn_fwd_mfma_dk256 with attention dropout applied inside the kernel (Philox, the mask of
+ * snf_dropout_mask_f32; never read from memory).  lse and the normalised P are, bit for bit, those of the launch without dropout; attn
+ * (when asked for) is P o M with M the keep-mask / (1 - p), out = (P o M)^T V with P o M rounded to bf16.  Single bag only; the workspace
+ * is snf_sparse_attn_fwd_mfma_dk256_workspace_bytes'.  Above one key chunk every pass keeps the chunks of that launch (this kernel's P
+ * depends on which keys share a 32-key block); a chunk that starts off a multiple of 4 draws two Philox groups per 4 keys.  SNF_EINVAL: dropout_p outside [0, 1),
+ * dropout_p > 0 with neither lse nor attn.  dropout_p == 0 is snf_sparse_attn_fwd_mfma_dk256 itself. */
+int snf_sparse_attn_fwd_mfma_dk256_dropout(const void* q, int64_t ldq, const void* v, int64_t ldv, const void* kp, int kp_dtype, int64_t n,
+                                           int k, int h, float scale, float* out, float* attn, float* lse, void* workspace,
+                                           size_t workspace_bytes, snf_stream_t stream, float dropout_p, uint64_t seed, uint64_t offset);
 int snf_sparse_attn_varlen_dk256_plan(const int64_t* offsets, int bags, int k, int h, int32_t* table, size_t table_ints,
                                       size_t* table_ints_needed, size_t* workspace_bytes, int* n_chunks, int* chunk_k);
 int snf_sparse_attn_fwd_mfma_varlen_dk256(const void* q, int64_t ldq, const void* v, int64_t ldv, const void* kp, int kp_dtype,

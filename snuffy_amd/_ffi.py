@@ -243,7 +243,9 @@ for _dk in (192, 256):
         "snf_sparse_attn_varlen_dk%d_plan" % _dk: _WIDE_PLAN,
         "snf_sparse_attn_fwd_mfma_varlen_dk%d" % _dk: (c_int, _WIDE_QVKP + [c_int] + _WIDE_VARLEN)})
 SIGNATURES.update({"snf_sparse_attn_fwd_mfma_dk256_workspace_bytes": _WIDE_WORKSPACE,
-                   "snf_sparse_attn_fwd_mfma_dk256": (c_int, _WIDE_QVKP + [c_int] + _WIDE_BAG)})
+                   "snf_sparse_attn_fwd_mfma_dk256": (c_int, _WIDE_QVKP + [c_int] + _WIDE_BAG),
+                   # ... with in-kernel attention dropout: dropout_p, seed, offset behind the arguments of the entry above
+                   "snf_sparse_attn_fwd_mfma_dk256_dropout": (c_int, _WIDE_QVKP + [c_int] + _WIDE_BAG + [c_float, c_uint64, c_uint64])})
 
 _lib = None
 

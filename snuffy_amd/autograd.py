@@ -33,6 +33,16 @@ FUSED_BF16_KEY_CHUNKS = True
 # no padding); False: such layers take the generic autograd chain, as before (fused_layer0_dk192_ok).  Ships off, like
 # functional.MFMA_ATTN_DK192: not timed against the generic chain yet (tools/attn_dk192_time.py)
 FUSED_BF16_DK192 = False
+# ... and at head width 256 (D = 512 with h = 2, the README's SimCLR ResNet-18 recipe: the dk = 256 forward with in-kernel dropout,
+# ops.sparse_attn_fwd_mfma_dk256(dropout=...), and the chunked backward at DK = 256); False: such layers take the generic autograd
+# chain, as before (fused_layer0_dk256_ok).  Ships on: no row of tools/attn_dk256_train_time.py is behind the generic chain (1.17 - 1.66 x
+# per optimizer step at N = 8000 / 32768, profiles/attn_dk256_train.txt) and no test fails with it on
+FUSED_BF16_DK256 = True
+# the generic chain's attention (SparseAttnFn: GELU / SELU / LeakyReLU models, every layer after the first) on the MFMA kernels at head
+# widths 192 and 256 too: forward with in-kernel dropout, (q16, kp, v16, lse) saved instead of P and a mask tensor, backward on the
+# chunked kernel; False: the function is what it was (exact forward with P materialised, mask tensor, exact backward).  Ships off under
+# the same rule: 1.27 x at N = 32768 but 0.96 x, outside the spread, at N = 8000 with encoder dropout (same file)
+SPARSE_ATTN_FN_WIDE = False
 # fp32 training: the same for the fp32-class arithmetic (EncoderLayer0X3Fn, round 5)
 FUSED_X3_TRAINING = True
 # ... on the one-pass kernels (round 6): activations and gradients as interleaved hl images (4 bytes per element instead of the 6 of
@@ -194,8 +204,9 @@ class SparseAttnFn(torch.autograd.Function):
     mask is regenerated in registers from (seed, offset) in both (csrc/philox.h) -- no [h, N, K] tensor is stored for it and
     the forward's O is the kernel's own.  Otherwise: fp32-class forward (split-bf16 x 3 on the matrix cores where the shape
     allows, else the exact vector-ALU kernel) with P materialised for the exact backward kernel snf_sparse_attn_bwd_f32; the
-    mask is the same Philox stream written out as a tensor.  Returns (O, P): P is the dropped P in train mode, as the
-    reference's attention() returns it."""
+    mask is the same Philox stream written out as a tensor.  With SPARSE_ATTN_FN_WIDE the first route also serves dk = 192 and
+    dk = 256 (their own forward kernels, the backward over key chunks).  Returns (O, P): P is the dropped P in train mode, as
+    the reference's attention() returns it."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -206,6 +217,19 @@ class SparseAttnFn(torch.autograd.Function):
         drop = (float(dropout_p),) + draw_dropout_state() if dropout_p > 0.0 else None
         ctx.h, ctx.drop = h, drop
         ctx.fast_bwd = bool(bf16_operands and ops.mfma_attn_supported(k, dk) and ops.mfma_attn_bwd_supported(k, dk))
+        # SPARSE_ATTN_FN_WIDE: the same branch at the native head widths (any key count of theirs: the backward runs over key chunks)
+        wide = bool(SPARSE_ATTN_FN_WIDE and bf16_operands and not ctx.fast_bwd
+                    and ((dk == 192 and d == 192 * h and ops.mfma_attn_dk192_supported(k, n, d))
+                         or (dk == 256 and d == 256 * h and ops.mfma_attn_dk256_train_supported(k, n, d))))
+        if wide:
+            ctx.fast_bwd = True
+            q16, v16 = q.to(torch.bfloat16), v.to(torch.bfloat16)
+            if dk == 256:
+                out, p, lse = ops.sparse_attn_fwd_mfma_dk256(q16, v16, kp, h, need_attn=want_p, need_lse=True, dropout=drop)
+            else:
+                out, p, lse = ops.sparse_attn_fwd_mfma(q16, v16, kp, n, h, need_attn=want_p, need_lse=True, dropout=drop)
+            ctx.save_for_backward(q16, kp, v16, lse)
+            return out, p
         if ctx.fast_bwd:
             q16, v16 = q.to(torch.bfloat16), v.to(torch.bfloat16)
             out, p, lse = ops.sparse_attn_fwd_mfma(q16, v16, kp, n, h, need_attn=want_p, need_lse=True, dropout=drop)
@@ -394,8 +418,12 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
             kp = torch.addmm(fw["bk"], xs16, fw["wk"].t()).float()
         p_drop = mha.dropout.p if layer.training else 0.0
         drop = (float(p_drop),) + draw_dropout_state() if p_drop > 0.0 else None
-        o, attn, lse = ops.sparse_attn_fwd_mfma(q, v, kp, n, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn, need_lse=True,
-                                                dropout=drop)
+        if dkp == 256:                                                                 # the width's own entry point (fused_layer0_dk256_ok)
+            o, attn, lse = ops.sparse_attn_fwd_mfma_dk256(q, v, kp, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn, need_lse=True,
+                                                          dropout=drop)
+        else:
+            o, attn, lse = ops.sparse_attn_fwd_mfma(q, v, kp, n, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn, need_lse=True,
+                                                    dropout=drop)
         # encoder dropout: A = after the attention output (snuffy.py:108), H = inside the FFN (:225), Z = after it (:110)
         p_a, p_h, p_z = _encoder_dropout_ps(layer)
         drop_a = (p_a,) + draw_dropout_state() if p_a > 0.0 else None
@@ -593,6 +621,27 @@ def fused_layer0_dk192_ok(layer, n, d, k=None):
     return True
 
 
+def fused_layer0_dk256_ok(layer, n, d, k=None):
+    """EncoderLayer0Bf16Fn takes the layer at head width 256 (FUSED_BF16_DK256): the settings of fused_layer0_dk192_ok (ReLU FFN, one
+    eps, all parameters trainable, encoder dropout as admitted there) with the key counts of ops.mfma_attn_dk256_train_supported -- the
+    forward over up to 8 chunks of 128 keys with in-kernel dropout, the backward on the chunked kernel at any key count."""
+    if not (FUSED_BF16_TRAINING and FUSED_BF16_DK256):
+        return False
+    mha, ff = layer.self_attn, layer.feed_forward
+    n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
+    if ff.activation_name != "relu" or n0.eps != n1.eps or d % mha.h or d // mha.h != 256:
+        return False
+    if k is None:
+        k = min(int(layer.big_lambda), n)
+    if not (ops.mfma_attn_dk256_train_supported(k, n, 2 * d) and all(p.requires_grad for p in layer.parameters())):
+        return False
+    ps = _encoder_dropout_ps(layer)
+    if any(p != 0.0 for p in ps):
+        return (FUSED_BF16_ENCODER_DROPOUT and all(0.0 <= p < 1.0 for p in ps)
+                and ops.bf16_encoder_dropout_supported(n, d, ff.w_1.weight.shape[0]))
+    return True
+
+
 def fused_layer0_ok(x2, sel, layer, precision):
     """The first-layer chain applies: bf16, the bag is data (no gradient flows into x2), supported shape / settings;
     everything else keeps the generic autograd chain below."""
@@ -600,7 +649,8 @@ def fused_layer0_ok(x2, sel, layer, precision):
         return False
     return (fused_layer0_train_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
             or fused_layer0_chunked_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
-            or fused_layer0_dk192_ok(layer, x2.shape[0], x2.shape[1], sel.numel()))
+            or fused_layer0_dk192_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
+            or fused_layer0_dk256_ok(layer, x2.shape[0], x2.shape[1], sel.numel()))
 
 
 def _x3_train_weights(layer, hl=False):

@@ -30,6 +30,7 @@ EXTRA_FLAGS = {"sparse_attn_mfma.hip": ["-fno-honor-nans", "-fno-slp-vectorize"]
                "sparse_attn_x3_dk192.hip": ["-fno-honor-nans"], "sparse_attn_x3_dk192_chunks.hip": ["-fno-honor-nans"],
                "sparse_attn_x3_dk256.hip": ["-fno-honor-nans"], "sparse_attn_x3_dk256_chunks.hip": ["-fno-honor-nans"],
                "sparse_attn_mfma_dk256.hip": ["-fno-honor-nans"], "sparse_attn_mfma_dk256_chunks.hip": ["-fno-honor-nans"],
+               "sparse_attn_mfma_dk256_drop.hip": ["-fno-honor-nans"],
                "sparse_attn_x3p.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
                "sparse_attn_x3p_k2.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
                "sparse_attn_x3p_dk64.hip": ["-fno-honor-nans", "-fno-slp-vectorize"]}

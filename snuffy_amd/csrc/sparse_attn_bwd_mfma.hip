@@ -65,9 +65,18 @@ __device__ __forceinline__ float hi_f(unsigned u) { return __uint_as_float(u & 0
 // is 4 * quarter + ((c & 3) ^ ((r >> 2) & 3)): the quarter is a bijection of r & 3, and the rows of a group that agree in r & 3
 // ({0, 12, 20, 24}, {4, 8, 16, 28}, ...) have four different (r >> 2) & 3 -- 16 rows, 16 slots.  Everything is periodic in 16 rows
 // (16 * 384 bytes = 24 bank rows), which the fragment addresses below rely on.
+// 512-byte rows (DK = 256, the chunked kernel only) are TWO whole bank rows: every row starts at bank 0, and the 64-byte block at block
+// position b covers the bank quarter b mod 4 whatever the row.  Block cb goes to position (cb + (r & 3)) mod 8, a rotation over the
+// row's 8 blocks (the generic branch below would rotate by (r >> 1) & 1, the rule of 128-byte rows: rows r0 and r0 + 1 of a transpose-read
+// group would then share a quarter).  Transpose read: rows r0 .. r0 + 3 (r0 a multiple of 4) x the same block cb use the quarters cb,
+// cb + 1, cb + 2, cb + 3 (mod 4), and inside a quarter the 8 lanes of a row read its four 16-byte chunks in two 8-byte halves -- every
+// bank once.  ds_read_b128: the 16-byte slot (of 16 per bank row) is 4 * quarter + ((c & 3) ^ ((r >> 2) & 3)); all lanes of a service
+// group read the same chunk c, the quarter ((c >> 2) + (r & 3)) mod 4 is a bijection of r & 3, and the rows of a group that agree in
+// r & 3 ({0, 12, 20, 24}, {4, 8, 16, 28}, ...) have four different (r >> 2) & 3 -- 16 rows, 16 slots.  Periodic in 16 rows as well.
 template <int DK>
 __device__ __forceinline__ int img_pos(int row, int c) {
     if constexpr (DK == 192) return 4 * ((c >> 2) ^ ((row >> 1) & 1)) + ((c & 3) ^ ((row >> 2) & 3));
+    if constexpr (DK == 256) return 4 * (((c >> 2) + (row & 3)) & 7) + ((c & 3) ^ ((row >> 2) & 3));
     const int rot = DK == 128 ? (row & 3) : ((row >> 1) & 1);
     return 4 * (((c >> 2) + rot) & (DK / 32 - 1)) + ((c & 3) ^ ((row >> 2) & 3));
 }
@@ -423,7 +432,10 @@ int launch_bwd_nkb(const BwdParams& P, const BwdPlan& pl, hipStream_t s) {
 // series uses it once, so the single-chunk kernel's sign-bit memory has nothing to save here.
 // dk = 192: 4 waves (one per SIMD, 512 registers each).  A row's 6 accumulators (96 registers) next to the Q and V fragments (48 + 48 in
 // series B) and s / dp (32) do not fit the 256 registers of two waves per SIMD: series B spilled 63 - 119 registers that way.
-constexpr int ch_waves(int dk) { return dk == 192 ? 4 : 8; }
+// dk = 256: 4 waves for the same reason (8 accumulators = 128 registers, Q and V fragments 64 + 64, s / dp 32).
+constexpr int ch_waves(int dk) { return dk == 192 || dk == 256 ? 4 : 8; }
+// widths the single-launch kernel above is built for; the others (192, 256) run one chunk on the chunked kernel too
+constexpr bool bwd_single_launch(int dk) { return dk == 64 || dk == 128; }
 
 struct ChunkParams {
     BwdParams b;        // kp / dout point at the chunk's first key, b.k = keys of THIS chunk; mask / ds at column 0 of the full rows
@@ -570,7 +582,7 @@ __global__ __launch_bounds__(64 * ch_waves(DK), 1) void sparse_attn_bwd_chunk_ke
                 float pvv[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) pvv[e] = __builtin_amdgcn_exp2f(fmaf(s[4 * c4 + e], c_exp, -lse2));
-                if constexpr (SERIES == 1 && DK == 192) {
+                if constexpr (SERIES == 1 && !bwd_single_launch(DK)) {   // (64 and 128 keep the bits they always had)
                     // dS_j = (bf16(P_j M_j) dPd_j - P_j D) * scale.  D came out of series A as sum_j bf16(P_j M_j) dPd_j (bf16(P o M) is the
                     // MFMA operand of dV), so the first term carries the SAME rounded factor: sum_j dS_j = D - D sum_j P_j = 0 to fp32
                     // accuracy, and a row whose gradient cancels exactly (one key: P = 1, dS = 0) gives 0 instead of
@@ -679,8 +691,10 @@ __global__ __launch_bounds__(64 * ch_waves(DK), 1) void sparse_attn_bwd_chunk_ke
 // keys per chunk: as few chunks as the forward's make_chunks takes (224 keys at dk = 128, 256 at dk = 64, at most 8 chunks),
 // near-equal, every chunk start a multiple of 32.  dk = 192: two images of 32 nkb rows x 384 bytes fit 160 KiB up to nkb = 6
 // (144 KiB) = 192 keys per chunk -- fewer chunks than the forward's 128-key ones; the key range stays the forward's, k <= 8 * 128.
+// dk = 256: two images of 32 nkb rows x 512 bytes are 128 KiB at nkb = 4 (a fifth block would take all 160 KiB) = 128 keys per chunk,
+// the forward's figure: k <= 8 * 128 in at most 8 chunks.
 constexpr int CH_MAX_CHUNKS = 8;
-constexpr int bwd_chunk_kmax(int dk) { return dk == 64 ? 256 : dk == 128 ? 224 : dk == 192 ? 192 : 0; }
+constexpr int bwd_chunk_kmax(int dk) { return dk == 64 ? 256 : dk == 128 ? 224 : dk == 192 ? 192 : dk == 256 ? 128 : 0; }
 constexpr int bwd_chunk_klimit(int dk) { return dk == 192 ? 8 * 128 : CH_MAX_CHUNKS * bwd_chunk_kmax(dk); }
 inline bool make_bwd_chunks(int k, int dk, int* n_chunks, int* chunk_k) {
     const int kmax = bwd_chunk_kmax(dk);
@@ -747,7 +761,7 @@ int snf_sparse_attn_bwd_mfma_ex(const void* q, int64_t ldq, const void* v, int64
     BwdPlan pl;
     if (!make_bwd_plan(n, k, h, dk, &pl)) {
         snf::set_error("snf_sparse_attn_bwd_mfma: unsupported shape k=%d dk=%d (need dk == 128 with k <= 224 or dk == 64 "
-                       "with k <= 256)", k, dk);
+                       "with k <= 256; dk == 192 and dk == 256 run on snf_sparse_attn_bwd_mfma_chunked)", k, dk);
         return SNF_EUNSUPPORTED;
     }
     const int64_t d = (int64_t)h * dk;
@@ -790,8 +804,8 @@ int snf_sparse_attn_bwd_mfma_ex(const void* q, int64_t ldq, const void* v, int64
 
 size_t snf_sparse_attn_bwd_mfma_chunked_workspace_bytes(int64_t n, int k, int h, int dk, int dqv_dtype) {
     int nc, ck;
-    // one chunk is the single-launch kernel's (no workspace) -- except at dk = 192, which only the chunked kernel is built for
-    if (n < 1 || h < 1 || !make_bwd_chunks(k, dk, &nc, &ck) || (nc == 1 && dk != 192)) return 0;
+    // one chunk is the single-launch kernel's (no workspace) -- except at dk = 192 and 256, which only the chunked kernel is built for
+    if (n < 1 || h < 1 || !make_bwd_chunks(k, dk, &nc, &ck) || (nc == 1 && bwd_single_launch(dk))) return 0;
     const size_t dsum = ((size_t)h * n * sizeof(float) + 255) / 256 * 256;
     return dsum + (dqv_dtype == SNF_DT_BF16 ? 2 * chunked_acc_bytes(n, h, dk) : 0);   // D | fp32 dV | fp32 dQ
 }
@@ -804,10 +818,11 @@ int snf_sparse_attn_bwd_mfma_chunked(const void* q, int64_t ldq, const void* v, 
     int nc = 0, ck = 0;
     if (!make_bwd_chunks(k, dk, &nc, &ck)) {
         snf::set_error("snf_sparse_attn_bwd_mfma_chunked: unsupported shape k=%d dk=%d (need dk == 128 with k <= %d, dk == 64 with "
-                       "k <= %d or dk == 192 with k <= %d)", k, dk, bwd_chunk_klimit(128), bwd_chunk_klimit(64), bwd_chunk_klimit(192));
+                       "k <= %d, dk == 192 with k <= %d or dk == 256 with k <= %d)", k, dk, bwd_chunk_klimit(128), bwd_chunk_klimit(64),
+                       bwd_chunk_klimit(192), bwd_chunk_klimit(256));
         return SNF_EUNSUPPORTED;
     }
-    if (nc == 1 && dk != 192)   // one chunk: the single-launch kernel, bit for bit (dk = 192 has none: one launch per series below)
+    if (nc == 1 && bwd_single_launch(dk))   // one chunk: the single-launch kernel, bit for bit (dk = 192 / 256 have none: one launch per series below)
         return snf_sparse_attn_bwd_mfma_ex(q, ldq, v, ldv, qv_dtype, kp, dout, lse, mask, dropout_p, seed, offset, n, k, h, dk, scale, dq,
                                            dv, ldd, dqv_dtype, ds, ds_dtype, stream);
     SNF_REQUIRE(q && v && kp && dout && lse && dq && dv && ds, "snf_sparse_attn_bwd_mfma_chunked: null pointer");
@@ -879,6 +894,9 @@ int snf_sparse_attn_bwd_mfma_chunked(const void* q, int64_t ldq, const void* v, 
             else if (dk == 192)
                 rc = qv_dtype == SNF_DT_F32 ? launch_chunk_series<192, float>(C, series, (int)num_wg, s)
                                             : launch_chunk_series<192, unsigned short>(C, series, (int)num_wg, s);
+            else if (dk == 256)
+                rc = qv_dtype == SNF_DT_F32 ? launch_chunk_series<256, float>(C, series, (int)num_wg, s)
+                                            : launch_chunk_series<256, unsigned short>(C, series, (int)num_wg, s);
             else
                 rc = qv_dtype == SNF_DT_F32 ? launch_chunk_series<64, float>(C, series, (int)num_wg, s)
                                             : launch_chunk_series<64, unsigned short>(C, series, (int)num_wg, s);

@@ -52,10 +52,27 @@ constexpr int a256_lds_bytes(int nkb) {
     return (A256_DK / 16) * 1024 + A256_ROWS * p_row_bytes(nkb) + 2 * A256_ROWS * 2 * A256_DK + A256_WAVES * A256_ROWS * 8;
 }
 
+// Name of the kernel template below.  sparse_attn_mfma_dk256_drop.hip sets it (and SNF_ATTN_DK256_DROP) before it includes this header to
+// get the same text under a symbol of its own, with the attention dropout of training compiled in (the device of
+// SNF_ATTN_MFMA_KERNEL in sparse_attn_mfma_impl.h); with the defaults nothing about the existing kernels changes.
+#ifndef SNF_ATTN_DK256_KERNEL
+#define SNF_ATTN_DK256_KERNEL sparse_attn_mfma_dk256_kernel
+#endif
+#ifndef SNF_ATTN_DK256_DROP
+#define SNF_ATTN_DK256_DROP false
+#endif
+
 // MODE 0: one launch holds all keys.  MODE 1: statistics pass of one key chunk (P.stats_out).  MODE 2: main pass of one key chunk,
 // normalising with the statistics of all chunks (P.stats).  AUX: the attention matrix and / or lse are stored.
+// SNF_ATTN_DK256_DROP (single bag, AUX, MODE 0 | 2): the normalised fp32 P is multiplied by the Philox keep-mask / (1 - p) of its 4 keys
+// (philox.h; keyed on the key index among ALL keys, P.key0 + ..., and the total key count P.attn_ld) before it is stored and rounded for
+// GEMM2 -- lse and the statistics do not see the mask.  The main passes keep the chunks of the launch without dropout: this kernel forms
+// P as exp2(s - block max) * (exp2(block max - row max) / row sum), which depends on WHICH 32 keys share a block, so chunks moved to
+// multiples of 4 (the 64 / 128 / 192 family's way, whose P is relative to the row max alone) would change P in its last bit.
 template <int NKB, bool AUX, int MODE, bool VL = false>
-__global__ __launch_bounds__(A256_THREADS, 1) void sparse_attn_mfma_dk256_kernel(AttnParams PA) {
+__global__ __launch_bounds__(A256_THREADS, 1) void SNF_ATTN_DK256_KERNEL(AttnParams PA) {
+    constexpr bool DROP = SNF_ATTN_DK256_DROP;
+    static_assert(!DROP || (AUX && !VL && MODE != 1), "the dropout form: single bag, one launch or main pass");
     constexpr int DK = A256_DK, ROWS = A256_ROWS, NTH = A256_THREADS;
     constexpr int NKS = DK / 16;               // k-steps of GEMM1
     static_assert(NKB == 1 || NKB == 2 || NKB == 4, "one wave per key block, an even share of the column blocks");
@@ -350,6 +367,21 @@ __global__ __launch_bounds__(A256_THREADS, 1) void sparse_attn_mfma_dk256_kernel
                 f32x4 p4 = {s[4 * c4] * fscale, s[4 * c4 + 1] * fscale, s[4 * c4 + 2] * fscale, s[4 * c4 + 3] * fscale};
                 // the fp32 P is pinned here in every variant: the variants that store A and those that do not round the same values
                 asm volatile("" : "+v"(p4));
+                if constexpr (DROP) {
+                    // one Philox call covers the 4 keys 4 g .. 4 g + 3 among ALL keys.  A chunk that starts on a multiple of 4 (every
+                    // one-launch forward) has this lane's 4 keys in one group; otherwise they straddle two groups by sh = key0 & 3
+                    // (wave-uniform) and both are drawn.  (A group past the row's last only meets padded keys, whose P is 0.)
+                    const int g0 = P.key0 + 32 * w + 8 * c4 + 4 * hf, sh = MODE == 2 ? (P.key0 & 3) : 0;
+                    const int64_t mrow = rvalid ? row : n32 - 1;
+                    const snf::philox_f4 lo = snf::dropout_mask4(P.drop, a, P.n, mrow, (int)P.attn_ld, g0);
+                    f32x4 mk = {lo[0], lo[1], lo[2], lo[3]};
+                    if (sh) {
+                        const snf::philox_f4 hi = snf::dropout_mask4(P.drop, a, P.n, mrow, (int)P.attn_ld, g0 + 4);
+                        mk = sh == 1 ? f32x4{lo[1], lo[2], lo[3], hi[0]} : sh == 2 ? f32x4{lo[2], lo[3], hi[0], hi[1]}
+                                                                                  : f32x4{lo[3], hi[0], hi[1], hi[2]};
+                    }
+                    p4 *= mk;
+                }
                 if constexpr (AUX) {
                     if (arow && rvalid) {
                         const int key0 = 32 * w + 8 * c4 + 4 * hf;
@@ -409,7 +441,7 @@ struct A256 {
     static constexpr const char *DK_TEXT = "256", *NAME = "sparse_attn_mfma_dk256", *KERNEL = "sparse_attn_mfma_dk256_kernel";
     static constexpr int lds_bytes(int nkb) { return a256_lds_bytes(nkb); }
     template <int NKB, bool AUX, int MODE, bool VL>
-    static auto kernel() { return sparse_attn_mfma_dk256_kernel<NKB, AUX, MODE, VL>; }
+    static auto kernel() { return SNF_ATTN_DK256_KERNEL<NKB, AUX, MODE, VL>; }
     static int launch_chunk(int mode, const AttnParams& P, const Plan& pl, float* out, hipStream_t s) {
         return snf::attn_dk256_launch_chunk(mode, P, pl, out, s);
     }

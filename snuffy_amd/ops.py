@@ -678,7 +678,8 @@ def sparse_attn_bwd_mfma(q, v, kp, dout, lse, h, mask=None, scale=None, dropout=
     """MFMA backward (bf16 operands): (dq [n,d] f32, dkp [k,d] f32, dv [n,d] f32) from q, v (f32 or bf16, row-strided views
     allowed), kp [k,d] f32, dout [k,d] f32 and the forward's lse [h,n].  mask: dropout keep-mask / (1 - p) or None.
     fused_bf16_grads: dq and dv are the two column halves of ONE bf16 buffer [n, 2 d] (returned as views of it).
-    More keys than one launch holds (mfma_attn_bwd_supported) run over key chunks, snf_sparse_attn_bwd_mfma_chunked."""
+    More keys than one launch holds (mfma_attn_bwd_supported) run over key chunks, snf_sparse_attn_bwd_mfma_chunked; so does every
+    key count at head widths 192 and 256 (mfma_attn_dk192_supported, mfma_attn_dk256_train_supported)."""
     if q.dtype not in (torch.float32, torch.bfloat16) or v.dtype != q.dtype:
         raise TypeError("sparse_attn_bwd_mfma: q and v must both be float32 or both bfloat16")
     q = _rows16(q, "q")
@@ -706,8 +707,8 @@ def sparse_attn_bwd_mfma(q, v, kp, dout, lse, h, mask=None, scale=None, dropout=
     ds = torch.empty(h, n, k, dtype=torch.bfloat16 if bf16 else torch.float32, device=q.device)
     dt = DT_F32 if q.dtype == torch.float32 else DT_BF16
     pdrop, seed, offset = dropout if dropout is not None else (0.0, 0, 0)
-    # one chunk (or the library's own refusal); dk = 192 is built into the chunked kernel only, whatever the key count
-    if dk != 192 and (mfma_attn_bwd_supported(k, dk) or not mfma_attn_train_chunks_supported(k, dk)):
+    # one chunk (or the library's own refusal); dk = 192 and 256 are built into the chunked kernel only, whatever the key count
+    if dk not in (192, 256) and (mfma_attn_bwd_supported(k, dk) or not mfma_attn_train_chunks_supported(k, dk)):
         check(lib.snf_sparse_attn_bwd_mfma_ex(_p(q), q.stride(0), _p(v), v.stride(0), dt, _p(kp), _p(dout), _p(lse), _p(mask),
                                               float(pdrop), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), n, k, h, dk,
                                               float(scale), _p(dq), _p(dv), ldd, gdt, _p(ds), DT_BF16 if bf16 else DT_F32, _stream()),
@@ -771,13 +772,22 @@ def mfma_attn_dk192_supported(k, n=None, ld=None):
 
 def mfma_attn_dk256_supported(k, n=None, ld=None):
     """Shapes the bf16 MFMA attention takes at head width 256 (snf_sparse_attn_fwd_mfma_dk256; the README's SimCLR ResNet-18 recipe:
-    D = 512, h = 2, Lambda = 900), forward only: one launch holds 128 keys, up to 8 key chunks.  n / ld as in mfma_attn_supported.
-    mfma_attn_supported() keeps answering for dk = 64 / 128 only."""
+    D = 512, h = 2, Lambda = 900), forward: one launch holds 128 keys, up to 8 key chunks.  n / ld as in mfma_attn_supported.
+    mfma_attn_supported() keeps answering for dk = 64 / 128 only.  Training: mfma_attn_dk256_train_supported."""
     return _wide_attn_supported(k, n, ld)
 
 
-def _sparse_attn_fwd_mfma_wide(dk, q, v, kp, h, scale, need_attn, need_lse):
-    """The bf16 single-bag forward of a native head width (snf_sparse_attn_fwd_mfma_dk<dk>)."""
+def mfma_attn_dk256_train_supported(k, n=None, ld=None):
+    """Shapes the bf16 MFMA attention TRAINS at at head width 256: the forward with in-kernel Philox dropout
+    (sparse_attn_fwd_mfma_dk256(dropout=...), snf_sparse_attn_fwd_mfma_dk256_dropout) and the backward over key chunks of up to 128 keys
+    (sparse_attn_bwd_mfma, snf_sparse_attn_bwd_mfma_chunked) -- the forward's key range, 1 <= k <= 8 x 128.  n / ld as in
+    mfma_attn_supported (the backward addresses rows in 64 bits; the forward sets the limit)."""
+    return _wide_attn_supported(k, n, ld)
+
+
+def _sparse_attn_fwd_mfma_wide(dk, q, v, kp, h, scale, need_attn, need_lse, dropout=None):
+    """The bf16 single-bag forward of a native head width (snf_sparse_attn_fwd_mfma_dk<dk>; dropout = (p, seed, offset): its _dropout
+    form, which needs lse or attn)."""
     me = "sparse_attn_fwd_mfma_dk%d" % dk
     if q.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
         raise TypeError("%s: q and v must be bfloat16" % me)
@@ -801,16 +811,23 @@ def _sparse_attn_fwd_mfma_wide(dk, q, v, kp, h, scale, need_attn, need_lse):
     lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
     ws = _ws(wsb, q.device)
     kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
+    if dropout is not None:
+        pdrop, seed, offset = dropout
+        check(getattr(lib, "snf_%s_dropout" % me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, n, k, h, float(scale), _p(out), _p(attn),
+                                                  _p(lse), _p(ws), wsb, _stream(), float(pdrop), int(seed) & (2 ** 64 - 1),
+                                                  int(offset) & (2 ** 64 - 1)), "snf_%s_dropout" % me)
+        return out, attn, lse
     check(getattr(lib, "snf_" + me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, n, k, h, float(scale), _p(out), _p(attn), _p(lse),
                                     _p(ws), wsb, _stream()), "snf_" + me)
     return out, attn, lse
 
 
-def sparse_attn_fwd_mfma_dk256(q, v, kp, h, scale=None, need_attn=False, need_lse=False):
+def sparse_attn_fwd_mfma_dk256(q, v, kp, h, scale=None, need_attn=False, need_lse=False, dropout=None):
     """bf16 sparse attention on the matrix cores at head width 256 (snf_sparse_attn_fwd_mfma_dk256): q, v [n, 256 h] bf16 (row-strided
     views allowed: the halves of a fused [Q | V] projection), kp [k, 256 h] f32 or bf16 (the same bits either way)
-    -> (out [k, d] f32, attn [h, n, k] or None, lse [h, n] or None).  Inference only."""
-    return _sparse_attn_fwd_mfma_wide(256, q, v, kp, h, scale, need_attn, need_lse)
+    -> (out [k, d] f32, attn [h, n, k] or None, lse [h, n] or None).  dropout = (p, seed, offset): the training form
+    (snf_sparse_attn_fwd_mfma_dk256_dropout) -- the Philox mask in registers, attn = P o M, lse that of P; it needs need_lse or need_attn."""
+    return _sparse_attn_fwd_mfma_wide(256, q, v, kp, h, scale, need_attn, need_lse, dropout)
 
 
 def mfma_attn_dropout_supported(k, dk):
