@@ -32,7 +32,7 @@
 //            bank-row aligned): 128 contiguous bytes, every bank once.  (The argument of sparse_attn_x3_dk256_impl.h: the image is the same)
 //   LDS      4 key blocks: Q 16 KiB | P 10 KiB | V 2 x 16 KiB | statistics 1 KiB = 59 KiB.  V is DOUBLE-buffered: rows are fetched two
 //            tiles ahead into registers and written one tile ahead while the current tile's P is published.
-// Register and scratch figures of every form: DESIGN.md section 4, tests/test_attn_dk256_host.py.
+// Register and scratch figures of every form: DESIGN.md section 4, tests/test_attn_widths_host.py.
 #include "sparse_attn_mfma_impl.h"
 #include "attn_width.h"
 

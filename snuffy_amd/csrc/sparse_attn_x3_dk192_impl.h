@@ -20,7 +20,7 @@
 //            SINGLE-buffered (a second buffer would need 188 KiB): the next tile's V rows are written after GEMM2 behind a fourth
 //            workgroup barrier (B4), its Q rows just before it.  Both leave HBM after B2 of the tile before, so they are in flight under
 //            the softmax and GEMM2 and out of the registers during GEMM1 (the statistics pass, which has the room, fetches two tiles
-//            ahead as the 64 / 128 body does).  Scratch figures of every form: DESIGN.md section 4, tests/test_x3_dk192_host.py.
+//            ahead as the 64 / 128 body does).  Scratch figures of every form: DESIGN.md section 4, tests/test_attn_widths_host.py.
 #include "sparse_attn_x3_impl.h"
 #include "attn_width.h"
 

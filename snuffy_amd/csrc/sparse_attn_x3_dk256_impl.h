@@ -29,7 +29,7 @@
 //   LDS      32-row tiles, 4 key blocks: Q hi+lo 32 KiB | P hi+lo 20 KiB | V 2 x (hi+lo) 64 KiB | statistics 1 KiB = 117 KiB of 160.  V is
 //            DOUBLE-buffered, so the staging is that of the 64 / 128 body: rows fetched two tiles ahead into registers, split and written
 //            one tile ahead while the current tile's P is published; three workgroup barriers per tile.
-// Register and scratch figures of every form: DESIGN.md section 4, tests/test_x3_dk256_host.py.
+// Register and scratch figures of every form: DESIGN.md section 4, tests/test_attn_widths_host.py.
 #include "sparse_attn_x3_impl.h"
 #include "attn_width.h"
 

@@ -8,37 +8,16 @@ import sys
 import pytest
 import torch
 
+from tests.attn_widths import F32_NKB4_SCRATCH, TRAIN_192 as ROW, _layer
+from tests.attn_widths import stubbed_width as stubbed  # noqa: F401  (a fixture; it reads the row fixture below)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-# Scratch bytes per lane the dk = 192 kernels may use (tools/scan_spills.py on the build of the commit that added them).  Everything on
-# the model's path -- bf16 Q | V operands, every key-block count, the statistics pass, the backward over chunks -- spills nothing.
-# The f32-operand forward at 4 key blocks does: a pooling wave keeps 12 V-row loads of 8 floats in flight (96 registers, converted to
-# bf16 only on arrival) next to its 96 accumulator registers, which does not fit the 256 registers of two waves per SIMD; the spill code
-# sits around the once-per-tile V publish, not inside the MFMA loops.  Measured: 92 bytes with the attention / lse outputs, 108 without.
-F32_NKB4_SCRATCH = {True: 92, False: 108}
-
-
-class _Lib:
-    @staticmethod
-    def snf_device_cu_count():
-        return 256
-
-
-def _layer(d, h, lam, enc_drop, act="relu"):
-    from tests.helpers import build_amd_milnet
-    net = build_amd_milnet(d, h, act, lam, 0.0, 1, enc_drop=enc_drop)
-    return net.b_classifier.encoder.layers[0]
-
 
 @pytest.fixture
-def stubbed(monkeypatch):
-    from snuffy_amd import autograd as SA
-    from snuffy_amd import ops
-    monkeypatch.setattr(ops._ffi, "load", lambda: _Lib)
-    monkeypatch.setattr(SA, "FUSED_BF16_TRAINING", True)
-    monkeypatch.setattr(SA, "FUSED_BF16_DK192", True)                     # the switch under test, whatever its shipped default
-    return SA
+def row():
+    return ROW
 
 
 def test_dk192_predicate_of_ops():

@@ -8,46 +8,18 @@ import sys
 import pytest
 import torch
 
+from tests.attn_widths import BWD_TABLE, DROP_TABLE, TRAIN_256 as ROW, _layer, _nkb
+from tests.attn_widths import stubbed_width as stubbed  # noqa: F401  (a fixture; it reads the row fixture below)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 KMAX, MAX_CHUNKS = 128, 8
 
-# (VGPRs, scratch bytes per lane) of sparse_attn_mfma_dk256_drop_kernel<NKB, true, MODE, false> (tools/scan_spills.py on the build that
-# added them; DESIGN section 4 has the table): the Philox state and the mask cost 4 - 20 registers over the forms without dropout.
-DROP_TABLE = {(1, 0): (252, 0), (2, 0): (296, 0), (4, 0): (432, 0), (2, 2): (312, 0), (4, 2): (440, 0)}
-# sparse_attn_bwd_chunk_kernel<256, QT, SERIES, FAST>.  The bf16-operand forms (the model's) spill nothing.  Series B with f32 operands
-# does: its Q and V fragments are loaded as fp32 (twice the registers in flight until they are converted) next to 128 accumulator
-# registers.  It is held to the 368 bytes measured on the build that added it (the model passes bf16 operands; the f32-operand forms
-# serve fp32 callers and the tests' dS checks).
-BWD_TABLE = {("float", 0, False): (466, 0), ("float", 1, False): (512, 368), ("unsigned short", 0, False): (437, 0),
-             ("unsigned short", 1, False): (478, 0), ("unsigned short", 1, True): (475, 0)}
-
-
-class _Lib:
-    @staticmethod
-    def snf_device_cu_count():
-        return 256
-
-
-def _layer(d, h, lam, enc_drop, act="relu"):
-    from tests.helpers import build_amd_milnet
-    net = build_amd_milnet(d, h, act, lam, 0.0, 1, enc_drop=enc_drop)
-    return net.b_classifier.encoder.layers[0]
-
 
 @pytest.fixture
-def stubbed(monkeypatch):
-    from snuffy_amd import autograd as SA
-    from snuffy_amd import ops
-    monkeypatch.setattr(ops._ffi, "load", lambda: _Lib)
-    monkeypatch.setattr(SA, "FUSED_BF16_TRAINING", True)
-    monkeypatch.setattr(SA, "FUSED_BF16_DK256", True)                     # the switch under test, whatever its shipped default
-    return SA
-
-
-def _nkb(kc):
-    return next(o for o in (1, 2, 4) if 32 * o >= kc)
+def row():
+    return ROW
 
 
 def test_main_pass_chunks_for_every_key_count():

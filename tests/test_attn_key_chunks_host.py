@@ -5,34 +5,14 @@ import ctypes
 import os
 import re
 
-import pytest
 import torch
+
+from tests.attn_widths import _layer, stubbed  # noqa: F401  (stubbed is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "snuffy_hip.h")
 
 NEW = {"snf_sparse_attn_bwd_mfma_chunked": 26, "snf_sparse_attn_bwd_mfma_chunked_workspace_bytes": 5}
-
-
-class _Lib:
-    @staticmethod
-    def snf_device_cu_count():
-        return 256
-
-
-def _layer(d, h, lam, enc_drop, act="relu"):
-    from tests.helpers import build_amd_milnet
-    net = build_amd_milnet(d, h, act, lam, 0.0, 1, enc_drop=enc_drop)
-    return net.b_classifier.encoder.layers[0]
-
-
-@pytest.fixture
-def stubbed(monkeypatch):
-    from snuffy_amd import autograd as SA
-    from snuffy_amd import ops
-    monkeypatch.setattr(ops._ffi, "load", lambda: _Lib)
-    monkeypatch.setattr(SA, "FUSED_BF16_TRAINING", True)
-    return SA
 
 
 def test_new_entry_points_header_ctypes_and_exports_agree():

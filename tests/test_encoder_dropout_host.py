@@ -9,6 +9,9 @@ import sys
 import pytest
 import torch
 
+from tests.attn_widths import _layer
+from tests.attn_widths import stubbed_x3 as stubbed  # noqa: F401  (a fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "snuffy_hip.h")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -32,32 +35,6 @@ def test_new_entry_points_header_ctypes_and_exports_agree():
         args = _ffi.SIGNATURES[name][1]
         i = args.index(ctypes.c_float)
         assert args[i + 1:i + 3] == [ctypes.c_uint64, ctypes.c_uint64], name
-
-
-class _Lib:
-    @staticmethod
-    def snf_device_cu_count():
-        return 256
-
-
-def _layer(d, h, lam, enc_drop):
-    from tests.helpers import build_amd_milnet
-    net = build_amd_milnet(d, h, "relu", lam, 0.0, 1, enc_drop=enc_drop)
-    return net.b_classifier.encoder.layers[0]
-
-
-@pytest.fixture
-def stubbed(monkeypatch):
-    from snuffy_amd import autograd as SA
-    from snuffy_amd import functional as SF
-    from snuffy_amd import ops
-    monkeypatch.setattr(ops._ffi, "load", lambda: _Lib)
-    monkeypatch.setattr(ops, "GEMM_HL", True)
-    monkeypatch.setattr(ops, "GEMM_TN", True)
-    monkeypatch.setattr(SA, "X3_TRAIN_HL", True)
-    monkeypatch.setattr(SA, "FUSED_X3_TRAINING", True)
-    monkeypatch.setattr(SF, "FP32_GEMM", "x3")
-    return SA
 
 
 def test_fused_chain_takes_encoder_dropout_where_the_one_pass_chain_applies(stubbed, monkeypatch):

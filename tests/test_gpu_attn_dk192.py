@@ -10,28 +10,21 @@ import pytest
 import torch
 
 from oracle import snuffy_oracle as orc
-from tests.helpers import ReplayRNG, build_amd_milnet, rel_err
-from tests.test_gpu_kernels import attn_ref
-from tests.test_gpu_model import TOL, synth_state
-from tests.test_gpu_attn_key_chunks import _c_backward, _close, _qv, _ref, bf16r
-from tests.test_gpu_encoder_dropout import _perturbed_state_dict
-from tests.test_gpu_encoder_dropout_bf16 import _parity, _run
+from tests.attn_widths import DROP_OFFSET, DROP_SEED, P_DROP, TRAIN_192 as ROW
+from tests.helpers import (TOL, ReplayRNG, _c_backward, _ops, _parity, _perturbed_state_dict, _qv, _ref, _run, attn_ref, bf16r,
+                           build_amd_milnet, rel_err, synth_state)
+from tests.helpers import grad_close as _close
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BF = torch.bfloat16
-DK = 192
+DK = ROW.dk
 
 # (n, k, h): smallest possible; one partly filled tile, one key block; two row tiles, 4th key block partly filled; exactly one full
 # chunk; two chunks, the second nearly empty (2 key blocks); the recipe's keys and heads; eight full chunks
-SHAPES = [(1, 1, 1), (33, 7, 2), (130, 97, 1), (777, 128, 4), (300, 129, 2), (1000, 500, 4), (257, 1024, 1)]
+SHAPES = ROW.SHAPES
 # more row tiles than compute units: workgroups straddle heads
-BIG = (40000, 200, 4)
-
-
-def _ops():
-    from snuffy_amd import ops
-    return ops
+BIG = ROW.BIG
 
 
 @pytest.mark.parametrize("n,k,h,dt", [s + (dt,) for s in SHAPES for dt in ("f32", "bf16")] + [BIG + ("bf16",)])
@@ -39,13 +32,13 @@ def test_forward(n, k, h, dt):
     """The checks of test_sparse_attn_mfma at dk = 192.  Before the dk = 192 kernels the first call raises the library's "unsupported
     shape" error."""
     ops = _ops()
-    assert ops.mfma_attn_dk192_supported(k, n, 2 * h * DK)
+    assert getattr(ops, ROW.supported)(k, n, 2 * h * DK)
     g = torch.Generator().manual_seed(n * 3 + k)
     d = h * DK
     q, kp, v = torch.randn(n, d, generator=g), torch.randn(k, d, generator=g), torch.randn(n, d, generator=g)
     tdt = torch.float32 if dt == "f32" else BF
     qd, vd = _qv(q, v, dt)                                                   # row-strided halves of one [n, 2d] buffer
-    o, attn, lse = ops.sparse_attn_fwd_mfma(qd, vd, kp.to(DEV), n, h, need_attn=True, need_lse=True)
+    o, attn, lse = getattr(ops, ROW.single)(qd, vd, kp.to(DEV), n, h, need_attn=True, need_lse=True)
     # (a) against the exact oracle: bf16-class tolerance
     o_ref, p_ref = attn_ref(q, kp, v, h)
     assert (attn.cpu().double() - p_ref).abs().max() < 1e-2
@@ -61,19 +54,19 @@ def test_forward(n, k, h, dt):
     s_r = (bf16r(q).double().view(n, h, DK).transpose(0, 1) @ bf16r(kp).double().view(k, h, DK).transpose(0, 1).transpose(1, 2)) / DK ** 0.5
     assert (lse.cpu().double() - torch.logsumexp(s_r, -1)).abs().max() < 1e-3
     # run-to-run determinism, contiguous operands
-    o2, attn2, _ = ops.sparse_attn_fwd_mfma(q.to(DEV).to(tdt), v.to(DEV).to(tdt), kp.to(DEV), n, h, need_attn=True)
+    o2, attn2, _ = getattr(ops, ROW.single)(q.to(DEV).to(tdt), v.to(DEV).to(tdt), kp.to(DEV), n, h, need_attn=True)
     assert torch.equal(o2, o) and torch.equal(attn2, attn)
     # without materialising A (need_attn=False, with and without lse) the output is the same
-    o3, a3, l3 = ops.sparse_attn_fwd_mfma(qd, vd, kp.to(DEV), n, h)
+    o3, a3, l3 = getattr(ops, ROW.single)(qd, vd, kp.to(DEV), n, h)
     assert a3 is None and l3 is None and (torch.equal(o3, o) or rel_err(o3.cpu(), o.cpu()) < 2e-3)
-    o5, a5, l5 = ops.sparse_attn_fwd_mfma(qd, vd, kp.to(DEV), n, h, need_attn=False, need_lse=True)
+    o5, a5, l5 = getattr(ops, ROW.single)(qd, vd, kp.to(DEV), n, h, need_attn=False, need_lse=True)
     assert a5 is None and torch.equal(l5, lse) and torch.equal(o5, o)
     # a bf16 Kp is read as it is: same bits as the library's own round-to-nearest-even of the f32 Kp
-    o4, a4, _ = ops.sparse_attn_fwd_mfma(qd, vd, kp.to(DEV).to(BF), n, h, need_attn=True)
+    o4, a4, _ = getattr(ops, ROW.single)(qd, vd, kp.to(DEV).to(BF), n, h, need_attn=True)
     assert torch.equal(o4, o) and torch.equal(a4, attn)
 
 
-@pytest.mark.parametrize("n,k,h,dt", [(130, 97, 1, "f32"), (300, 300, 2, "bf16"), (1000, 500, 4, "bf16")])
+@pytest.mark.parametrize("n,k,h,dt", ROW.DROP_SHAPES)
 def test_dropout_forward_and_backward(n, k, h, dt):
     """test_dropout_over_key_chunks_forward_and_backward at dk = 192: lse is the undropped forward's, A = P o M bit for bit with the host
     Philox mask, O within 3e-3 of fp64 with that mask; the backward with (p, seed, offset) equals the backward fed with the mask tensor,
@@ -81,14 +74,14 @@ def test_dropout_forward_and_backward(n, k, h, dt):
     key index among all keys."""
     from oracle import philox_ref
     ops = _ops()
-    p_drop, seed, offset = 0.1, 987654321, 5
+    p_drop, seed, offset = P_DROP, DROP_SEED, DROP_OFFSET
     g = torch.Generator().manual_seed(n + k)
     d = h * DK
     q, kp, v, dout = (torch.randn(s, d, generator=g) for s in (n, k, n, k))
     qd_, vd_ = _qv(q, v, dt)
     mask = torch.from_numpy(philox_ref.dropout_mask(h, n, k, p_drop, seed, offset))
-    o, attn, lse = ops.sparse_attn_fwd_mfma(qd_, vd_, kp.to(DEV), n, h, need_attn=True, need_lse=True, dropout=(p_drop, seed, offset))
-    o0, attn0, lse0 = ops.sparse_attn_fwd_mfma(qd_, vd_, kp.to(DEV), n, h, need_attn=True, need_lse=True)
+    o, attn, lse = getattr(ops, ROW.single)(qd_, vd_, kp.to(DEV), n, h, need_attn=True, need_lse=True, dropout=(p_drop, seed, offset))
+    o0, attn0, lse0 = getattr(ops, ROW.single)(qd_, vd_, kp.to(DEV), n, h, need_attn=True, need_lse=True)
     assert torch.equal(lse, lse0)
     assert torch.equal(attn.cpu(), attn0.cpu() * mask)
     qr, kr, vr = bf16r(q), bf16r(kp), bf16r(v)
@@ -96,7 +89,7 @@ def test_dropout_forward_and_backward(n, k, h, dt):
     p_r = torch.softmax(qh @ kh.transpose(1, 2) / DK ** 0.5, dim=-1)
     o_r = ((p_r * mask.double()).transpose(1, 2) @ vh).transpose(0, 1).reshape(k, d)
     err_o = rel_err(o.cpu(), o_r)
-    o1, _, _ = ops.sparse_attn_fwd_mfma(qd_, vd_, kp.to(DEV), n, h, need_attn=False, need_lse=True, dropout=(p_drop, seed, offset))
+    o1, _, _ = getattr(ops, ROW.single)(qd_, vd_, kp.to(DEV), n, h, need_attn=False, need_lse=True, dropout=(p_drop, seed, offset))
     assert torch.equal(o1, o)
     dq, dkp, dv = ops.sparse_attn_bwd_mfma(qd_, vd_, kp.to(DEV), dout.to(DEV), lse, h, dropout=(p_drop, seed, offset))
     dq2, dkp2, dv2 = ops.sparse_attn_bwd_mfma(qd_, vd_, kp.to(DEV), dout.to(DEV), lse, h, mask=mask.to(DEV))
@@ -124,7 +117,7 @@ def test_backward(n, k, h, dt, drop):
     mask = (torch.rand(h, n, k, generator=g) >= drop).float() / (1.0 - drop) if drop > 0 else None
     mask_d = None if mask is None else mask.to(DEV)
     qd_, vd_ = _qv(q, v, dt)
-    _, _, lse = ops.sparse_attn_fwd_mfma(qd_, vd_, kp.to(DEV), n, h, need_lse=True)
+    _, _, lse = getattr(ops, ROW.single)(qd_, vd_, kp.to(DEV), n, h, need_lse=True)
     dq, dkp, dv = ops.sparse_attn_bwd_mfma(qd_, vd_, kp.to(DEV), dout.to(DEV), lse, h, mask=mask_d)
     print("dk192 backward %s %s drop %.2f" % ((n, k, h), dt, drop))
     rq, rk, rv, pdp = _ref(bf16r(q), bf16r(kp), bf16r(v), bf16r(dout), h, mask)
@@ -155,7 +148,7 @@ def test_single_launch_backward_keeps_refusing_dk192():
     g = torch.Generator().manual_seed(0)
     q, kp, v, dout = (torch.randn(s, h * DK, generator=g) for s in (n, k, n, k))
     qd_, vd_ = _qv(q, v, "bf16")
-    _, _, lse = ops.sparse_attn_fwd_mfma(qd_, vd_, kp.to(DEV), n, h, need_lse=True)
+    _, _, lse = getattr(ops, ROW.single)(qd_, vd_, kp.to(DEV), n, h, need_lse=True)
     with pytest.raises(Exception, match="unsupported shape"):
         _c_backward("ex", qd_, vd_, kp.to(DEV), dout.to(DEV), lse, h)
 
@@ -167,7 +160,7 @@ def test_model_inference_on_the_dk192_route(monkeypatch):
     attention launch), bit-identical run to run, inside the same bound, and the new route is within TOL["bf16"] of it."""
     from snuffy_amd import functional as SF
     from snuffy_amd import ops
-    N, D, h, lam, r = 3000, 768, 4, 500, 0.5
+    N, D, h, lam, r = 3000, ROW.D, ROW.H, ROW.LAM, 0.5
     net = synth_state(D, h, 1)
     layer = net.b_classifier.encoder.layers[0]
     layer.big_lambda, layer.random_patch_share, layer.top_big_lambda_share = lam, r, 1.0 - r
@@ -194,11 +187,11 @@ def test_model_inference_on_the_dk192_route(monkeypatch):
         assert (A.sum(-1) - 1).abs().max() < 1e-4
         return logits, A
 
-    monkeypatch.setattr(SF, "MFMA_ATTN_DK192", True)
+    monkeypatch.setattr(SF, ROW.single_switch, True)
     logits, A = run()
     assert calls == [(lam, D)] and not exact                              # the MFMA attention, no fp32 copies into the exact kernel
     del calls[:]
-    monkeypatch.setattr(SF, "MFMA_ATTN_DK192", False)
+    monkeypatch.setattr(SF, ROW.single_switch, False)
     logits0, A0 = run()
     logits1, A1 = run()
     assert not calls and exact == [torch.float32, torch.float32]          # the previous routing
@@ -214,9 +207,9 @@ def test_chain_at_dk192_matches_the_restated_layer(sites, monkeypatch):
     N = 3000 against the plain-torch restatement, with the bounds and the widening rule of tests/test_gpu_encoder_dropout_bf16.py; then,
     with FUSED_BF16_DK192 off, the same step takes the generic chain."""
     from snuffy_amd import autograd as SA
-    n, d, h, lam = 3000, 768, 4, 500
+    n, d, h, lam = 3000, ROW.D, ROW.H, ROW.LAM
     assert d // h == DK
-    monkeypatch.setattr(SA, "FUSED_BF16_DK192", True)
+    monkeypatch.setattr(SA, ROW.train_switch, True)
     _parity(monkeypatch, n, d, h, lam, sites=sites)
     calls = []
     real_apply = SA.EncoderLayer0Bf16Fn.apply
@@ -229,7 +222,7 @@ def test_chain_at_dk192_matches_the_restated_layer(sites, monkeypatch):
     for k_, g_ in grads.items():                                          # parameter gradient shapes are unchanged
         assert g_.shape == params[k_].shape and bool(torch.isfinite(g_).all()), k_
     del calls[:]
-    monkeypatch.setattr(SA, "FUSED_BF16_DK192", False)
+    monkeypatch.setattr(SA, ROW.train_switch, False)
     _, grads0, logits0 = _run(monkeypatch, sd, x, d, h, lam, "bf16", 0.0, sites=sites)
     assert not calls and bool(torch.isfinite(logits0).all())
     assert sorted(grads0) == sorted(grads)
@@ -240,13 +233,13 @@ def test_stepper_step_takes_the_chain_at_dk192_and_the_switch_takes_it_out(monke
     finite, the state_dict keeps its keys and shapes; with FUSED_BF16_DK192 off the same step takes the generic chain."""
     from snuffy_amd import autograd as SA
     from snuffy_amd.train import BagParallelStepper
-    n, d, h, lam = 3000, 768, 4, 500
+    n, d, h, lam = 3000, ROW.D, ROW.H, ROW.LAM
     sd = _perturbed_state_dict(n, d, h, lam)
     calls = []
     real_apply = SA.EncoderLayer0Bf16Fn.apply
     monkeypatch.setattr(SA.EncoderLayer0Bf16Fn, "apply", lambda *a: (calls.append(1), real_apply(*a))[1])
     for on in (True, False):
-        monkeypatch.setattr(SA, "FUSED_BF16_DK192", on)
+        monkeypatch.setattr(SA, ROW.train_switch, on)
         net = build_amd_milnet(d, h, "relu", lam, 0.5, 1, enc_drop=0.1)
         net.load_state_dict(sd, strict=True)
         net = net.to(DEV)

@@ -9,35 +9,29 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import build_amd_milnet, rel_err
-from tests.test_gpu_attn_key_chunks import _c_backward, _close, _qv, _ref, bf16r
-from tests.test_gpu_encoder_dropout import _perturbed_state_dict
-from tests.test_gpu_encoder_dropout_bf16 import _parity
+from tests.attn_widths import DROP_OFFSET, DROP_SEED, P_DROP, TRAIN_256 as ROW
+from tests.helpers import _c_backward, _ops, _parity, _perturbed_state_dict, _qv, _ref, bf16r, build_amd_milnet, rel_err
+from tests.helpers import grad_close as _close
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BF = torch.bfloat16
-DK = 256
+DK = ROW.dk
 
 # (n, k, h): smallest possible; one key block with a tail; two blocks, row-tile tail; four blocks, k % 4 != 0 (the scalar dS path);
 # exactly one chunk; two chunks (forward 65 + 64: the second starts at key 65, off a multiple of 4; backward 96 + 33); the recipe's
 # keys (forward 7 chunks of 113 and one of 109, starts at every residue mod 4; backward 7 x 128 + 4); eight full chunks
-SHAPES = [(1, 1, 1), (40, 20, 2), (777, 64, 2), (130, 97, 1), (333, 128, 2), (300, 129, 2), (640, 900, 2), (257, 1024, 1)]
+SHAPES = ROW.SHAPES
 # more row tiles than compute units: workgroups straddle heads (bf16 only)
-BIG = (40000, 200, 2)
-DROP_SHAPES = [(130, 97, 1), (300, 300, 2), (640, 900, 2)]
-P_DROP, SEED, OFFSET = 0.1, 987654321, 5
-
-
-def _ops():
-    from snuffy_amd import ops
-    return ops
+BIG = ROW.BIG
+DROP_SHAPES = ROW.DROP_SHAPES
+SEED, OFFSET = DROP_SEED, DROP_OFFSET
 
 
 def _lse(q, v, kp, h):
     """The forward's lse: the dk = 256 forward takes bf16 Q and V only, and those are the values the backward's MFMAs see either way."""
     qb, vb = _qv(q, v, "bf16")
-    return _ops().sparse_attn_fwd_mfma_dk256(qb, vb, kp.to(DEV), h, need_lse=True)[2]
+    return getattr(_ops(), ROW.single)(qb, vb, kp.to(DEV), h, need_lse=True)[2]
 
 
 _CASES = {}
@@ -84,8 +78,8 @@ def test_dropout_forward(n, k, h):
     d = h * DK
     qd_, vd_ = _qv(q, v, "bf16")
     kd = kp.to(DEV)
-    o, attn, lse = ops.sparse_attn_fwd_mfma_dk256(qd_, vd_, kd, h, need_attn=True, need_lse=True, dropout=(P_DROP, SEED, OFFSET))
-    o0, attn0, lse0 = ops.sparse_attn_fwd_mfma_dk256(qd_, vd_, kd, h, need_attn=True, need_lse=True)
+    o, attn, lse = getattr(ops, ROW.single)(qd_, vd_, kd, h, need_attn=True, need_lse=True, dropout=(P_DROP, SEED, OFFSET))
+    o0, attn0, lse0 = getattr(ops, ROW.single)(qd_, vd_, kd, h, need_attn=True, need_lse=True)
     assert torch.equal(lse, lse0)
     assert torch.equal(attn.cpu(), attn0.cpu() * mask)
     qh, kh, vh = (bf16r(t).double().view(-1, h, DK).transpose(0, 1) for t in (q, kp, v))
@@ -94,15 +88,15 @@ def test_dropout_forward(n, k, h):
     err_o = rel_err(o.cpu(), o_r)
     print("dk256 dropout forward %s: O %.3e" % ((n, k, h), err_o))
     assert err_o < 3e-3
-    o1, a1, l1 = ops.sparse_attn_fwd_mfma_dk256(qd_, vd_, kd, h, need_attn=False, need_lse=True, dropout=(P_DROP, SEED, OFFSET))
+    o1, a1, l1 = getattr(ops, ROW.single)(qd_, vd_, kd, h, need_attn=False, need_lse=True, dropout=(P_DROP, SEED, OFFSET))
     assert a1 is None and torch.equal(o1, o) and torch.equal(l1, lse)
-    o2, attn2, lse2 = ops.sparse_attn_fwd_mfma_dk256(qd_, vd_, kd, h, need_attn=True, need_lse=True, dropout=(0.0, SEED, OFFSET))
+    o2, attn2, lse2 = getattr(ops, ROW.single)(qd_, vd_, kd, h, need_attn=True, need_lse=True, dropout=(0.0, SEED, OFFSET))
     assert torch.equal(o2, o0) and torch.equal(attn2, attn0) and torch.equal(lse2, lse0)
     # dropout without lse or attn is refused, as at the family's entry; so is p outside [0, 1)
     with pytest.raises(Exception, match="dropout needs the lse"):
-        ops.sparse_attn_fwd_mfma_dk256(qd_, vd_, kd, h, dropout=(P_DROP, SEED, OFFSET))
+        getattr(ops, ROW.single)(qd_, vd_, kd, h, dropout=(P_DROP, SEED, OFFSET))
     with pytest.raises(Exception, match="outside"):
-        ops.sparse_attn_fwd_mfma_dk256(qd_, vd_, kd, h, need_lse=True, dropout=(1.0, SEED, OFFSET))
+        getattr(ops, ROW.single)(qd_, vd_, kd, h, need_lse=True, dropout=(1.0, SEED, OFFSET))
 
 
 @pytest.mark.parametrize("n,k,h", DROP_SHAPES)
@@ -131,7 +125,7 @@ def test_backward(n, k, h, dt, drop):
     the fp32 ones rounded once; with f32 operands every dS column is written and |sum_j dS| <= 2^-7 sum_j |P_j dP_j| * scale (derived
     there).  Before DK = 256 was built the chunked entry raises "unsupported shape"."""
     ops = _ops()
-    assert ops.mfma_attn_dk256_train_supported(k, n, 2 * h * DK)
+    assert getattr(ops, ROW.supported)(k, n, 2 * h * DK)
     q, kp, v, dout, mask, (rq, rk, rv, pdp), (eq, ek, ev) = _case(n, k, h, drop)
     d = h * DK
     mask_d = None if mask is None else mask.to(DEV)
@@ -234,9 +228,9 @@ def test_chain_at_dk256_matches_the_restated_layer(sites, monkeypatch):
     """One training step through EncoderLayer0Bf16Fn (asserted by the spy inside _parity) on the D = 512 / h = 2 / Lambda = 900 layer at
     N = 3000 against the plain-torch restatement, with the bounds and the widening rule of tests/test_gpu_encoder_dropout_bf16.py."""
     from snuffy_amd import autograd as SA
-    n, d, h, lam = 3000, 512, 2, 900
+    n, d, h, lam = 3000, ROW.D, ROW.H, ROW.LAM
     assert d // h == DK
-    monkeypatch.setattr(SA, "FUSED_BF16_DK256", True)
+    monkeypatch.setattr(SA, ROW.train_switch, True)
     _parity(monkeypatch, n, d, h, lam, sites=sites)
 
 
@@ -245,13 +239,13 @@ def test_stepper_step_takes_the_chain_at_dk256_and_the_switch_takes_it_out(monke
     chain runs, off it does not; either way the loss is finite and the state_dict keeps its keys and shapes."""
     from snuffy_amd import autograd as SA
     from snuffy_amd.train import BagParallelStepper
-    n, d, h, lam = 3000, 512, 2, 900
+    n, d, h, lam = 3000, ROW.D, ROW.H, ROW.LAM
     sd = _perturbed_state_dict(n, d, h, lam)
     calls = []
     real_apply = SA.EncoderLayer0Bf16Fn.apply
     monkeypatch.setattr(SA.EncoderLayer0Bf16Fn, "apply", lambda *a: (calls.append(1), real_apply(*a))[1])
     for on in (True, False):
-        monkeypatch.setattr(SA, "FUSED_BF16_DK256", on)
+        monkeypatch.setattr(SA, ROW.train_switch, on)
         net = build_amd_milnet(d, h, "relu", lam, 0.5, 1, enc_drop=0.1)
         net.load_state_dict(sd, strict=True)
         net = net.to(DEV)

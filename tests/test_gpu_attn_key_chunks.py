@@ -6,76 +6,10 @@ import math
 import pytest
 import torch
 
-from tests.helpers import rel_err
-from tests.test_gpu_encoder_dropout import _perturbed_state_dict
-from tests.test_gpu_encoder_dropout_bf16 import _parity, _run
+from tests.helpers import BF, DEV, _c_backward, _ops, _parity, _perturbed_state_dict, _qv, _ref, _run, bf16r, rel_err
+from tests.helpers import grad_close as _close
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-BF = torch.bfloat16
-
-
-def _ops():
-    from snuffy_amd import ops
-    return ops
-
-
-def bf16r(t):
-    return t.to(BF).float()
-
-
-def _qv(q, v, dt):
-    """Row-strided halves of one [n, 2 d] buffer, as the model passes them."""
-    d = q.shape[1]
-    qv = torch.cat([q, v], dim=1).to(DEV).to(torch.float32 if dt == "f32" else BF)
-    return qv[:, :d], qv[:, d:]
-
-
-def _c_backward(entry, q, v, kp, dout, lse, h, mask=None, drop=(0.0, 0, 0)):
-    """The C entry point itself (fp32 dq / dv; dS in the operands' class, as ops.sparse_attn_bwd_mfma asks for it) -> (dq, dv, ds)."""
-    ops = _ops()
-    lib = ops._ffi.load()
-    n, d = q.shape
-    k, dk = kp.shape[0], d // h
-    bf = q.dtype == BF
-    dq = torch.empty(n, d, dtype=torch.float32, device=DEV)
-    dv = torch.empty(n, d, dtype=torch.float32, device=DEV)
-    ds = torch.full((h, n, k), float("nan"), dtype=BF if bf else torch.float32, device=DEV)
-    head = (ops._p(q), q.stride(0), ops._p(v), v.stride(0), ops.DT_BF16 if bf else ops.DT_F32, ops._p(kp), ops._p(dout), ops._p(lse),
-            ops._p(mask), float(drop[0]), int(drop[1]), int(drop[2]), n, k, h, dk, 1.0 / math.sqrt(dk), ops._p(dq), ops._p(dv), d,
-            ops.DT_F32, ops._p(ds), ops.DT_BF16 if bf else ops.DT_F32)
-    if entry == "chunked":
-        wsb = lib.snf_sparse_attn_bwd_mfma_chunked_workspace_bytes(n, k, h, dk, ops.DT_F32)
-        ws = ops._ws(wsb, DEV)
-        ops.check(lib.snf_sparse_attn_bwd_mfma_chunked(*head, ops._p(ws), wsb, ops._stream()), "snf_sparse_attn_bwd_mfma_chunked")
-    else:
-        ops.check(lib.snf_sparse_attn_bwd_mfma_ex(*head, ops._stream()), "snf_sparse_attn_bwd_mfma_ex")
-    return dq, dv, ds
-
-
-def _ref(q, kp, v, dout, h, mask):
-    """fp64 autograd of O = (softmax(Q Kp^T / sqrt(dk)) o M)^T V -> (dq, dkp, dv, sum_j |P_j dP_j| per head and row)."""
-    n, d = q.shape
-    k, dk = kp.shape[0], d // h
-    qd, kd, vd = (t.double().requires_grad_(True) for t in (q, kp, v))
-    qh, kh, vh = (t.view(-1, h, dk).transpose(0, 1) for t in (qd, kd, vd))
-    p = torch.softmax(qh @ kh.transpose(1, 2) / dk ** 0.5, dim=-1)
-    pr = p * mask.double() if mask is not None else p
-    (pr.transpose(1, 2) @ vh).transpose(0, 1).reshape(k, d).backward(dout.double())
-    with torch.no_grad():
-        dp = vh @ dout.double().view(k, h, dk).transpose(0, 1).transpose(1, 2)
-        if mask is not None:
-            dp = dp * mask.double()
-        pdp = (p * dp).abs().sum(-1)
-    return qd.grad, kd.grad, vd.grad, pdp
-
-
-def _close(got, want, tol, name):
-    """The rule of test_sparse_attn_bwd_mfma: relative to the gradient's own scale."""
-    scale_ = max(float(want.abs().max()), 1e-3)
-    err = float((got.cpu().double() - want).abs().max())
-    print("    %-4s max err %.3e (%.3e of its scale), rel_err %.3e, tol %.1e" % (name, err, err / scale_, rel_err(got.cpu(), want), tol))
-    assert err < tol * 4 * scale_ or rel_err(got.cpu(), want) < tol, name
 
 
 # a last chunk of few keys, exactly full chunks, the README's 500 and 900 keys, K % 4 != 0 (scalar dS stores, fp32 dS)

@@ -6,17 +6,10 @@ import math
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-from tests.helpers import build_amd_milnet
+from tests.helpers import DEV, _ops, _perturbed_state_dict, _restated_layer, build_amd_milnet
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def _ops():
-    from snuffy_amd import ops
-    return ops
 
 
 def _operands(m, n, k, seed):
@@ -101,65 +94,6 @@ def test_mask_statistics():
     assert abs(agree - 0.82) <= 5 * math.sqrt(0.82 * 0.18 / cnt), agree
     assert torch.equal(a, ops.dropout_mask(1, 4096, 3072, 0.1, 99, 1000, DEV))
     assert set(torch.unique(a).tolist()) == {0.0, float(np.float32(1.0 / (1.0 - np.float64(np.float32(0.1)))))}
-
-
-def _perturbed_state_dict(n, d, h, lam):
-    torch.manual_seed(n)
-    ref = build_amd_milnet(d, h, "relu", lam, 0.0, 1)
-    with torch.no_grad():
-        for m in ref.modules():
-            if isinstance(m, torch.nn.LayerNorm):
-                m.weight.add_(0.3 * torch.randn(d))
-                m.bias.add_(0.2 * torch.randn(d))
-            if isinstance(m, torch.nn.Linear) and m.bias is not None:
-                m.bias.add_(0.1 * torch.randn_like(m.bias))
-    return ref.state_dict()
-
-
-def _restated_layer(states, arithmetic):
-    """EncoderLayer.forward (snuffy.py:126-157) in plain torch under autograd, every dropout as a multiplication by the mask tensor of its
-    Philox state.  arithmetic: "library" = fp32 library GEMMs, "x3" = the bag-sized projections through autograd._linear (split-bf16 x 3
-    where functional.FP32_GEMM == "x3"), "fp64" = the whole layer in double."""
-    from snuffy_amd import autograd as SA
-    from snuffy_amd.functional import Parts
-    ops = _ops()
-
-    def fn(x2, sel, layer, need_attn, precision):
-        mha, ff = layer.self_attn, layer.feed_forward
-        n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
-        lq, lk, lv, lo = mha.linears
-        n, d = x2.shape
-        h, k = mha.h, sel.numel()
-        dk = d // h
-        dt = torch.float64 if arithmetic == "fp64" else torch.float32
-        c = lambda t: t.to(dt)
-
-        def big(x, lin):
-            if arithmetic == "x3":
-                return SA._linear(x, lin)
-            return F.linear(x, c(lin.weight), c(lin.bias))
-
-        def mask(site, rows, cols, heads=1):
-            st = states[site]
-            assert st is not None and st[0] > 0, site
-            return c(ops.dropout_mask(heads, rows, cols, st[0], st[1], st[2], x2.device))
-
-        x = c(x2)
-        xs = x.index_select(0, sel)
-        xn = F.layer_norm(x, (d,), c(n0.weight), c(n0.bias), n0.eps)
-        q, v = big(xn, lq), big(xn, lv)
-        kp = F.linear(xs, c(lk.weight), c(lk.bias))
-        s = torch.einsum("nhd,khd->hnk", q.view(n, h, dk), kp.view(k, h, dk)) / math.sqrt(dk)
-        p = torch.softmax(s, dim=-1) * mask("attn", n, k, h)                              # snuffy.py:166-167
-        o = torch.einsum("hnk,nhd->khd", p, v.view(n, h, dk)).reshape(k, d)
-        delta = F.linear(o, c(lo.weight), c(lo.bias)) * mask("A", k, d)[0]                # snuffy.py:108
-        y = x.index_copy(0, sel, xs + delta)
-        yn = F.layer_norm(y, (d,), c(n1.weight), c(n1.bias), n1.eps)
-        hid = torch.relu(big(yn, ff.w_1)) * mask("H", n, ff.w_1.weight.shape[0])[0]       # snuffy.py:225
-        f = big(hid, ff.w_2) * mask("Z", n, d)[0]                                         # snuffy.py:110
-        return Parts((y + f).float()), None
-
-    return fn
 
 
 @pytest.mark.parametrize("n,d,h,lam", [(16384, 768, 6, 200), (16391, 768, 6, 200)])

@@ -7,18 +7,10 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import build_amd_milnet
-from tests.test_gpu_encoder_dropout import _perturbed_state_dict, _restated_layer
+from tests.helpers import BF, DEV, _ops, _parity, _perturbed_state_dict, _run
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-BF = torch.bfloat16
 STATE = (0.1, 2 ** 63 + 12345, 2 ** 61 + 77)
-
-
-def _ops():
-    from snuffy_amd import ops
-    return ops
 
 
 def _mask(m, c, state=STATE):
@@ -145,88 +137,6 @@ def test_colsum_fused_with_dropout(n, d):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5. - 7. chain parity
-def _run(monkeypatch, sd, x, d, h, lam, precision, enc_drop=0.1, layer_fn=None, gemm=None, sites=None):
-    from snuffy_amd import autograd as SA
-    from snuffy_amd import functional as SF
-    with monkeypatch.context() as mp:
-        if gemm is not None:
-            mp.setattr(SF, "FP32_GEMM", gemm)
-        if layer_fn is not None:
-            mp.setattr(SA, "encoder_layer_train", layer_fn)
-        net = build_amd_milnet(d, h, "relu", lam, 0.0, 1, enc_drop=enc_drop)
-        net.load_state_dict(sd, strict=True)
-        net = net.to(DEV).configure(precision=precision, return_attention=False)
-        net.train(True)
-        layer = net.b_classifier.encoder.layers[0]
-        if sites is not None:
-            layer.sublayer[0].dropout.p, layer.feed_forward.dropout.p, layer.sublayer[1].dropout.p = sites
-        torch.manual_seed(11)
-        np.random.seed(5)
-        ins, logits, _ = net(x)
-        (logits.sum() * 3 + ins.max()).backward()
-        return net, {k: p.grad.float().clone() for k, p in net.named_parameters()}, logits.detach().clone()
-
-
-def _under_autocast(fn):
-    def wrapped(*args):
-        with torch.autocast("cuda", torch.bfloat16):
-            return fn(*args)
-    return wrapped
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-12))
-
-
-def _parity(monkeypatch, n, d, h, lam, sites=None):
-    """The fused bf16 chain against _restated_layer(states, "library") in fp32 (a) and under bf16 autocast (b); bounds of
-    test_fused_bf16_layer0_training_matches_generic_and_fp32: logits 2e-2 max(1, |ref|max), gradients 0.08 against (b), 0.1 against (a).
-    The distance between (a) and (b) involves no code under test: where it alone exceeds a bound for a key, that key's bound is 1.5 x
-    that distance (printed as WIDENED; profiles/encoder_dropout_bf16_train.txt lists them)."""
-    from snuffy_amd import autograd as SA
-    sd = _perturbed_state_dict(n, d, h, lam)
-    x = torch.randn(1, n, d, device=DEV)
-    calls = []
-    real_apply = SA.EncoderLayer0Bf16Fn.apply
-    monkeypatch.setattr(SA.EncoderLayer0Bf16Fn, "apply", lambda *a: (calls.append(1), real_apply(*a))[1])
-    enc = 0.1 if sites is None else 0.0
-    net, g_fused, out_fused = _run(monkeypatch, sd, x, d, h, lam, "bf16", enc, sites=sites)
-    assert calls, "the fused bf16 chain declined a layer with encoder dropout"
-    states = dict(net.b_classifier.encoder.layers[0].last_dropout_states)
-    want_p = dict(zip(("A", "H", "Z"), sites if sites is not None else (0.1, 0.1, 0.1)))
-    assert states["attn"] is not None and states["attn"][0] == 0.1
-    for s, p in want_p.items():
-        assert (states[s] is None) if p == 0 else (states[s] is not None and states[s][0] == p), (s, states[s])
-    drawn = [states[s][2] for s in states if states[s] is not None]
-    assert len(set(drawn)) == len(drawn) == 1 + sum(p > 0 for p in want_p.values())       # one Philox offset per site
-    # a site that is off: the restatement multiplies by the mask of p = 1e-30, which keeps everything at scale 1.0f
-    restate = {s: (st if st is not None else (1e-30, 0, 0)) for s, st in states.items()}
-    for s, st in restate.items():
-        if states[s] is None:
-            assert bool((_ops().dropout_mask(1, 8, 8, *st, DEV) == 1).all())
-    del calls[:]
-    _, g_a, out_a = _run(monkeypatch, sd, x, d, h, lam, "fp32", enc, _restated_layer(restate, "library"), "library", sites)
-    _, g_b, out_b = _run(monkeypatch, sd, x, d, h, lam, "bf16", enc, _under_autocast(_restated_layer(restate, "library")), None, sites)
-    assert not calls                                                     # the comparators did not run the chain
-    tag = "bf16 encoder dropout parity n=%d d=%d sites=%s" % (n, d, sites)
-    for name, out_ref in (("a", out_a), ("b", out_b)):
-        err = (out_fused - out_ref).abs().max().item() / max(1.0, out_ref.abs().max().item())
-        print("%s: logits vs (%s) %.3e; (a) vs (b) %.3e" % (tag, name, err, (out_a - out_b).abs().max().item() / max(1.0, out_b.abs().max().item())))
-        assert err <= 2e-2, (name, err)
-    bad = []
-    for k in g_fused:
-        if k.endswith("self_attn.linears.1.bias"):
-            continue                               # mathematically zero gradient
-        d_ab = _rel(g_a[k], g_b[k])
-        r_a, r_b = _rel(g_fused[k], g_a[k]), _rel(g_fused[k], g_b[k])
-        bound_a = 0.1 if d_ab <= 0.1 else 1.5 * d_ab
-        bound_b = 0.08 if d_ab <= 0.08 else 1.5 * d_ab
-        print("    %-55s vs (a) %.3e  vs (b) %.3e  (a) vs (b) %.3e%s" % (k, r_a, r_b, d_ab, "  WIDENED" if d_ab > 0.08 else ""))
-        if not (r_a < bound_a and r_b < bound_b):
-            bad.append((k, r_a, bound_a, r_b, bound_b))
-    assert not bad, bad
-
-
 @pytest.mark.parametrize("n,d,h,lam", [(700, 256, 4, 50), (2048, 768, 6, 200), (2051, 768, 6, 200)])
 def test_fused_bf16_chain_with_encoder_dropout_matches_the_restated_layer(n, d, h, lam, monkeypatch):
     _parity(monkeypatch, n, d, h, lam)

@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import snuffy_oracle as orc
-from tests.helpers import golden_files, rel_err
+from tests.helpers import attn_ref, bf16r, golden_files, rel_err
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -277,11 +277,6 @@ def test_ln_mean_head(n, d, c):
 
 
 # ---------------------------------------------------------------- K7 sparse attention
-def attn_ref(q, kp, v, h):
-    o, p = orc.sparse_attention(q.double(), kp.double(), v.double(), h)
-    return o, p
-
-
 @pytest.mark.parametrize("n,k,h,dk", [(40, 40, 2, 83), (1000, 200, 6, 16), (3000, 900, 4, 24), (777, 64, 1, 128),
                                       (257, 5, 3, 7), (1, 1, 2, 32), (5000, 512, 6, 128), (17, 17, 2, 256),
                                       # the README recipes' head widths (h = 4) and the limits of the matrix-core forms
@@ -408,10 +403,6 @@ def test_exact_attention_lds_staged_kernels_are_the_direct_ones_bit_for_bit(n, k
         _ffi.load().snf_debug_exact_attn_mfma(1)
     for x, y in zip(res[1], res[2]):
         assert torch.equal(x, y)
-
-
-def bf16r(t):
-    return t.to(torch.bfloat16).float()
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])

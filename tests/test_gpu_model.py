@@ -7,21 +7,11 @@ import pytest
 import torch
 
 from oracle import snuffy_oracle as orc
-from tests.helpers import ReplayRNG, build_amd_milnet, forced_sel, golden_files, load_case, rel_err
+from tests.helpers import (TOL, ReplayRNG, build_amd_milnet, forced_sel, golden_files, load_case, rel_err, synth_state,
+                           tol_for)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-# north-star tolerances: fp32 1e-3, bf16 1e-2 (attention / logits)
-TOL = {"fp32": 1e-3, "bf16": 1e-2}
-
-
-# The gates are FLAT (north_star gives no depth allowance).  precision="bf16" holds 1e-2 for one encoder layer -- the benchmark model;
-# stacks of more than one layer run the fp32-class kernels whatever the setting (snuffy.RuntimeConfig.compute): the reference's
-# depth-5 fixture f1_n150_d5 measured |dA| = 0.10 through five literal bf16 layers, 1.5e-4 fp32-class.
-def tol_for(precision, depth, fixture=None, what="logits"):
-    return TOL[precision]
-
 
 def _record_error(fixture, precision, err_logits, err_a):
     """Measured errors per fixture -> gpurun_out/measured_f1.json (scratch; summarised in DESIGN.md)."""
@@ -93,19 +83,6 @@ def test_f1_selection_bit_exact_at_bclassifier_boundary(path):
         else:
             assert rnd is None
     np.testing.assert_allclose(logits.cpu().numpy(), z["logits"], rtol=0, atol=3e-5)
-
-
-def synth_state(D, h, depth, seed=0):
-    """train.py defaults: xavier_normal weights, zero biases (train.py:68-72, utils.py:69-75)."""
-    torch.manual_seed(seed)
-    net = build_amd_milnet(D, h, "relu", 200, 0.0, depth)
-    for _, p in net.named_parameters():
-        if p.dim() > 1:
-            torch.nn.init.xavier_normal_(p)
-    for m in net.modules():
-        if isinstance(m, torch.nn.Linear):
-            torch.nn.init.zeros_(m.bias)
-    return net
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])

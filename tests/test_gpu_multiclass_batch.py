@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import snuffy_oracle as orc
-from tests.test_gpu_model import tol_for          # the project's flat gates: fp32 1e-3, bf16 1e-2
+from tests.helpers import tol_for                 # the project's flat gates: fp32 1e-3, bf16 1e-2
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"

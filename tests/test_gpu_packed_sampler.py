@@ -7,11 +7,12 @@ import torch
 
 from oracle import philox_ref
 from oracle import snuffy_oracle as orc
+from tests.attn_widths import OFFSET, SEED, _bags, _loop, _offset, _place_sampler
+from tests.attn_widths import outputs_close as _close
 from tests.helpers import build_amd_milnet
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-SEED, OFFSET = 1234567, 99
 KERNEL_SIZES = [1, 23, 24, 25, 63, 64, 65, 1023, 1025, 4097, 8192, 8193, 16385, 32769, 65536]
 
 
@@ -75,40 +76,6 @@ def _net(d, h, lam, r, depth, precision, seed=0, return_attention=True):
                 torch.nn.init.xavier_uniform_(p)
     net.configure(precision=precision, return_attention=return_attention, sampler="device")
     return net
-
-
-def _bags(sizes, d, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    return [torch.randn(1, n, d, generator=g).to(DEV) for n in sizes]
-
-
-def _place_sampler(net, offset):
-    from snuffy_amd import ops
-    net.b_classifier.cfg._device_sampler = ops.DeviceSampler(torch.device(DEV, torch.cuda.current_device()), SEED, offset)
-    return net.b_classifier.cfg._device_sampler
-
-
-def _offset(net):
-    return int(net.b_classifier.cfg._device_sampler.state[1].item())
-
-
-def _loop(net, bags):
-    out, sels = [], []
-    for x in bags:
-        out.append(net(x))
-        sels.append([tuple(None if t is None else t.clone() for t in l.last_selection) for l in net.b_classifier.encoder.layers])
-    return out, sels
-
-
-def _close(ref, got, precision):
-    tol = 2e-5 if precision == "fp32" else 2e-2
-    (c0, y0, a0), (c1, y1, a1) = ref, got
-    assert c1.shape == c0.shape and y1.shape == y0.shape and a1.shape == a0.shape
-    assert torch.equal(c0, c1)
-    err_y, err_a = (y0 - y1).abs().max().item(), (a0 - a1).abs().max().item()
-    print("logit err %.3e (|y| %.3e)  A err %.3e" % (err_y, y0.abs().max().item(), err_a))
-    assert err_y <= tol * max(1.0, y0.abs().max().item())
-    assert err_a <= tol
 
 
 @pytest.fixture(autouse=True)

@@ -7,17 +7,13 @@ import pytest
 import torch
 
 from oracle import snuffy_oracle as orc
+from tests.attn_widths import _bags, _packed
 from tests.helpers import build_amd_milnet
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 SIZES = [300, 1000, 129, 5000, 2048, 777]
-
-
-def _packed(sizes):
-    from snuffy_amd import ops
-    return ops.PackedBags(sizes, DEV)
 
 
 def test_topk_segmented_matches_per_bag_selection():
@@ -154,11 +150,6 @@ def _net(d, h, lam, r, depth, precision, seed=0):
                 torch.nn.init.xavier_uniform_(p)
     net.configure(precision=precision, return_attention=True)
     return net
-
-
-def _bags(sizes, d, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    return [torch.randn(1, n, d, generator=g).to(DEV) for n in sizes]
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])

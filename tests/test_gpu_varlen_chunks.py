@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import snuffy_oracle as orc
+from tests.attn_widths import _bags, _fp64_reference, _packed, _sizes
 from tests.helpers import build_amd_milnet
 
 pytestmark = pytest.mark.gpu
@@ -21,34 +22,9 @@ SHAPES = [(768, 6, 225),                          # smallest chunked case: chunk
           (512, 4, 900)]                          # 5 chunks
 
 
-def _packed(sizes):
-    from snuffy_amd import ops
-    return ops.PackedBags(sizes, DEV)
-
-
-def _sizes(k):
-    return [k if n is None else n for n in LENGTHS if n is None or n >= k]
-
-
-_REF64 = {}
-
-
-def _fp64_reference(tag, q, v, kp, h):
-    """softmax(Q Kp^T / sqrt(dk))^T V of one bag in fp64, computed once per (family, shape)."""
-    if tag not in _REF64:
-        n, d = q.shape
-        k, dk = kp.shape[0], d // h
-        qd = q.double().view(n, h, dk).transpose(0, 1)
-        vd = v.double().view(n, h, dk).transpose(0, 1)
-        kd = kp.double().view(k, h, dk).transpose(0, 1)
-        p = torch.softmax(qd @ kd.transpose(1, 2) / dk ** 0.5, dim=-1)
-        _REF64[tag] = (p.transpose(1, 2) @ vd).transpose(0, 1).reshape(k, d)
-    return _REF64[tag]
-
-
 def _check_family(fam, d, h, k, need_attn):
     from snuffy_amd import ops
-    sizes = _sizes(k)
+    sizes = _sizes(k, LENGTHS)
     pk = _packed(sizes)
     g = torch.Generator().manual_seed(1 if fam == "bf16" else 2)
     qv = torch.randn(pk.total, 2 * d, generator=g).to(DEV)
@@ -115,11 +91,6 @@ def _net(d, h, lam, r, depth, precision, seed=0):
                 torch.nn.init.xavier_uniform_(p)
     net.configure(precision=precision, return_attention=True)
     return net
-
-
-def _bags(sizes, d, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    return [torch.randn(1, n, d, generator=g).to(DEV) for n in sizes]
 
 
 @pytest.fixture

@@ -9,45 +9,15 @@ import pytest
 import torch
 
 from oracle import snuffy_oracle as orc
+from tests.attn_widths import (OFFSET, VARLEN_192 as ROW, _bags, _close, _fp64_reference, _loop, _offset, _packed, _place_sampler,
+                               _sizes, device_sampler_on, op, single_bag, y_bound)  # noqa: F401  (fixtures)
 from tests.helpers import build_amd_milnet
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
-D_K, H_K = 384, 2                                 # kernel level: the smallest model width with dk = 192
-LENGTHS = [None, 777, 1024, 1025, 4100]           # None: exactly k rows; a row-tile tail, the last directly stored length; reduced bags
-KEYS = [20,                                       # 1 key block
-        64,                                       # 2 key blocks
-        100,                                      # 4 key blocks with a key tail
-        128,                                      # a full launch
-        129,                                      # two chunks whose key-block counts differ (65: 4, 64: 2)
-        500,                                      # the recipe: 4 x 125
-        1024]                                     # 8 full chunks
-
-
-def _packed(sizes):
-    from snuffy_amd import ops
-    return ops.PackedBags(sizes, DEV)
-
-
-def _sizes(k):
-    return [k if n is None else n for n in LENGTHS if n is None or n >= k]
-
-
-_REF64 = {}
-
-
-def _fp64_reference(tag, q, v, kp, h):
-    """softmax(Q Kp^T / sqrt(dk))^T V of one bag in fp64, computed once per key count."""
-    if tag not in _REF64:
-        n, d = q.shape
-        k, dk = kp.shape[0], d // h
-        qd = q.double().view(n, h, dk).transpose(0, 1)
-        vd = v.double().view(n, h, dk).transpose(0, 1)
-        kd = kp.double().view(k, h, dk).transpose(0, 1)
-        p = torch.softmax(qd @ kd.transpose(1, 2) / dk ** 0.5, dim=-1)
-        _REF64[tag] = (p.transpose(1, 2) @ vd).transpose(0, 1).reshape(k, d)
-    return _REF64[tag]
+D_K, H_K = ROW.D_K, ROW.H_K                       # kernel level: the smallest model width with dk = 192
+KEYS = ROW.KEYS
 
 
 @pytest.mark.parametrize("k", KEYS)
@@ -60,15 +30,15 @@ def test_attention_varlen_dk192_vs_per_bag_and_composition_independent(k, need_a
     g = torch.Generator().manual_seed(1)
     qv = torch.randn(pk.total, 2 * d, generator=g).to(DEV).to(torch.bfloat16)
     kp = (torch.randn(pk.bags * k, d, generator=g) * 0.5).to(DEV).to(torch.bfloat16)
-    assert ops.varlen_attn_dk192_supported(k) and not ops.varlen_attn_chunks_supported("bf16", k, d // h)
-    varlen = ops.sparse_attn_fwd_mfma_varlen
+    assert op(ROW, "varlen_supported")(k) and not ops.varlen_attn_chunks_supported(ROW.kind, k, d // h)
+    varlen = op(ROW, "varlen")
     q, v = qv[:, :d], qv[:, d:]
     out, attn, lse = varlen(q, v, kp, pk, k, h, need_attn=need_attn, need_lse=need_attn)
     assert out.shape == (pk.bags * k, d)
     for b, n in enumerate(sizes):
         lo = int(pk.host[b])
         qb, kb = qv[lo:lo + n], kp[b * k:(b + 1) * k]
-        o1, a1, l1 = ops.sparse_attn_fwd_mfma(qb[:, :d], qb[:, d:], kb, n, h, need_attn=need_attn, need_lse=need_attn)
+        o1, a1, l1 = single_bag(ROW, qb[:, :d], qb[:, d:], kb, h, need_attn=need_attn, need_lse=need_attn)
         err, ref = (out[b * k:(b + 1) * k] - o1).abs().max().item(), o1.abs().max().item()
         print("dk=192 k=%d bag %d n=%d: |out - single| / max|out| = %.3g" % (k, b, n, err / ref))
         # the single-bag entry point spreads a small bag over more workgroups: same P, O up to the fp32 order of the partial sums
@@ -84,10 +54,10 @@ def test_attention_varlen_dk192_vs_per_bag_and_composition_independent(k, need_a
     # against fp64 on one bag (the kernels agree with each other; this pins them to the definition)
     b = 1
     lo, n = int(pk.host[b]), sizes[b]
-    ref = _fp64_reference(k, qv[lo:lo + n, :d], qv[lo:lo + n, d:], kp[b * k:(b + 1) * k], h)
+    ref = _fp64_reference((ROW.id, k), qv[lo:lo + n, :d], qv[lo:lo + n, d:], kp[b * k:(b + 1) * k], h)
     err = (out[b * k:(b + 1) * k].double() - ref).abs().max().item() / ref.abs().max().item()
     print("dk=192 k=%d: relative error against fp64 %.3g" % (k, err))
-    assert err < 1e-2, err
+    assert err < ROW.O_FP64[k > 256], err
     # a repeat call is bit-identical
     out_r, attn_r, lse_r = varlen(q, v, kp, pk, k, h, need_attn=need_attn, need_lse=need_attn)
     assert torch.equal(out, out_r)
@@ -96,14 +66,13 @@ def test_attention_varlen_dk192_vs_per_bag_and_composition_independent(k, need_a
 
 
 # ---- model level ----------------------------------------------------------------------------------------------------------------------
-D, H, LAM, R = 768, 4, 500, 0.5
-SIZES = [500, 777, 1025, 2100, 3000]
-SEED, OFFSET = 1234567, 99
+D, H, LAM, R, ACT = ROW.D, ROW.H, ROW.LAM, ROW.R, ROW.ACT
+SIZES = ROW.SIZES
 
 
 def _net(precision="bf16", sampler=None, return_attention=True, seed=0):
     torch.manual_seed(seed)
-    net = build_amd_milnet(D, H, "relu", LAM, R, 1).to(DEV).eval()
+    net = build_amd_milnet(D, H, ACT, LAM, R, 1).to(DEV).eval()
     with torch.no_grad():
         for p in net.parameters():
             if p.dim() > 1:
@@ -115,47 +84,21 @@ def _net(precision="bf16", sampler=None, return_attention=True, seed=0):
     return net
 
 
-def _bags(sizes, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    return [torch.randn(1, n, D, generator=g).to(DEV) for n in sizes]
-
-
-def _loop(net, bags):
-    out, sels = [], []
-    for x in bags:
-        out.append(net(x))
-        sels.append([tuple(None if t is None else t.clone() for t in l.last_selection) for l in net.b_classifier.encoder.layers])
-    return out, sels
-
-
-def _close(ref, got, n):
-    """The bf16 figures of test_gpu_varlen_chunks.py: logits 2e-2 (relative above 1), A 2e-2, row sums of A 1e-3."""
-    (c0, y0, a0), (c1, y1, a1) = ref, got
-    assert c1.shape == c0.shape and y1.shape == y0.shape and a1.shape == a0.shape == (1, H, n, LAM)
-    assert torch.equal(c0, c1)                           # critic scores: same kernel, row-wise
-    dy, da = (y0 - y1).abs().max().item(), (a0 - a1).abs().max().item()
-    ds = (a1.sum(-1) - 1).abs().max().item()
-    print("n=%d: |dlogit| %.3g  |dA| %.3g  |rowsum - 1| %.3g" % (n, dy, da, ds))
-    assert dy <= 2e-2 * max(1.0, y0.abs().max().item()), (y0, y1)
-    assert da <= 2e-2
-    assert ds <= 1e-3                                    # only the row sum notices a chunk normalised by the wrong statistics
-
-
 @pytest.fixture
 def dk192_on(monkeypatch):
     from snuffy_amd import packed
-    monkeypatch.setattr(packed, "PACK_DK192", True)              # the switch under test, whatever its shipped default
+    monkeypatch.setattr(packed, ROW.pack_switch, True)              # the switch under test, whatever its shipped default
 
 
 def _count_varlen_calls(monkeypatch):
     from snuffy_amd import ops
-    calls, real = [], ops.sparse_attn_fwd_mfma_varlen
+    calls, real = [], getattr(ops, ROW.varlen)
 
     def spy(*a, **kw):
         calls.append(1)
         return real(*a, **kw)
 
-    monkeypatch.setattr(ops, "sparse_attn_fwd_mfma_varlen", spy)
+    monkeypatch.setattr(ops, ROW.varlen, spy)
     return calls
 
 
@@ -165,10 +108,10 @@ def test_forward_bags_of_the_mae_recipe_matches_per_bag_forwards(dk192_on, monke
     (off: the loop runs the exact kernel on bf16-rounded Q | V) -- the bf16 class holds either way."""
     from snuffy_amd import functional as SF
     if single_bag_mfma:
-        monkeypatch.setattr(SF, "MFMA_ATTN_DK192", True)
+        monkeypatch.setattr(SF, ROW.single_switch, True)
     calls = _count_varlen_calls(monkeypatch)
     net = _net()
-    bags = _bags(SIZES)
+    bags = _bags(SIZES, D)
     with torch.no_grad():
         np.random.seed(11)
         ref, sel_ref = _loop(net, bags)
@@ -184,13 +127,13 @@ def test_forward_bags_of_the_mae_recipe_matches_per_bag_forwards(dk192_on, monke
     top, rnd = net.b_classifier.encoder.layers[0].last_selection_bags
     for b in range(len(bags)):                           # selections, random share included: bit-exact
         assert torch.equal(top[b], sel_ref[b][0][0]) and torch.equal(rnd[b], sel_ref[b][0][1])
-        _close(ref[b], got[b], SIZES[b])
+        _close(ROW, ref[b], got[b], SIZES[b])
 
 
 def test_forward_bags_of_the_mae_recipe_vs_oracle(dk192_on):
-    sizes = [600, 1100]
+    sizes = ROW.ORACLE_SIZES
     net = _net()
-    bags = _bags(sizes, seed=9)
+    bags = _bags(sizes, D, seed=9)
     sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
     with torch.no_grad():
         np.random.seed(3)
@@ -199,33 +142,18 @@ def test_forward_bags_of_the_mae_recipe_vs_oracle(dk192_on):
     top, rnd = net.b_classifier.encoder.layers[0].last_selection_bags
     for b, x in enumerate(bags):
         sel = torch.cat((top[b], rnd[b])).cpu()
-        classes, logits, attn, _ = orc.milnet_forward(x[0].cpu(), sd, H, "relu", LAM, R, 1, forced_sel=[sel])
+        classes, logits, attn, _ = orc.milnet_forward(x[0].cpu(), sd, H, ACT, LAM, R, 1, forced_sel=[sel])
         own_top, _ = orc.select_indices(classes[:, 0], LAM, R, np.random.RandomState(0))
         assert np.array_equal(own_top.numpy(), top[b].cpu().numpy())                   # bit-exact top indices per bag
         dy, da = (got[b][1][0].cpu() - logits).abs().max().item(), (got[b][2][0].cpu() - attn).abs().max().item()
         print("bag %d against the oracle: |dlogit| %.3g  |dA| %.3g" % (b, dy, da))
-        assert dy <= 2e-2 * max(1.0, logits.abs().max().item())
-        assert da <= 2e-2
-
-
-def _place_sampler(net, offset):
-    from snuffy_amd import ops
-    net.b_classifier.cfg._device_sampler = ops.DeviceSampler(torch.device(DEV, torch.cuda.current_device()), SEED, offset)
-
-
-def _offset(net):
-    return int(net.b_classifier.cfg._device_sampler.state[1].item())
-
-
-@pytest.fixture
-def device_sampler_on(monkeypatch):
-    from snuffy_amd import packed
-    monkeypatch.setattr(packed, "PACK_DEVICE_SAMPLER", True)
+        assert dy <= y_bound(ROW, logits)
+        assert da <= ROW.A_TOL
 
 
 def test_device_sampler_one_group_equals_the_loop(dk192_on, device_sampler_on):
     net = _net(sampler="device")
-    bags = _bags(SIZES)
+    bags = _bags(SIZES, D)
     with torch.no_grad():
         _place_sampler(net, OFFSET)
         ref, sel_ref = _loop(net, bags)
@@ -236,15 +164,15 @@ def test_device_sampler_one_group_equals_the_loop(dk192_on, device_sampler_on):
     top, rnd = net.b_classifier.encoder.layers[0].last_selection_bags
     for b in range(len(bags)):
         assert torch.equal(top[b], sel_ref[b][0][0]) and torch.equal(rnd[b], sel_ref[b][0][1]), b
-        _close(ref[b], got[b], SIZES[b])
+        _close(ROW, ref[b], got[b], SIZES[b])
 
 
 def test_device_sampler_mix_with_a_short_bag(dk192_on, device_sampler_on):
     """A 150-row bag (shorter than Lambda: it selects all of its rows, 150 keys) next to the uniform group: pack_groups leaves it to the
     per-bag loop (a ragged group needs two bags), which runs after the group and draws from the next offset."""
-    sizes = [777, 150, 1025, 500]
+    sizes = ROW.MIX_SIZES
     net = _net(sampler="device")
-    bags = _bags(sizes, seed=17)
+    bags = _bags(sizes, D, seed=17)
     with torch.no_grad():
         groups = net._pack_groups(bags)
         assert groups == [([0, 2, 3], False)]
@@ -258,19 +186,19 @@ def test_device_sampler_mix_with_a_short_bag(dk192_on, device_sampler_on):
             c1, y1, a1 = got[i]
             assert a1.shape == a0.shape == (1, H, sizes[i], min(LAM, sizes[i]))
             assert torch.equal(c0, c1)
-            assert (y0 - y1).abs().max().item() <= 2e-2 * max(1.0, y0.abs().max().item()), i
-            assert (a0 - a1).abs().max().item() <= 2e-2, i
+            assert (y0 - y1).abs().max().item() <= y_bound(ROW, y0), i
+            assert (a0 - a1).abs().max().item() <= ROW.A_TOL, i
         # two short bags form a ragged group behind the uniform one (150 keys: inside the ragged kernel at this width)
-        bags2 = bags + _bags([160], seed=19)
+        bags2 = bags + _bags([160], D, seed=19)
         assert net._pack_groups(bags2) == [([0, 2, 3], False), ([1, 4], True)]
 
 
 def test_device_sampler_graph_replay_draws_fresh_rows(dk192_on, device_sampler_on):
-    sizes = [600, 1500, 900]
+    sizes = ROW.GRAPH_SIZES
     B = len(sizes)
     net = _net(sampler="device", return_attention=False)
     net.configure(sampler="device", graph_max_patches=1 << 20, return_attention=False)
-    bags = _bags(sizes, seed=21)
+    bags = _bags(sizes, D, seed=21)
     _place_sampler(net, OFFSET)
     # call 1 is eager (the composition is remembered), call 2 warms up twice, captures and replays, call 3 replays only
     starts = [OFFSET, OFFSET + 3 * B, OFFSET + 4 * B]
@@ -295,10 +223,10 @@ def test_device_sampler_graph_replay_draws_fresh_rows(dk192_on, device_sampler_o
 
 def test_switch_off_keeps_the_per_bag_loop(monkeypatch):
     from snuffy_amd import packed
-    monkeypatch.setattr(packed, "PACK_DK192", False)
+    monkeypatch.setattr(packed, ROW.pack_switch, False)
     calls = _count_varlen_calls(monkeypatch)
     net = _net()
-    bags = _bags([600, 1100, 2048], seed=13)
+    bags = _bags(ROW.OFF_SIZES, D, seed=13)
     with torch.no_grad():
         assert not net._packable(bags) and net._pack_groups(bags) is None
         np.random.seed(11)
@@ -313,10 +241,10 @@ def test_switch_off_keeps_the_per_bag_loop(monkeypatch):
 @pytest.mark.parametrize("on", [True, False])
 def test_fp32_stays_per_bag_whatever_the_switch(monkeypatch, on):
     from snuffy_amd import packed
-    monkeypatch.setattr(packed, "PACK_DK192", on)
+    monkeypatch.setattr(packed, ROW.pack_switch, on)
     calls = _count_varlen_calls(monkeypatch)
     net = _net(precision="fp32")
-    bags = _bags([600, 1100], seed=13)
+    bags = _bags([600, 1100], D, seed=13)
     with torch.no_grad():
         assert net._pack_groups(bags) is None
         np.random.seed(11)

@@ -7,50 +7,41 @@ repeat.
 Model level: the single-bag forward behind functional.X3_ATTN_DK256 at depth 1 and on a depth-2 stack, MILNet.forward_bags behind
 packed.PACK_X3_DK256 against the per-bag forwards and the CPU oracle, with the device sampler (one group, a mix with a short bag), and
 the routing that ships with both switches at their defaults."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import snuffy_oracle as orc
-from tests.helpers import ReplayRNG, build_amd_milnet, rel_err
+from tests.attn_widths import (OFFSET, X3_256 as ROW, _bags, _close, _fp64_reference, _loop, _offset, _packed, _place_sampler, _sizes,
+                               _spy, device_sampler_on, op, pack_on)  # noqa: F401  (fixtures)
+from tests.helpers import ReplayRNG, _ops, build_amd_milnet, rel_err
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture
+def row():
+    return ROW
 DEV = "cuda"
 
-D_K, H_K, DK = 512, 2, 256
-
-
-def _ops():
-    from snuffy_amd import ops
-    return ops
+D_K, H_K, DK = ROW.D_K, ROW.H_K, ROW.dk
 
 
 # ---- single bag -------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n,k,h", [(1, 1, 2),
-                                   (40, 20, 2),         # 1 key block, key tail
-                                   (777, 64, 2),        # 2 key blocks, row-tile tail (777 = 24 x 32 + 9)
-                                   (1000, 100, 2),      # 4 key blocks, key tail
-                                   (333, 128, 2),       # a full launch
-                                   (4100, 129, 2),      # two chunks (68: 4 blocks, 61: 2 blocks), several workgroups per head
-                                   (2000, 900, 2),      # the recipe: 7 chunks of 116 keys and one of 88
-                                   (333, 1024, 2),      # 8 full chunks
-                                   (500, 200, 1),       # the head loop: one head (D = 256) ...
-                                   (500, 200, 3)])      # ... and three (D = 768)
+@pytest.mark.parametrize("n,k,h", ROW.SHAPES)
 def test_sparse_attn_x3_dk256_fp32_class(n, k, h):
     """Bounds: those of test_sparse_attn_x3_fp32_class / test_sparse_attn_x3u_fp32_class, which the unfused pair holds at dk = 256
     (P 1e-5, O 2e-5 of its scale up to 256 keys and 4e-5 above, lse 3e-5, row sums 1e-5, all against fp64); against the unfused pair P
     within the sum of the two P bounds."""
     ops = _ops()
     dk = DK
-    g = torch.Generator().manual_seed(n * 3 + k + dk + h)
+    g = torch.Generator().manual_seed(ROW.seed(n, k, h))
     d = h * dk
     q, kp, v = torch.randn(n, d, generator=g), torch.randn(k, d, generator=g), torch.randn(n, d, generator=g)
     o_ref, p_ref = orc.sparse_attention(q.double(), kp.double(), v.double(), h)
-    assert ops.x3_attn_dk256_supported(k) and not ops.x3_attn_supported(k, dk)
+    assert op(ROW, "single_supported")(k) and not ops.x3_attn_supported(k, dk)
     qd, kd, vd = q.to(DEV), kp.to(DEV), v.to(DEV)
-    o, attn, lse = ops.sparse_attn_fwd_x3_dk256(qd, vd, kd, h, need_attn=True, need_lse=True)
+    o, attn, lse = op(ROW, "single")(qd, vd, kd, h, need_attn=True, need_lse=True)
     s_ref = (q.double().view(n, h, dk).transpose(0, 1) @ kp.double().view(k, h, dk).transpose(0, 1).transpose(1, 2)) / dk ** 0.5
     e_p = (attn.cpu().double() - p_ref).abs().max().item()
     e_o = rel_err(o.cpu(), o_ref)
@@ -58,22 +49,22 @@ def test_sparse_attn_x3_dk256_fp32_class(n, k, h):
     e_s = (attn.sum(-1) - 1).abs().max().item()
     print("x3 dk=256 n=%d k=%d h=%d: |dP| %.3g  O rel %.3g  |dlse| %.3g  |rowsum - 1| %.3g" % (n, k, h, e_p, e_o, e_l, e_s))
     assert e_p < 1e-5
-    assert e_o < (2e-5 if k <= 256 else 4e-5)
+    assert e_o < ROW.O_FP64[k > 256]
     assert e_l < 3e-5
     assert e_s < 1e-5
     # the unfused pair on the same operands
-    _, a_u, _ = ops.sparse_attn_fwd_x3u(qd, kd, vd, h, need_attn=True)
+    _, a_u, _ = op(ROW, "replaced")(qd, kd, vd, h, need_attn=True)
     e_u = (attn - a_u).abs().max().item()
     print("x3 dk=256 n=%d k=%d h=%d: |P - P(x3u)| %.3g" % (n, k, h, e_u))
     assert e_u < 2e-5
     # the same O without the A output; a repeat call is bit-identical
-    o2, a2, l2 = ops.sparse_attn_fwd_x3_dk256(qd, vd, kd, h)
+    o2, a2, l2 = op(ROW, "single")(qd, vd, kd, h)
     assert a2 is None and l2 is None and torch.equal(o2, o)
-    o3, a3, l3 = ops.sparse_attn_fwd_x3_dk256(qd, vd, kd, h, need_attn=True, need_lse=True)
+    o3, a3, l3 = op(ROW, "single")(qd, vd, kd, h, need_attn=True, need_lse=True)
     assert torch.equal(o3, o) and torch.equal(a3, attn) and torch.equal(l3, lse)
     # the halves of a fused [Q | V] projection output, used in place (row pitch 2 d)
     qv = torch.cat([q, v], dim=1).to(DEV)
-    o4, a4, _ = ops.sparse_attn_fwd_x3_dk256(qv[:, :d], qv[:, d:], kd, h, need_attn=True)
+    o4, a4, _ = op(ROW, "single")(qv[:, :d], qv[:, d:], kd, h, need_attn=True)
     assert torch.equal(o4, o) and torch.equal(a4, attn)
 
 
@@ -82,33 +73,13 @@ def test_sparse_attn_x3_dk256_refuses_other_shapes():
     ops = _ops()
     z = lambda *s: torch.zeros(*s, device=DEV)                                  # noqa: E731
     with pytest.raises((SnuffyHipError, ValueError)):
-        ops.sparse_attn_fwd_x3_dk256(z(64, 512), z(64, 512), z(1025, 512), 2)
+        op(ROW, "single")(z(64, D_K), z(64, D_K), z(1025, D_K), 2)
     with pytest.raises((SnuffyHipError, ValueError)):
-        ops.sparse_attn_fwd_x3_dk256(z(64, 256), z(64, 256), z(8, 256), 2)     # dk = 128
+        op(ROW, "single")(z(64, 256), z(64, 256), z(8, 256), 2)     # dk = 128
 
 
 # ---- varlen -----------------------------------------------------------------------------------------------------------------------------
-LENGTHS = [None, 777, 1024, 1025, 4100]           # None: exactly k rows; a row-tile tail, the last directly stored length; reduced bags
-KEYS = [20, 64, 100, 128, 129, 900, 1024]
-
-
-def _packed(sizes):
-    return _ops().PackedBags(sizes, DEV)
-
-
-def _sizes(k):
-    return [k if n is None else n for n in LENGTHS if n is None or n >= k]
-
-
-_REF64 = {}
-
-
-def _fp64_reference(tag, q, v, kp, h):
-    """softmax(Q Kp^T / sqrt(dk))^T V of one bag in fp64, computed once per key count."""
-    if tag not in _REF64:
-        o, _ = orc.sparse_attention(q.double().cpu(), kp.double().cpu(), v.double().cpu(), h)
-        _REF64[tag] = o
-    return _REF64[tag]
+KEYS = ROW.KEYS
 
 
 @pytest.mark.parametrize("k", KEYS)
@@ -121,15 +92,15 @@ def test_attention_varlen_x3_dk256_vs_per_bag_and_composition_independent(k, nee
     g = torch.Generator().manual_seed(1)
     qv = torch.randn(pk.total, 2 * d, generator=g).to(DEV)
     kp = (torch.randn(pk.bags * k, d, generator=g) * 0.5).to(DEV)
-    assert ops.varlen_attn_x3_dk256_supported(k) and not ops.varlen_attn_chunks_supported("fp32", k, d // h)
-    varlen = ops.sparse_attn_fwd_x3_varlen
+    assert op(ROW, "varlen_supported")(k) and not ops.varlen_attn_chunks_supported(ROW.kind, k, d // h)
+    varlen = op(ROW, "varlen")
     q, v = qv[:, :d], qv[:, d:]
     out, attn, lse = varlen(q, v, kp, pk, k, h, need_attn=need_attn, need_lse=need_attn)
     assert out.shape == (pk.bags * k, d)
     for b, n in enumerate(sizes):
         lo = int(pk.host[b])
         qb, kb = qv[lo:lo + n], kp[b * k:(b + 1) * k]
-        o1, a1, l1 = ops.sparse_attn_fwd_x3_dk256(qb[:, :d], qb[:, d:], kb, h, need_attn=need_attn, need_lse=need_attn)
+        o1, a1, l1 = op(ROW, "single")(qb[:, :d], qb[:, d:], kb, h, need_attn=need_attn, need_lse=need_attn)
         err, ref = (out[b * k:(b + 1) * k] - o1).abs().max().item(), o1.abs().max().item()
         print("x3 dk=256 k=%d bag %d n=%d: |out - single| / max|out| = %.3g" % (k, b, n, err / ref))
         # the single-bag entry point spreads a small bag over more workgroups (one tile each; a packed bag takes up to 32 tiles per
@@ -146,10 +117,10 @@ def test_attention_varlen_x3_dk256_vs_per_bag_and_composition_independent(k, nee
     # against fp64 on one bag (the kernels agree with each other; this pins them to the definition)
     b = 1
     lo, n = int(pk.host[b]), sizes[b]
-    ref = _fp64_reference(k, qv[lo:lo + n, :d], qv[lo:lo + n, d:], kp[b * k:(b + 1) * k], h)
+    ref = _fp64_reference((ROW.id, k), qv[lo:lo + n, :d], qv[lo:lo + n, d:], kp[b * k:(b + 1) * k], h, oracle=True)
     err = rel_err(out[b * k:(b + 1) * k].cpu(), ref)
     print("x3 dk=256 k=%d: relative error against fp64 %.3g" % (k, err))
-    assert err < (2e-5 if k <= 256 else 4e-5), err
+    assert err < ROW.O_FP64[k > 256], err
     # a repeat call is bit-identical
     out_r, attn_r, lse_r = varlen(q, v, kp, pk, k, h, need_attn=need_attn, need_lse=need_attn)
     assert torch.equal(out, out_r)
@@ -158,11 +129,9 @@ def test_attention_varlen_x3_dk256_vs_per_bag_and_composition_independent(k, nee
 
 
 # ---- model level ------------------------------------------------------------------------------------------------------------------------
-D, H, LAM, R, ACT = 512, 2, 900, 7 / 9, "gelu"
-K_TOP = 200                                        # ceil(900 (1 - 7/9)); the random share draws the other 700
-SIZES = [900, 1100, 1500, 2100, 3000]
-SEED, OFFSET = 1234567, 99
-TOL_FP32 = 1e-3                                    # TOL["fp32"] of tests/test_gpu_model.py
+D, H, LAM, R, ACT = ROW.D, ROW.H, ROW.LAM, ROW.R, ROW.ACT
+K_TOP = ROW.K_TOP                                 # 200 = ceil(900 (1 - 7/9)); the random share draws the other 700
+SIZES = ROW.SIZES
 
 
 def _net(sampler=None, return_attention=True, seed=0, depth=1, precision="fp32"):
@@ -179,60 +148,12 @@ def _net(sampler=None, return_attention=True, seed=0, depth=1, precision="fp32")
     return net
 
 
-def _bags(sizes, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    return [torch.randn(1, n, D, generator=g).to(DEV) for n in sizes]
-
-
-def _loop(net, bags):
-    out, sels = [], []
-    for x in bags:
-        out.append(net(x))
-        sels.append([tuple(None if t is None else t.clone() for t in l.last_selection) for l in net.b_classifier.encoder.layers])
-    return out, sels
-
-
-def _close(ref, got, n, k=LAM):
-    (c0, y0, a0), (c1, y1, a1) = ref, got
-    assert c1.shape == c0.shape and y1.shape == y0.shape and a1.shape == a0.shape == (1, H, n, k)
-    assert torch.equal(c0, c1)                           # critic scores: same kernel, row-wise
-    dy, da = (y0 - y1).abs().max().item(), (a0 - a1).abs().max().item()
-    ds = (a1.sum(-1) - 1).abs().max().item()
-    print("n=%d: |dlogit| %.3g  |dA| %.3g  |rowsum - 1| %.3g" % (n, dy, da, ds))
-    assert dy <= TOL_FP32 and da <= TOL_FP32
-    assert ds <= 1e-5                                    # only the row sum notices a chunk normalised by the wrong statistics
-
-
-def _spy(monkeypatch, name):
-    ops = _ops()
-    calls, real = [], getattr(ops, name)
-
-    def spy(*a, **kw):
-        calls.append(1)
-        return real(*a, **kw)
-
-    monkeypatch.setattr(ops, name, spy)
-    return calls
-
-
-@pytest.fixture
-def pack_on(monkeypatch):
-    from snuffy_amd import packed
-    monkeypatch.setattr(packed, "PACK_X3_DK256", True)
-
-
-@pytest.fixture
-def device_sampler_on(monkeypatch):
-    from snuffy_amd import packed
-    monkeypatch.setattr(packed, "PACK_DEVICE_SAMPLER", True)
-
-
 @pytest.mark.parametrize("depth,precision", [(1, "fp32"),
                                              (2, "bf16")])   # a stack runs the fp32-class kernels whatever precision says: roi.py's route
 @pytest.mark.filterwarnings("ignore:snuffy_amd. precision='bf16' on a stack:RuntimeWarning")
 def test_single_bag_routing_and_oracle(monkeypatch, depth, precision):
     from snuffy_amd import functional as SF
-    new, old = _spy(monkeypatch, "sparse_attn_fwd_x3_dk256"), _spy(monkeypatch, "sparse_attn_fwd_x3u")
+    new, old = _spy(monkeypatch, ROW.single), _spy(monkeypatch, ROW.replaced)
     n = 3000
     net = _net(depth=depth, precision=precision)
     assert net.b_classifier.cfg.compute == "fp32"
@@ -240,13 +161,13 @@ def test_single_bag_routing_and_oracle(monkeypatch, depth, precision):
     sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
     x = torch.randn(n, D, generator=torch.Generator().manual_seed(77))
     _, logits_ref, p_ref, sels = orc.milnet_forward(x, sd, H, ACT, LAM, R, depth, ReplayRNG(9))
-    monkeypatch.setattr(SF, "X3_ATTN_DK256", False)
+    monkeypatch.setattr(SF, ROW.single_switch, False)
     with torch.no_grad():
         np.random.seed(9)
         _, y_off, a_off = net(x.to(DEV).unsqueeze(0))
         sel_off = [tuple(t.clone() for t in l.last_selection) for l in layers]
         assert (len(new), len(old)) == (0, depth)                              # the call list of before: the unfused pair only
-        monkeypatch.setattr(SF, "X3_ATTN_DK256", True)
+        monkeypatch.setattr(SF, ROW.single_switch, True)
         np.random.seed(9)
         _, y_on, a_on = net(x.to(DEV).unsqueeze(0))
         assert (len(new), len(old)) == (depth, depth)
@@ -257,18 +178,18 @@ def test_single_bag_routing_and_oracle(monkeypatch, depth, precision):
     dy, da = (y_on.cpu()[0] - logits_ref).abs().max().item(), (a_on[0].cpu() - p_ref).abs().max().item()
     print("single bag n=%d depth %d against the oracle: |dlogit| %.3g  |dA| %.3g; against the switch-off forward: %.3g  %.3g"
           % (n, depth, dy, da, (y_on - y_off).abs().max().item(), (a_on - a_off).abs().max().item()))
-    assert dy < TOL_FP32 and da < TOL_FP32
-    assert (a_on.sum(-1) - 1).abs().max().item() <= 1e-5
+    assert dy < ROW.ORACLE_TOL and da < ROW.ORACLE_TOL
+    assert (a_on.sum(-1) - 1).abs().max().item() <= ROW.ROWSUM
 
 
 @pytest.mark.parametrize("depth", [1, 2])              # 2: a stack, as roi.py's model is (every layer packs)
 def test_forward_bags_matches_per_bag_forwards(pack_on, monkeypatch, depth):
-    varlen, new, old = (_spy(monkeypatch, "sparse_attn_fwd_x3_varlen"), _spy(monkeypatch, "sparse_attn_fwd_x3_dk256"),
-                        _spy(monkeypatch, "sparse_attn_fwd_x3u"))
+    varlen, new, old = (_spy(monkeypatch, ROW.varlen), _spy(monkeypatch, ROW.single),
+                        _spy(monkeypatch, ROW.replaced))
     from snuffy_amd import functional as SF
-    monkeypatch.setattr(SF, "X3_ATTN_DK256", False)      # the per-bag loop is the route of before
+    monkeypatch.setattr(SF, ROW.single_switch, False)      # the per-bag loop is the route of before
     net = _net(depth=depth)
-    bags = _bags(SIZES)
+    bags = _bags(SIZES, D)
     with torch.no_grad():
         np.random.seed(11)
         ref, sel_ref = _loop(net, bags)
@@ -286,13 +207,13 @@ def test_forward_bags_matches_per_bag_forwards(pack_on, monkeypatch, depth):
         for b in range(len(bags)):                       # selections, random share included: bit-exact
             assert torch.equal(top[b], sel_ref[b][li][0]) and torch.equal(rnd[b], sel_ref[b][li][1]), (li, b)
     for b in range(len(bags)):
-        _close(ref[b], got[b], SIZES[b])
+        _close(ROW, ref[b], got[b], SIZES[b])
 
 
 def test_forward_bags_vs_oracle(pack_on):
-    sizes = [1000, 1300]
+    sizes = ROW.ORACLE_SIZES
     net = _net()
-    bags = _bags(sizes, seed=9)
+    bags = _bags(sizes, D, seed=9)
     sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
     with torch.no_grad():
         np.random.seed(3)
@@ -306,20 +227,12 @@ def test_forward_bags_vs_oracle(pack_on):
         assert np.array_equal(own_top.numpy(), top[b].cpu().numpy())                   # bit-exact top indices per bag
         dy, da = (got[b][1][0].cpu() - logits).abs().max().item(), (got[b][2][0].cpu() - attn).abs().max().item()
         print("bag %d against the oracle: |dlogit| %.3g  |dA| %.3g" % (b, dy, da))
-        assert dy <= TOL_FP32 and da <= TOL_FP32
-
-
-def _place_sampler(net, offset):
-    net.b_classifier.cfg._device_sampler = _ops().DeviceSampler(torch.device(DEV, torch.cuda.current_device()), SEED, offset)
-
-
-def _offset(net):
-    return int(net.b_classifier.cfg._device_sampler.state[1].item())
+        assert dy <= ROW.Y_TOL and da <= ROW.A_TOL
 
 
 def test_device_sampler_one_group_equals_the_loop(pack_on, device_sampler_on):
     net = _net(sampler="device")
-    bags = _bags(SIZES)
+    bags = _bags(SIZES, D)
     with torch.no_grad():
         _place_sampler(net, OFFSET)
         ref, sel_ref = _loop(net, bags)
@@ -330,16 +243,16 @@ def test_device_sampler_one_group_equals_the_loop(pack_on, device_sampler_on):
     top, rnd = net.b_classifier.encoder.layers[0].last_selection_bags
     for b in range(len(bags)):
         assert torch.equal(top[b], sel_ref[b][0][0]) and torch.equal(rnd[b], sel_ref[b][0][1]), b
-        _close(ref[b], got[b], SIZES[b])
+        _close(ROW, ref[b], got[b], SIZES[b])
 
 
 def test_device_sampler_mix_with_a_short_bag(pack_on, device_sampler_on):
     """A 600-row bag (shorter than Lambda: it selects all of its rows) next to the uniform group: pack_groups leaves it to the per-bag
     loop (a ragged group needs two bags, and 600 keys at this width are outside the ragged kernel), which runs after the group and
     draws from the next offset."""
-    sizes = [1100, 600, 1500, 900]
+    sizes = ROW.MIX_SIZES
     net = _net(sampler="device")
-    bags = _bags(sizes, seed=17)
+    bags = _bags(sizes, D, seed=17)
     with torch.no_grad():
         groups = net._pack_groups(bags)
         assert groups == [([0, 2, 3], False)]
@@ -353,8 +266,8 @@ def test_device_sampler_mix_with_a_short_bag(pack_on, device_sampler_on):
             c1, y1, a1 = got[i]
             assert a1.shape == a0.shape == (1, H, sizes[i], min(LAM, sizes[i]))
             assert torch.equal(c0, c1)
-            assert (y0 - y1).abs().max().item() <= TOL_FP32, i
-            assert (a0 - a1).abs().max().item() <= TOL_FP32, i
+            assert (y0 - y1).abs().max().item() <= ROW.Y_TOL, i
+            assert (a0 - a1).abs().max().item() <= ROW.A_TOL, i
 
 
 def test_defaults_route_as_shipped(monkeypatch):
@@ -362,12 +275,12 @@ def test_defaults_route_as_shipped(monkeypatch):
     behind it at every row), packed bags take the varlen launches of the new kernel (PACK_X3_DK256 on: ahead of the loop at every row)."""
     from snuffy_amd import functional as SF
     from snuffy_amd import packed
-    assert SF.X3_ATTN_DK256 is False and packed.PACK_X3_DK256 is True
-    varlen, new, old = (_spy(monkeypatch, "sparse_attn_fwd_x3_varlen"), _spy(monkeypatch, "sparse_attn_fwd_x3_dk256"),
-                        _spy(monkeypatch, "sparse_attn_fwd_x3u"))
-    sizes = [1000, 1100, 2048]
+    assert getattr(SF, ROW.single_switch) is ROW.SHIPPED[0] is False and getattr(packed, ROW.pack_switch) is ROW.SHIPPED[1] is True
+    varlen, new, old = (_spy(monkeypatch, ROW.varlen), _spy(monkeypatch, ROW.single),
+                        _spy(monkeypatch, ROW.replaced))
+    sizes = ROW.SHIPPED_SIZES
     net = _net()
-    bags = _bags(sizes, seed=13)
+    bags = _bags(sizes, D, seed=13)
     with torch.no_grad():
         assert net._packable(bags) and net._pack_groups(bags) == [([0, 1, 2], False)]
         np.random.seed(11)
@@ -377,4 +290,4 @@ def test_defaults_route_as_shipped(monkeypatch):
         ref = [net(x) for x in bags]
         assert (len(varlen), len(new), len(old)) == (1, 0, len(bags))          # the single bag: the unfused pair, as before
     for b, n in enumerate(sizes):
-        _close(ref[b], got[b], n)
+        _close(ROW, ref[b], got[b], n)

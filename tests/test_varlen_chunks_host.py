@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 from snuffy_amd import _ffi
+from tests.attn_widths import _offsets
+from tests.attn_widths import nkb_of_family as _nkb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -17,12 +19,6 @@ VL_DESC = 12
 OLD = {"mfma": "snf_sparse_attn_varlen_plan", "x3": "snf_sparse_attn_x3_varlen_plan"}
 NEW = {"mfma": "snf_sparse_attn_varlen_chunked_plan", "x3": "snf_sparse_attn_x3_varlen_chunked_plan"}
 KMAX = {128: 224, 64: 256}
-
-
-def _offsets(sizes):
-    off = np.zeros(len(sizes) + 1, dtype=np.int64)
-    np.cumsum(sizes, out=off[1:])
-    return off
 
 
 def _old_plan(lib, fam, sizes, k, h, dk):
@@ -49,12 +45,6 @@ def _new_plan(lib, fam, sizes, k, h, dk, table=True):
     assert fn(ctypes.c_void_p(off.ctypes.data), len(sizes), k, h, dk, ctypes.c_void_p(tab.ctypes.data), tab.size, ctypes.byref(need),
               ctypes.byref(ws), None, None) == 0                              # the chunk outputs are nullable
     return 0, tab, ws.value, nc.value, ck.value
-
-
-def _nkb(fam, kc, dk):
-    """Key-block count the family's planner picks for a launch of kc keys."""
-    opts = (1, 2, 4, 6, 7, 8) if fam == "mfma" else (2, 4, 7, 8)
-    return next(o for o in opts if 32 * o >= kc and not (o == 8 and dk == 128))
 
 
 @pytest.mark.parametrize("fam,keys", [("mfma", 113), ("x3", 116)])
