@@ -300,6 +300,16 @@ int snf_sparse_attn_fwd_f32(const float* q, const float* kp, const float* v, int
 int snf_sparse_attn_fwd_x3u_f32(const float* q, int64_t ldq, const float* kp, const float* v, int64_t ldv, int64_t n, int k, int h, int dk,
                                 float scale, float* out, float* attn, float* lse, void* workspace, size_t workspace_bytes,
                                 snf_stream_t stream);
+/* ... and its training forward: out = (P o M)^T V with M the keep-mask of snf_dropout_mask_f32 for the same (dropout_p, seed, offset),
+ * regenerated in registers by the pooling pass (the LDS-staged P^T V kernel draws one Philox group per 16-byte load of P); no mask tensor.
+ * `attn` is required and receives the UNDROPPED P (the convention of snf_sparse_attn_fwd_x3_dropout: snf_sparse_attn_bwd_dropout_f32
+ * regenerates M from the same state); `lse` stays nullable.  dropout_p == 0 is the plain entry; dropout_p outside [0, 1) SNF_EINVAL.
+ * Only the LDS-staged pooling pass has the form: k % 4 == 0, ldv % 4 == 0, 16-byte aligned attn / v and h <= 1023 on top of the plain
+ * entry's limits, anything else SNF_EUNSUPPORTED before any launch (the caller applies the mask tensor to the plain entry's P).
+ * Workspace: the plain entry's with `attn` given (the slice partials). */
+int snf_sparse_attn_fwd_x3u_dropout_f32(const float* q, int64_t ldq, const float* kp, const float* v, int64_t ldv, int64_t n, int k, int h,
+                                        int dk, float scale, float dropout_p, uint64_t seed, uint64_t offset, float* out, float* attn,
+                                        float* lse, void* workspace, size_t workspace_bytes, snf_stream_t stream);
 int snf_sparse_attn_fwd_mfma(const void* q, int64_t ldq, const void* v, int64_t ldv, int qv_dtype, const void* kp,
                              int kp_dtype, int64_t n, int k, int h, int dk, float scale, float* out, float* attn,
                              float* lse, void* workspace, size_t workspace_bytes, snf_stream_t stream);

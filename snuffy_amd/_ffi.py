@@ -83,6 +83,8 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "snf_sparse_attn_fwd_x3u_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_float, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "snf_sparse_attn_fwd_x3u_dropout_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_float,
+                                                    c_float, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "snf_sparse_attn_bwd_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "snf_sparse_attn_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                         c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

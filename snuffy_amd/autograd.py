@@ -53,6 +53,12 @@ X3_TRAIN_GATED_GEMM = True
 # ... and encoder dropout (snuffy.py:108,225,110) inside that chain: Philox masks regenerated in the FFN GEMMs' epilogues and in the dz split
 # pass, a [K, D] mask tensor for the attention output; False: a layer with encoder dropout on takes the generic autograd chain
 FUSED_X3_ENCODER_DROPOUT = True
+# fp32 training at the head widths outside the pipelined x 3 kernels (dk = 96 / 192 / 256: the README's DINO, MAE and SimCLR recipes): the
+# forward of SparseAttnFn and EncoderLayer0X3Fn on the unfused fp32-class pair (ops.sparse_attn_fwd_x3u) with the attention dropout mask
+# regenerated in its pooling pass, so no [h, N, K] mask tensor and no bmm where k % 4 == 0; False: the exact vector-ALU forward plus the
+# mask tensor, as before (x3u_train_ok).  Ships on: no row of tools/x3u_train_time.py is behind the routing of before (1.08 - 1.25 x per
+# optimizer step on the three recipes at N = 8000 / 32768, 5 - 18 % less peak memory, profiles/x3u_train.txt) and no test fails with it on
+X3U_TRAINING = True
 
 _ACT = {
     "relu": F.relu,
@@ -197,6 +203,12 @@ def draw_dropout_state():
     return int(torch.initial_seed()), int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
 
 
+def x3u_train_ok(k, dk):
+    """fp32 operands train on the unfused fp32-class pair: the widths the pipelined x 3 kernels do not take (64 / 128 keep every route they
+    have), unless the exact arithmetic is asked for."""
+    return bool(X3U_TRAINING and SF.FP32_ATTENTION != "exact" and not ops.x3_attn_supported(k, dk) and ops.x3u_attn_supported(k, dk))
+
+
 class SparseAttnFn(torch.autograd.Function):
     """O = dropout(softmax_K(Q Kp^T / sqrt(dk)))^T V per head (snuffy.py:160-168).
 
@@ -204,7 +216,9 @@ class SparseAttnFn(torch.autograd.Function):
     mask is regenerated in registers from (seed, offset) in both (csrc/philox.h) -- no [h, N, K] tensor is stored for it and
     the forward's O is the kernel's own.  Otherwise: fp32-class forward (split-bf16 x 3 on the matrix cores where the shape
     allows, else the exact vector-ALU kernel) with P materialised for the exact backward kernel snf_sparse_attn_bwd_f32; the
-    mask is the same Philox stream written out as a tensor.  With SPARSE_ATTN_FN_WIDE the first route also serves dk = 192 and
+    mask is the same Philox stream written out as a tensor -- or, where the forward applied it itself (x3 within one key chunk; with
+    X3U_TRAINING the unfused pair at the other widths, k % 4 == 0) and nobody asked for the dropped P, regenerated by the backward too.
+    With SPARSE_ATTN_FN_WIDE the first route also serves dk = 192 and
     dk = 256 (their own forward kernels, the backward over key chunks).  Returns (O, P): P is the dropped P in train mode, as
     the reference's attention() returns it."""
 
@@ -241,6 +255,9 @@ class SparseAttnFn(torch.autograd.Function):
         elif ops.x3_attn_supported(k, dk) and SF.FP32_ATTENTION != "exact":
             in_kernel = drop is not None and ops.x3_attn_dropout_supported(k, dk)       # mask applied to P in registers, P written undropped
             out, p, _ = ops.sparse_attn_fwd_x3(q, v, kp, h, need_attn=True, dropout=drop if in_kernel else None)
+        elif not bf16_operands and x3u_train_ok(k, dk):
+            in_kernel = drop is not None and ops.x3u_attn_dropout_supported(k, dk)      # mask applied in the pooling pass, P written undropped
+            out, p, _ = ops.sparse_attn_fwd_x3u(q, kp, v, h, need_attn=True, dropout=drop if in_kernel else None)
         else:
             out, p, _ = ops.sparse_attn_fwd(q, kp, v, h, need_attn=True)
         mask = None
@@ -771,10 +788,14 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
         p_drop = mha.dropout.p if layer.training else 0.0
         drop = (float(p_drop),) + draw_dropout_state() if p_drop > 0.0 else None
         x3 = ops.x3_attn_supported(k, dk) and SF.FP32_ATTENTION != "exact"
-        in_kernel = drop is not None and x3 and ops.x3_attn_dropout_supported(k, dk)
+        x3u = x3u_train_ok(k, dk)                                                         # never together with x3
+        in_kernel = drop is not None and ((x3 and ops.x3_attn_dropout_supported(k, dk)) or (x3u and ops.x3u_attn_dropout_supported(k, dk)))
         if x3:
             # training: the kernel applies the Philox mask to P in registers (O = (P o M)^T V) and writes the undropped P for the backward
             o, p, _ = ops.sparse_attn_fwd_x3(q, v, kp, h, need_attn=True, dropout=drop if in_kernel else None)
+        elif x3u:
+            # the widths outside those kernels: the unfused pair, the mask applied in its pooling pass
+            o, p, _ = ops.sparse_attn_fwd_x3u(q, kp, v, h, need_attn=True, dropout=drop if in_kernel else None)
         else:
             o, p, _ = ops.sparse_attn_fwd(q, kp, v, h, need_attn=True)
         mask = None

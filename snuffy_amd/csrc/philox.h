@@ -56,6 +56,12 @@ __device__ __forceinline__ philox_f4 dropout_mask4(const DropoutState& d, int a,
     return philox_f4{r[0] >= d.thresh ? d.scale : 0.f, r[1] >= d.thresh ? d.scale : 0.f, r[2] >= d.thresh ? d.scale : 0.f,
                      r[3] >= d.thresh ? d.scale : 0.f};
 }
+
+// the same group as 4 keep bits (bit e: key0 + e is kept), for a caller that parks the mask until its operand has landed
+__device__ __forceinline__ unsigned dropout_keep4(const DropoutState& d, int a, int64_t n, int64_t row, int k, int key0) {
+    const philox_f4 m = dropout_mask4(d, a, n, row, k, key0);
+    return (m[0] != 0.f ? 1u : 0u) | (m[1] != 0.f ? 2u : 0u) | (m[2] != 0.f ? 4u : 0u) | (m[3] != 0.f ? 8u : 0u);
+}
 #endif
 
 }  // namespace snf

@@ -1160,10 +1160,14 @@ __global__ __launch_bounds__(256) void ragged_attn_kernel(const float* __restric
 // ([32 rows, 32 CT columns]) is fetched with coalesced 16-byte loads a whole chunk (128 MFMAs per wave) ahead, parked in registers, then in LDS,
 // and the MFMA operands are conflict-free dword reads.  Against pt_v_mfma_kernel (a wave per slice, every operand straight from L2): V is read
 // k / 256 times instead of k / 64, and nothing waits on L2 inside the MFMA stream.  Same row pairs in the same order: bit-identical partials.
-template <int CT>
+// DROP (the training forward): out = (P o M)^T V with M the Philox keep-mask of snf_dropout_mask_f32, regenerated here.  A thread's P loads
+// are groups of 4 keys at a multiple of 4 of one global row -- one dropout_mask4 group each.  The rounds run right behind the issue of a
+// stage's loads (they need no loaded data), their 32 keep bits ride in one register beside the stage, and the multiply happens on the way
+// into LDS.  Every column group of a width regenerates the same mask: twice the Philox work at dk = 192 / 256, no bytes.
+template <int CT, bool DROP>
 __global__ __launch_bounds__(256, 2) void pt_v_lds_kernel(const float* __restrict__ p /*[h,n,k]*/, const float* __restrict__ v, int64_t n, int k,
                                                           int h, int dk, int64_t rows_per_slice, float* __restrict__ partial /*[slices,h,k,dk]*/,
-                                                          int ldv) {
+                                                          int ldv, const snf::DropoutState drop) {
     constexpr int PP = 256, PV = 32 * CT;                      // row pitches (floats) of the staged chunks
     __shared__ __attribute__((aligned(16))) float lp[32 * PP];
     __shared__ __attribute__((aligned(16))) float lv[32 * PV];
@@ -1178,6 +1182,7 @@ __global__ __launch_bounds__(256, 2) void pt_v_lds_kernel(const float* __restric
     const float* va = v + a * dk;
     struct Stage {
         f32x4 pp[8], vv[CT];
+        unsigned keep;                                         // DROP: bit 4 i + e = element e of pp[i] is kept
     };
     auto load_stage = [&](int64_t r0, Stage& st) __attribute__((always_inline)) {
 #pragma unroll
@@ -1196,12 +1201,28 @@ __global__ __launch_bounds__(256, 2) void pt_v_lds_kernel(const float* __restric
             st.vv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (row < r_end && col + 4 <= dk) st.vv[i] = *reinterpret_cast<const f32x4*>(va + row * ldv + col);
         }
+        if constexpr (DROP) {                                  // behind the loads' issue: rows past r_end / keys past k hold zeros, no group drawn
+            // (one group after the other: unrolled, the eight independent Philox chains ran side by side and their registers did not
+            // fit next to the 128 accumulators and the stage in flight)
+            st.keep = 0u;
+            const int key = kt0 + 4 * (threadIdx.x & 63);
+#pragma unroll 1
+            for (int i = 0; i < 8; ++i) {
+                const int64_t row = r0 + (threadIdx.x >> 6) + 4 * i;
+                if (row < r_end && key + 4 <= k) st.keep |= snf::dropout_keep4(drop, a, n, row, k, key) << (4 * i);
+            }
+        }
     };
     auto park_stage = [&](const Stage& st) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int idx = threadIdx.x + 256 * i;
-            *reinterpret_cast<f32x4*>(lp + (idx >> 6) * PP + 4 * (idx & 63)) = st.pp[i];
+            f32x4 pv = st.pp[i];
+            if constexpr (DROP) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pv[e] = (st.keep >> (4 * i + e)) & 1u ? pv[e] * drop.scale : 0.f;
+            }
+            *reinterpret_cast<f32x4*>(lp + (idx >> 6) * PP + 4 * (idx & 63)) = pv;
         }
 #pragma unroll
         for (int i = 0; i < CT; ++i) {
@@ -1257,22 +1278,36 @@ __global__ __launch_bounds__(256, 2) void pt_v_lds_kernel(const float* __restric
 
 std::atomic<bool> g_pt_v_lds{true};      // snf_debug_exact_attn_mfma(2): the direct-from-L2 kernels (A / B partners of the LDS-staged ones)
 
+// the shapes pt_v_lds_kernel takes (16-byte P / V loads, one grid plane per slice and head)
+bool pt_v_lds_form_ok(const float* p, const float* v, int k, int h, int dk, int ldv, int64_t rows_per_slice, int slices) {
+    return k % 4 == 0 && dk % 4 == 0 && ldv % 4 == 0 && (rows_per_slice & 1) == 0 &&
+           ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(v)) & 15) == 0 && (int64_t)slices * h <= 65535;
+}
+
+template <bool DROP>
+int launch_pt_v_lds(const float* p, const float* v, int64_t n, int k, int h, int dk, int64_t rows_per_slice, int slices, float* partial,
+                    hipStream_t s, int ldv, const snf::DropoutState drop) {
+    const int ncb = (dk + 31) / 32;
+    const int ctl = ncb % 3 == 0 ? 3 : (ncb % 4 == 0 || ncb > 4) ? 4 : ncb;
+    dim3 grid((unsigned)((k + 255) / 256), (unsigned)((ncb + ctl - 1) / ctl), (unsigned)(slices * h));
+#define LAUNCH_PTV(CT) \
+    hipLaunchKernelGGL((pt_v_lds_kernel<CT, DROP>), grid, dim3(256), 0, s, p, v, n, k, h, dk, rows_per_slice, partial, ldv, drop)
+    switch (ctl) {
+        case 1: LAUNCH_PTV(1); break;
+        case 2: LAUNCH_PTV(2); break;
+        case 3: LAUNCH_PTV(3); break;
+        default: LAUNCH_PTV(4); break;
+    }
+#undef LAUNCH_PTV
+    return snf::check_launch("pt_v_lds_kernel");
+}
+
 int launch_pt_v_mfma(const float* p, const float* v, int64_t n, int k, int h, int dk, int64_t rows_per_slice, int slices, float* partial,
                      hipStream_t s, int ldv = 0) {
     if (ldv == 0) ldv = h * dk;
     const int ncb = (dk + 31) / 32;
-    if (g_pt_v_lds && k % 4 == 0 && dk % 4 == 0 && ldv % 4 == 0 && (rows_per_slice & 1) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(v)) & 15) == 0 && (int64_t)slices * h <= 65535) {
-        const int ctl = ncb % 3 == 0 ? 3 : (ncb % 4 == 0 || ncb > 4) ? 4 : ncb;
-        dim3 grid((unsigned)((k + 255) / 256), (unsigned)((ncb + ctl - 1) / ctl), (unsigned)(slices * h));
-        switch (ctl) {
-            case 1: hipLaunchKernelGGL((pt_v_lds_kernel<1>), grid, dim3(256), 0, s, p, v, n, k, h, dk, rows_per_slice, partial, ldv); break;
-            case 2: hipLaunchKernelGGL((pt_v_lds_kernel<2>), grid, dim3(256), 0, s, p, v, n, k, h, dk, rows_per_slice, partial, ldv); break;
-            case 3: hipLaunchKernelGGL((pt_v_lds_kernel<3>), grid, dim3(256), 0, s, p, v, n, k, h, dk, rows_per_slice, partial, ldv); break;
-            default: hipLaunchKernelGGL((pt_v_lds_kernel<4>), grid, dim3(256), 0, s, p, v, n, k, h, dk, rows_per_slice, partial, ldv); break;
-        }
-        return snf::check_launch("pt_v_lds_kernel");
-    }
+    if (g_pt_v_lds && pt_v_lds_form_ok(p, v, k, h, dk, ldv, rows_per_slice, slices))
+        return launch_pt_v_lds<false>(p, v, n, k, h, dk, rows_per_slice, slices, partial, s, ldv, snf::make_dropout(0.f, 0, 0));
     const int ct = ncb % 3 == 0 ? 3 : (ncb % 4 == 0 || ncb > 4) ? 4 : ncb;          // 96 / 192 -> 3, 128 / 256 -> 4, 64 -> 2, 32 -> 1
     dim3 grid((unsigned)(((k + 31) / 32 + 1) / 2), (unsigned)((ncb + ct - 1) / ct), (unsigned)(((slices + 3) / 4) * h));
     switch (ct) {
@@ -1369,6 +1404,15 @@ static int bwd_impl(const float* q, int64_t ldq, const float* kp, const float* v
         snf::set_error("snf_sparse_attn_bwd_ld_f32: row pitches other than h dk need the matrix-core kernels (dk %% 8 == 0, k <= 1024, 16-byte rows)");
         return SNF_EUNSUPPORTED;
     }
+    const bool lds_ok = g_dq_dv_lds && k % 4 == 0 && dk % 4 == 0 &&
+                        ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(ds) | reinterpret_cast<uintptr_t>(dout) |
+                          reinterpret_cast<uintptr_t>(kp) | (mask ? reinterpret_cast<uintptr_t>(mask) : 0)) & 15) == 0;
+    // a Philox state instead of a mask tensor: only bwd_ds_mfma_kernel and bwd_dq_dv_lds_kernel regenerate the mask
+    if (!mask && drop.thresh != 0u && !(mfma_ok && k <= 1024 && lds_ok)) {
+        snf::set_error("snf_sparse_attn_bwd_dropout_f32: k=%d dk=%d (or a pointer that is not 16-byte aligned) outside the kernels that regenerate "
+                       "the mask: hand it over as a tensor (snf_dropout_mask_f32 + snf_sparse_attn_bwd_ld_f32)", k, dk);
+        return SNF_EUNSUPPORTED;
+    }
     if (mfma_ok && k <= 1024) {
         const size_t lds_m = (size_t)(32 * (dk + 4) + 128) * sizeof(float);
         dim3 grid1((unsigned)((n + 31) / 32), (unsigned)h);
@@ -1400,9 +1444,6 @@ static int bwd_impl(const float* q, int64_t ldq, const float* kp, const float* v
         const int ncb = (dk + 31) / 32;
         const int ct = ncb % 3 == 0 ? 3 : (ncb >= 4 ? 4 : ncb);
         dim3 grid2((unsigned)((n + 127) / 128), (unsigned)((ncb + ct - 1) / ct), (unsigned)h);
-        const bool lds_ok = g_dq_dv_lds && k % 4 == 0 && dk % 4 == 0 &&
-                            ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(ds) | reinterpret_cast<uintptr_t>(dout) |
-                              reinterpret_cast<uintptr_t>(kp) | (mask ? reinterpret_cast<uintptr_t>(mask) : 0)) & 15) == 0;
         if (lds_ok) {
             switch (ct) {
                 case 1: rc = launch_dq_dv_lds<1>(p, mask, ds, dout, kp, n, k, h, dk, dq, dv, grid2, s, drop); break;
@@ -1544,9 +1585,10 @@ int snf_sparse_attn_fwd_f32(const float* q, const float* kp, const float* v, int
 
 // fp32-CLASS attention for head widths outside the pipelined kernels: scores + softmax in split-bf16 x 3 on the bf16 matrix cores
 // (operands split on the fly), P^T V exact on the f32 matrix cores.  dk % 16 == 0, dk <= 256, k <= 1024; same outputs / workspace as snf_sparse_attn_fwd_f32.
-int snf_sparse_attn_fwd_x3u_f32(const float* q, int64_t ldq, const float* kp, const float* v, int64_t ldv, int64_t n, int k, int h, int dk,
-                                float scale, float* out, float* attn, float* lse, void* workspace, size_t workspace_bytes,
-                                snf_stream_t stream) {
+// (drop == nullptr: the plain pooling; else out = (P o M)^T V on the DROP form of pt_v_lds_kernel, which has no partner outside its shapes)
+static int fwd_x3u_impl(const float* q, int64_t ldq, const float* kp, const float* v, int64_t ldv, int64_t n, int k, int h, int dk,
+                        float scale, const snf::DropoutState* drop, float* out, float* attn, float* lse, void* workspace,
+                        size_t workspace_bytes, snf_stream_t stream) {
     SNF_REQUIRE(q && kp && v && out, "snf_sparse_attn_fwd_x3u_f32: null pointer");
     SNF_REQUIRE(n >= 1 && k >= 1 && h >= 1 && h <= 65535, "snf_sparse_attn_fwd_x3u_f32: bad shape n=%lld k=%d h=%d", (long long)n, k, h);
     SNF_REQUIRE(ldq >= (int64_t)h * dk && ldv >= (int64_t)h * dk && ldq % 4 == 0 && ldv < (1 << 24),
@@ -1565,6 +1607,13 @@ int snf_sparse_attn_fwd_x3u_f32(const float* q, int64_t ldq, const float* kp, co
     float* p = attn ? attn : reinterpret_cast<float*>(workspace);
     float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (attn ? 0 : pbytes));
     hipStream_t s = snf::as_stream(stream);
+    const int64_t rows_per_slice = (((n + slices - 1) / slices) + 15) & ~(int64_t)15;
+    if (drop && !pt_v_lds_form_ok(p, v, k, h, dk, (int)ldv, rows_per_slice, slices)) {
+        snf::set_error("snf_sparse_attn_fwd_x3u_dropout_f32: k=%d dk=%d ldv=%lld h=%d outside the LDS pooling pass (k %% 4 == 0, ldv %% 4 == 0, "
+                       "16-byte aligned attn / v, slices x h <= 65535): apply the mask of snf_dropout_mask_f32 to the plain entry's P", k, dk,
+                       (long long)ldv, h);
+        return SNF_EUNSUPPORTED;
+    }
     // two row tiles per workgroup (every Kp fragment used twice) once the bag gives every CU a few such workgroups; up to 4 key blocks per wave
     const int kbw = ((k + 31) / 32 + 3) / 4;
     const int rt = (kbw <= 4 && n * h >= (int64_t)64 * 4 * snf::cu_count() && 64 * (4 * dk + 16) + 2048 <= 64 * 1024) ? 2 : 1;
@@ -1584,14 +1633,31 @@ int snf_sparse_attn_fwd_x3u_f32(const float* q, int64_t ldq, const float* kp, co
 #undef LAUNCH_SX
     int rc = snf::check_launch("scores_softmax_x3u_kernel");
     if (rc) return rc;
-    const int64_t rows_per_slice = (((n + slices - 1) / slices) + 15) & ~(int64_t)15;
-    rc = launch_pt_v_mfma(p, v, n, k, h, dk, rows_per_slice, slices, partial, s, (int)ldv);
+    rc = drop ? launch_pt_v_lds<true>(p, v, n, k, h, dk, rows_per_slice, slices, partial, s, (int)ldv, *drop)
+              : launch_pt_v_mfma(p, v, n, k, h, dk, rows_per_slice, slices, partial, s, (int)ldv);
     if (rc) return rc;
     const int64_t total = (int64_t)h * k * dk;
     int rgrid = (int)((total + 255) / 256);
     if (rgrid > 2048) rgrid = 2048;
     hipLaunchKernelGGL(reduce_slices_kernel, dim3(rgrid), dim3(256), 0, s, partial, slices, k, h, dk, out);
     return snf::check_launch("reduce_slices_kernel");
+}
+
+int snf_sparse_attn_fwd_x3u_f32(const float* q, int64_t ldq, const float* kp, const float* v, int64_t ldv, int64_t n, int k, int h, int dk,
+                                float scale, float* out, float* attn, float* lse, void* workspace, size_t workspace_bytes,
+                                snf_stream_t stream) {
+    return fwd_x3u_impl(q, ldq, kp, v, ldv, n, k, h, dk, scale, nullptr, out, attn, lse, workspace, workspace_bytes, stream);
+}
+
+// the training forward of the pair: out = (P o M)^T V, M regenerated in the pooling pass from (dropout_p, seed, offset); attn = the undropped P
+int snf_sparse_attn_fwd_x3u_dropout_f32(const float* q, int64_t ldq, const float* kp, const float* v, int64_t ldv, int64_t n, int k, int h,
+                                        int dk, float scale, float dropout_p, uint64_t seed, uint64_t offset, float* out, float* attn,
+                                        float* lse, void* workspace, size_t workspace_bytes, snf_stream_t stream) {
+    SNF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "snf_sparse_attn_fwd_x3u_dropout_f32: dropout_p = %f", (double)dropout_p);
+    SNF_REQUIRE(attn, "snf_sparse_attn_fwd_x3u_dropout_f32: attn is required (it receives the undropped P the backward reads)");
+    if (dropout_p == 0.f) return snf_sparse_attn_fwd_x3u_f32(q, ldq, kp, v, ldv, n, k, h, dk, scale, out, attn, lse, workspace, workspace_bytes, stream);
+    const snf::DropoutState drop = snf::make_dropout(dropout_p, seed, offset);
+    return fwd_x3u_impl(q, ldq, kp, v, ldv, n, k, h, dk, scale, &drop, out, attn, lse, workspace, workspace_bytes, stream);
 }
 
 // Ragged varlen attention, exact fp32 (see ragged_attn_kernel).  desc_dev [bags][4] int32 = (row0, n, key0, k) per bag in DEVICE

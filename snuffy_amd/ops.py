@@ -885,10 +885,18 @@ def x3u_attn_supported(k, dk):
     return dk % 16 == 0 and 16 <= dk <= 256 and 1 <= k <= 1024
 
 
-def sparse_attn_fwd_x3u(q, kp, v, h, scale=None, need_attn=False, need_lse=False):
+def x3u_attn_dropout_supported(k, dk):
+    """The unfused pair applies the training dropout mask in its pooling pass (snf_sparse_attn_fwd_x3u_dropout_f32: the LDS-staged P^T V
+    kernel, whose 16-byte P loads need k % 4 == 0)."""
+    return x3u_attn_supported(k, dk) and k % 4 == 0
+
+
+def sparse_attn_fwd_x3u(q, kp, v, h, scale=None, need_attn=False, need_lse=False, dropout=None):
     """fp32-class sparse attention for head widths like 192 (snf_sparse_attn_fwd_x3u_f32: scores + softmax in split-bf16 x 3 on the
     bf16 matrix cores with the operands split on the fly, P^T V exact on the f32 matrix cores).  q, v [n, d] f32 (row-strided views
-    allowed: the halves of a fused [Q | V] projection), kp [k, d] f32 -> (out, attn or None, lse or None)."""
+    allowed: the halves of a fused [Q | V] projection), kp [k, d] f32 -> (out, attn or None, lse or None).  dropout = (p, seed, offset):
+    the training forward (snf_sparse_attn_fwd_x3u_dropout_f32, x3u_attn_dropout_supported shapes, need_attn=True): out = (P o M)^T V with
+    M the mask ops.dropout_mask writes for the same (p, seed, offset); attn stays the UNDROPPED P."""
     if q.dtype != torch.float32 or v.dtype != torch.float32:
         raise TypeError("sparse_attn_fwd_x3u: q and v must be float32")
     q = _rows16(q, "q")
@@ -900,6 +908,9 @@ def sparse_attn_fwd_x3u(q, kp, v, h, scale=None, need_attn=False, need_lse=False
         raise ValueError("d_model %d not divisible by h %d" % (d, h))
     dk = d // h
     scale = 1.0 / math.sqrt(dk) if scale is None else scale
+    dropped = dropout is not None and float(dropout[0]) > 0.0
+    if dropped and not need_attn:
+        raise ValueError("sparse_attn_fwd_x3u: dropout needs need_attn=True (attn receives the undropped P the backward reads)")
     lib = _ffi.load()
     out = torch.empty(k, d, dtype=torch.float32, device=q.device)
     attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
@@ -908,6 +919,12 @@ def sparse_attn_fwd_x3u(q, kp, v, h, scale=None, need_attn=False, need_lse=False
     if need_attn:
         wsb -= ((h * n * k * 4 + 255) // 256) * 256
     ws = _ws(wsb, q.device)
+    if dropped:
+        check(lib.snf_sparse_attn_fwd_x3u_dropout_f32(_p(q), q.stride(0), _p(kp), _p(v), v.stride(0), n, k, h, dk, float(scale),
+                                                      float(dropout[0]), int(dropout[1]) & (2 ** 64 - 1), int(dropout[2]) & (2 ** 64 - 1),
+                                                      _p(out), _p(attn), _p(lse), _p(ws), wsb, _stream()),
+              "snf_sparse_attn_fwd_x3u_dropout_f32")
+        return out, attn, lse
     check(lib.snf_sparse_attn_fwd_x3u_f32(_p(q), q.stride(0), _p(kp), _p(v), v.stride(0), n, k, h, dk, float(scale), _p(out), _p(attn),
                                           _p(lse), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_x3u_f32")
     return out, attn, lse
