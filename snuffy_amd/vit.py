@@ -553,6 +553,13 @@ class VisionTransformer(nn.Module):
         use_mfma = ops.vit_mfma_attention_supported(T, dk)
         if BF16_FUSED_BLOCK and use_mfma and self._fused_ok():
             return self._blocks_fused(xt, W, B, T)
+        return self._blocks_unfused(xt, W, B, T)
+
+    def _blocks_unfused(self, xt, W, B, T):
+        """The round-2 blocks of the bf16 path on the fp32 token matrix xt [B * T, D] (updated in place): LayerNorm fused with the
+        residual adds (vit_residual_ln_) between bf16 GEMMs; the attention on the MFMA kernel where it applies, exact fp32 otherwise."""
+        heads = self.num_heads
+        use_mfma = ops.vit_mfma_attention_supported(T, self.embed_dim // heads)
         n1 = self.blocks[0].norm1
         ln = ops.layernorm_rows(xt, n1.weight, n1.bias, n1.eps, out_dtype=torch.bfloat16)
         for i, blk in enumerate(self.blocks):

@@ -294,3 +294,70 @@ def synth_state(D, h, depth, seed=0):
         if isinstance(m, torch.nn.Linear):
             torch.nn.init.zeros_(m.bias)
     return net
+
+
+# ---- ViT blocks: drawn state dicts, token rows, the exact fp64 blocks ---------------------------------------------------------------------
+VIT_EPS = 1e-6
+VIT_ROW_KINDS = ("plain", "offset", "outliers")
+
+
+def vit_block_state(d, depth=1, bott=0, qkv_bias=True, scale_param=None, mlp_ratio=4, seed=0, up_gain=1.0):
+    """State dict of `depth` ViT blocks under the reference's key names, nothing at its init value: LayerNorm gamma = 1 + 0.2 randn,
+    beta = 0.2 randn, Linear weights randn / sqrt(k), biases 0.2 randn, the adapter's up-projection NON-zero (the LoRA zero init would
+    hide the branch).  bott = 0: no adapter.  scale_param: the value of adaptmlp.scale where it is a parameter ("learnable_scalar").
+    up_gain multiplies the up-projection: 1 / scalar for a model whose adapter scalar is 10, so that the scaled branch is of the size of
+    the MLP's and does not set the scale of the block's update by itself (an error of the other branches would hide behind it)."""
+    g = torch.Generator().manual_seed(1000 + seed)
+
+    def lin(sd, name, n, k, bias=True):
+        sd[name + ".weight"] = torch.randn(n, k, generator=g) / k ** 0.5
+        if bias:
+            sd[name + ".bias"] = 0.2 * torch.randn(n, generator=g)
+
+    sd = {}
+    for i in range(depth):
+        pre = "blocks.%d." % i
+        for nm in ("norm1", "norm2"):
+            sd[pre + nm + ".weight"] = 1.0 + 0.2 * torch.randn(d, generator=g)
+            sd[pre + nm + ".bias"] = 0.2 * torch.randn(d, generator=g)
+        lin(sd, pre + "attn.qkv", 3 * d, d, qkv_bias)
+        lin(sd, pre + "attn.proj", d, d)
+        lin(sd, pre + "mlp.fc1", mlp_ratio * d, d)
+        lin(sd, pre + "mlp.fc2", d, mlp_ratio * d)
+        if bott:
+            if scale_param is not None:
+                sd[pre + "adaptmlp.scale"] = torch.tensor([float(scale_param)])
+            lin(sd, pre + "adaptmlp.down_proj", bott, d)
+            lin(sd, pre + "adaptmlp.up_proj", d, bott)
+            sd[pre + "adaptmlp.up_proj.weight"] *= up_gain
+            sd[pre + "adaptmlp.up_proj.bias"] *= up_gain
+    return sd
+
+
+def vit_token_rows(kind, rows, d, seed=0):
+    """Token matrix [rows, d] f32.  plain: randn; offset: randn + 4 (sign alternating by row: |row mean| = 4 row spreads); outliers:
+    randn with channel 5 = +150 and channel 77 = -60 in every row (two massive activations, row mean ~ 0)."""
+    g = torch.Generator().manual_seed(2000 + seed)
+    x = torch.randn(rows, d, generator=g)
+    if kind == "offset":
+        x += 4.0 * (1.0 - 2.0 * (torch.arange(rows) % 2)).unsqueeze(1)
+    elif kind == "outliers":
+        x[:, 5], x[:, 77] = 150.0, -60.0
+    elif kind != "plain":
+        raise ValueError(kind)
+    return x
+
+
+def vit_blocks_update_fp64(x, sd, b, t, heads, depth, adapter_scale, images_per_pass=8):
+    """blocks(x) - x in float64 for the token matrix x [b * t, d]: oracle.vit_oracle.block over the drawn state dict, a few images at a
+    time (images do not interact; the [B, h, T, T] probabilities of all of them at once would not fit at T = 785)."""
+    from oracle import vit_oracle as vorc
+    sd64 = {k: v.double() for k, v in sd.items()}
+    x3 = x.double().view(b, t, -1)
+    out = torch.empty_like(x3)
+    for i in range(0, b, images_per_pass):
+        y = x3[i:i + images_per_pass]
+        for j in range(depth):
+            y = vorc.block(y, sd64, "blocks.%d." % j, heads, adapter_scale, VIT_EPS)
+        out[i:i + images_per_pass] = y
+    return (out - x3).view(b * t, -1)
