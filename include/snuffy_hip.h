@@ -152,6 +152,11 @@ int snf_layernorm_bwd_blocks(int64_t n);
 int snf_layernorm_rows_bwd_f32(const float* x, int64_t n, int d, const void* dy, int dy_dtype, int64_t dy_stride,
                                const float* gamma, float eps, const float* residual, float* dx, void* dx_bf16,
                                float* partials, snf_stream_t stream);
+/* Host-only query, no launch: the register form the row passes above (critic, LayerNorm rows and their backward, the mean-pooled
+ * head) run a row of d floats in.  *vec = 4 (16-byte vectors: d % 4 == 0 and every operand 16-byte aligned -- all_aligned != 0) or 1;
+ * *nv = the 64-lane vector groups a wave holds per row.  vec / nv nullable.  SNF_EUNSUPPORTED when d is too wide for the
+ * register-resident passes (d > 2048). */
+int snf_row_form(int d, int all_aligned, int* vec, int* nv);
 /* bf16 path: the LayerNorm affine of SublayerConnection (snuffy.py:97,107,110) folded into the projection that follows it
  * (LN(x) W^T + b = xhat (W * gamma)^T + (W beta + b)), and the gradients of the folded weights taken back to (W, b, gamma, beta):
  *   fold:    wf_bf16[r, c] = bf16(w[r, c] * gamma[c]) (row pitch ldwf);  bf[r] = sum_c w[r, c] * beta[c] + bias[r] (f32 / bf16, nullable)

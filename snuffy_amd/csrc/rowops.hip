@@ -84,13 +84,52 @@ __device__ __forceinline__ void store_row_bf16(unsigned short* __restrict__ row,
     }
 }
 
+// Row statistics, normalisation and affine of layernorm_rows_kernel and of critic_kernel<LN>, whose images are promised to be equal bit
+// for bit: ONE body, with floating-point contraction off.  Left to the compiler, `sum * inv_d` was fused into the subtractions or into
+// `var + eps` in some instantiations of one kernel and not of the other (VEC 4 NV 8 and the hl critic at NV 3 among them), which moves
+// the last place of mean / rstd wherever d is no power of two -- and a bf16 rounding of the normalised value with it.
+template <int VEC, int NV>
+__device__ __forceinline__ void normalise_row(float (&r)[NV * VEC], int d, int lane, float inv_d, float eps, float& mean, float& rstd) {
+#pragma clang fp contract(off)
+    float s1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV * VEC; ++i) s1 += r[i];
+    mean = wave_sum(s1) * inv_d;
+    float s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+#pragma unroll
+        for (int t = 0; t < VEC; ++t) {
+            int e = (i * 64 + lane) * VEC + t;
+            float dv = (e < d) ? (r[i * VEC + t] - mean) : 0.f;
+            s2 = fmaf(dv, dv, s2);
+        }
+    }
+    const float var = wave_sum(s2) * inv_d;
+    rstd = 1.0f / sqrtf(var + eps);
+#pragma unroll
+    for (int i = 0; i < NV * VEC; ++i) r[i] = (r[i] - mean) * rstd;
+}
+
+template <int N>
+__device__ __forceinline__ void affine_row(float (&r)[N], const float (&g)[N], const float (&bt)[N], bool scale, bool shift) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        float v = r[i];
+        if (scale) v *= g[i];
+        if (shift) v += bt[i];
+        r[i] = v;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // K1 critic: scores[i, c] = x[i,:] . w[c,:] + b[c]          (FCLayer.forward, snuffy.py:39-41)
 // ---------------------------------------------------------------------------------------------------------------
 // LN = also emit the row-normalised bf16 copy (x - mean) * rstd that the first encoder layer needs (its LayerNorm affine is
 // folded into the projection weights): the bag is read from HBM once for both, instead of once per kernel.
 // LN == 2 (fp32-class path): emit LayerNorm(x) WITH its affine as the interleaved hi / lo image the one-pass GEMM reads
-// (the output of snf_layernorm_rows_hl_f32 up to the last fp32 place of the normalised value) instead of the affine-free bf16 copy.
+// (the output of snf_layernorm_rows_hl_f32, bit for bit: normalise_row / affine_row) instead of the affine-free bf16 copy.
 template <int VEC, int NV, int LN>
 __global__ __launch_bounds__(WG) void critic_kernel(const float* __restrict__ x, int64_t n, int d,
                                                     const float* __restrict__ w, const float* __restrict__ b,
@@ -142,25 +181,9 @@ __global__ __launch_bounds__(WG) void critic_kernel(const float* __restrict__ x,
             acc = wave_sum(acc);
             if (lane == 0) scores[row * c_out + c] = acc + (b ? b[c] : 0.f);
         }
-        if constexpr (LN != 0) {   // same arithmetic, in the same order, as layernorm_rows_kernel
-            float s1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < NV * VEC; ++i) s1 += r[i];
-            const float mean = wave_sum(s1) * inv_d;
-            float s2 = 0.f;
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-#pragma unroll
-                for (int t = 0; t < VEC; ++t) {
-                    int e = (i * 64 + lane) * VEC + t;
-                    float dv = (e < d) ? (r[i * VEC + t] - mean) : 0.f;
-                    s2 = fmaf(dv, dv, s2);
-                }
-            }
-            const float var = wave_sum(s2) * inv_d;
-            const float rstd = 1.0f / sqrtf(var + eps);
-#pragma unroll
-            for (int i = 0; i < NV * VEC; ++i) r[i] = (r[i] - mean) * rstd;
+        if constexpr (LN != 0) {   // the arithmetic of layernorm_rows_kernel: the same body
+            float mean, rstd;
+            normalise_row<VEC, NV>(r, d, lane, inv_d, eps, mean, rstd);
             if constexpr (LN == 1) store_row_bf16<VEC, NV>(xhat + row * d, d, lane, r);
             if constexpr (LN == 2 && VEC == 4) {
                 // affine (the registers that held the critic weights' row are free again only after the loop: gamma / beta are
@@ -170,10 +193,7 @@ __global__ __launch_bounds__(WG) void critic_kernel(const float* __restrict__ x,
                     float g[NV * VEC], bt[NV * VEC];
                     load_row<VEC, NV>(gamma, d, lane, g);
                     load_row<VEC, NV>(beta, d, lane, bt);
-#pragma unroll
-                    for (int i = 0; i < NV * VEC; ++i) {
-                        r[i] = fmaf(r[i], g[i], bt[i]);
-                    }
+                    affine_row(r, g, bt, true, true);
                 }
                 unsigned short* o2 = xhat + row * 2 * d;
 #pragma unroll
@@ -285,29 +305,9 @@ __global__ __launch_bounds__(WG) void layernorm_rows_kernel(const float* __restr
 #pragma unroll
             for (int i = 0; i < NV * VEC; ++i) r[i] += ad[i];
         }
-        float s1 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV * VEC; ++i) s1 += r[i];
-        const float mean = wave_sum(s1) * inv_d;
-        float s2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-#pragma unroll
-            for (int t = 0; t < VEC; ++t) {
-                int e = (i * 64 + lane) * VEC + t;
-                float dv = (e < d) ? (r[i * VEC + t] - mean) : 0.f;
-                s2 = fmaf(dv, dv, s2);
-            }
-        }
-        const float var = wave_sum(s2) * inv_d;
-        const float rstd = 1.0f / sqrtf(var + eps);
-#pragma unroll
-        for (int i = 0; i < NV * VEC; ++i) {
-            float v = (r[i] - mean) * rstd;
-            if (gamma) v *= g[i];
-            if (beta) v += bt[i];
-            r[i] = v;
-        }
+        float mean, rstd;
+        normalise_row<VEC, NV>(r, d, lane, inv_d, eps, mean, rstd);
+        affine_row(r, g, bt, gamma != nullptr, beta != nullptr);
         const int64_t orow = out_row_idx ? out_row_idx[row] : row;
         if (out_f32) store_row_f32<VEC, NV>(out_f32 + orow * d, d, lane, r);
         if (out_bf16 && !split3) store_row_bf16<VEC, NV>(out_bf16 + orow * d, d, lane, r);
@@ -1689,6 +1689,18 @@ int snf_layernorm_rows_split3_f32(const float* x, int64_t n, int d, const int32_
 }
 
 int snf_layernorm_bwd_blocks(int64_t n) { return row_grid(n); }
+
+int snf_row_form(int d, int all_aligned, int* vec, int* nv) {
+    SNF_REQUIRE(d >= 1, "snf_row_form: bad width d=%d", d);
+    RowCfg cfg;
+    if (!pick_row_cfg(d, all_aligned != 0, &cfg)) {
+        snf::set_error("snf_row_form: d=%d too wide (max 2048)", d);
+        return SNF_EUNSUPPORTED;
+    }
+    if (vec) *vec = cfg.vec;
+    if (nv) *nv = cfg.nv;
+    return SNF_OK;
+}
 
 int snf_layernorm_rows_bwd_f32(const float* x, int64_t n, int d, const void* dy, int dy_dtype, int64_t dy_stride,
                                const float* gamma, float eps, const float* residual, float* dx, void* dx_bf16,

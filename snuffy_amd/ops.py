@@ -160,7 +160,7 @@ def critic_select(x, w, b, eps=None):
 
 def critic_ln_hl(x, w, b, gamma, beta, eps):
     """One pass over the bag for the fp32-class path: (scores [n, c] f32, LayerNorm(x) with its affine as the interleaved hi / lo
-    image [n, 2 d] bf16 -- the operand layernorm_rows_hl() would produce, to the last fp32 place of the normalised value).  With one class and a bag long enough for
+    image [n, 2 d] bf16 -- the operand layernorm_rows_hl() would produce, bit for bit).  With one class and a bag long enough for
     the fused selector the pass also counts the selector's histogram (the following topk() starts from it)."""
     x = _req(x, torch.float32, "x", 2)
     w = _req(w, torch.float32, "w", 2)

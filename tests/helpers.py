@@ -129,6 +129,23 @@ def grad_close(got, want, tol, name):
     assert err < tol * 4 * scale_ or rel_err(got.cpu(), want) < tol, name
 
 
+# ---- row passes: the LayerNorm backward in fp64, the split of an fp32 value into bf16 hi / lo ----------------------------------------------
+def _ln_reference(x, dy, gamma, eps, residual):
+    x = x.double().requires_grad_(True)
+    g = gamma.double().requires_grad_(True)
+    b = torch.zeros_like(g).requires_grad_(True)
+    y = torch.nn.functional.layer_norm(x, (x.shape[1],), g, b, eps)
+    y.backward(dy.double().expand_as(y))
+    dx = x.grad + (residual.double() if residual is not None else 0)
+    return dx, g.grad, b.grad
+
+
+def _split_host(x):
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    return hi, lo
+
+
 # ---- the encoder layer's training chains against their plain-torch restatement ---------------------------------------------------------
 def _perturbed_state_dict(n, d, h, lam):
     torch.manual_seed(n)

@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import _split_host
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -92,12 +94,6 @@ def test_gemm_rejects_unsupported_shapes():
 
 
 # ---- fp32-class projections: split-bf16 x3 over a tripled K axis ---------------------------------------------------------
-def _split_host(x):
-    hi = x.to(torch.bfloat16)
-    lo = (x - hi.float()).to(torch.bfloat16)
-    return hi, lo
-
-
 @pytest.mark.parametrize("n,d", [(700, 384), (513, 768), (64, 96), (1000, 100)])
 def test_layernorm_rows_split3_is_the_split_of_the_fp32_rows(n, d):
     """snf_layernorm_rows_split3_f32 == [hi | hi | lo] of snf_layernorm_rows_f32's fp32 output, bit for bit (incl. patch rows)."""

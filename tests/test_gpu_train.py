@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import build_amd_milnet, golden_files, load_case
+from tests.helpers import _ln_reference, build_amd_milnet, golden_files, load_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -169,16 +169,6 @@ def test_multiclass_gradients_match_oracle_autograd():
         assert float((p.grad.cpu() - g_ref).abs().max()) / denom < 2e-3, name
         checked += 1
     assert checked >= 20
-
-
-def _ln_reference(x, dy, gamma, eps, residual):
-    x = x.double().requires_grad_(True)
-    g = gamma.double().requires_grad_(True)
-    b = torch.zeros_like(g).requires_grad_(True)
-    y = torch.nn.functional.layer_norm(x, (x.shape[1],), g, b, eps)
-    y.backward(dy.double().expand_as(y))
-    dx = x.grad + (residual.double() if residual is not None else 0)
-    return dx, g.grad, b.grad
 
 
 @pytest.mark.gpu
