@@ -618,6 +618,21 @@ int snf_vit_attention_f32(const float* qkv, int b, int t, int h, int dk, float s
 int snf_vit_attention_mfma(const void* qkv_bf16, int b, int t, int h, int dk, float scale, void* out_bf16,
                            snf_stream_t stream);
 int snf_vit_attention_x3_f32(const float* qkv, int b, int t, int h, int dk, float scale, void* out, int out_dtype, snf_stream_t stream);
+/* Training pair of the MFMA self-attention (adapter pre-training, snuffy_amd/ssl_pretrain.py): O(b h t) saved state.
+ *   snf_vit_attention_fwd_lse  the forward above with one more output, lse [b, h, t] f32 = log sum_j exp(scale q_i . k_j) (natural
+ *       log).  dtype SNF_DT_BF16: the program of snf_vit_attention_mfma (bf16 in / out); SNF_DT_F32: the program of
+ *       snf_vit_attention_x3_f32 (fp32 in / out).  `out` is bit for bit what those entry points write; same shape domain.
+ *   snf_vit_attention_bwd      qkv as given to the forward, dout [b*t, h*dk], lse from the forward -> dqkv [b*t, 3*h*dk] laid out as
+ *       qkv (dQ | dK | dV), every element written.  SNF_DT_F32: fp32 tensors, every product hi hi + hi lo + lo hi on the bf16 matrix
+ *       cores with fp32 accumulation (P and dS split in registers); SNF_DT_BF16: bf16 tensors, P and dS rounded to bf16 as operands,
+ *       fp32 accumulation.  Neither the probabilities nor the forward's output are needed: P is rebuilt from q, k and lse, and
+ *       D_i = sum_j P_ij dP_ij.  Deterministic (no atomics, one summation order).  dk == 64, 1 <= t <= SNF_VIT_BWD_MAX_T (the keys
+ *       of an (image, head) in one LDS image), b <= 65535, qkv / dout / dqkv 16-byte aligned; anything else: SNF_EUNSUPPORTED. */
+#define SNF_VIT_BWD_MAX_T 256
+int snf_vit_attention_fwd_lse(const void* qkv, int dtype, int b, int t, int h, int dk, float scale, void* out, float* lse,
+                              snf_stream_t stream);
+int snf_vit_attention_bwd(const void* qkv, const void* dout, const float* lse, int dtype, int b, int t, int h, int dk, float scale,
+                          void* dqkv, snf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Tile preprocessing for the extractor, batched on the device     replaces the per-tile CPU transforms of

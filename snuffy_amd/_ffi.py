@@ -226,6 +226,9 @@ SIGNATURES = {
     "snf_debug_exact_attn_mfma": (None, [c_int]),
     "snf_vit_attention_mfma": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "snf_vit_attention_x3_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
+    "snf_vit_attention_fwd_lse": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "snf_vit_attention_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                      c_void_p]),
 }
 
 # The entry points of the native head widths (csrc/attn_width.h): one workspace and one varlen-plan signature for both families, one

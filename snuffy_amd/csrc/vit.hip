@@ -343,7 +343,7 @@ constexpr int VIT_ATTN_THREADS = 512;   // 8 waves: one 32-query tile each (T = 
 template <int NKB, bool CHUNK, bool X3>
 __global__ __launch_bounds__(VIT_ATTN_THREADS, (X3 || CHUNK) ? 2 : 4) void vit_attention_mfma_kernel(const void* __restrict__ qkv_, int B, int T,
                                                                                           int h, float scale, void* __restrict__ out_,
-                                                                                          int tpw, int out_hl) {
+                                                                                          int tpw, int out_hl, float* __restrict__ lse) {
     constexpr int DK = 64;
     constexpr int NW = VIT_ATTN_THREADS / 64;   // waves per workgroup = query tiles in flight
     constexpr int NP = X3 ? 2 : 1;            // operand planes (hi, lo)
@@ -547,6 +547,8 @@ __global__ __launch_bounds__(VIT_ATTN_THREADS, (X3 || CHUNK) ? 2 : 4) void vit_a
         const float inv = __builtin_amdgcn_rcpf(l);
         const int q_out = 32 * tile + j;
         if (q_out < T) {
+            // the row statistic a backward rebuilds P from: log sum_j exp(scale s_j) = scale max + log l  (nullable)
+            if (lse && hf == 0) lse[((int64_t)b * h + a) * T + q_out] = fmaf(m_run, scale, __builtin_amdgcn_logf(l) * 0.69314718055994530942f);
             elt_t* op = out + (base + q_out) * D + a * DK;
             static_for<0, 2>([&](auto db) __attribute__((always_inline)) {
 #pragma unroll
@@ -609,7 +611,7 @@ __global__ __launch_bounds__(VIT_ATTN_THREADS, (X3 || CHUNK) ? 2 : 4) void vit_a
 }
 
 template <int NKB, bool CHUNK, bool X3>
-int launch_vit_mfma(const void* qkv, int B, int T, int h, float scale, void* out, hipStream_t s, int out_hl = 0) {
+int launch_vit_mfma(const void* qkv, int B, int T, int h, float scale, void* out, hipStream_t s, int out_hl = 0, float* lse = nullptr) {
     constexpr size_t lds = (size_t)(X3 ? 2 : 1) * ((size_t)(32 * NKB * (64 + 8)) * sizeof(unsigned short) + (size_t)32 * NKB * 128);
     static_assert(lds <= 160 * 1024, "vit_attention_mfma: LDS budget");
     auto kern = vit_attention_mfma_kernel<NKB, CHUNK, X3>;
@@ -620,8 +622,26 @@ int launch_vit_mfma(const void* qkv, int B, int T, int h, float scale, void* out
     const int ntile = (T + 31) / 32;
     const int nz = CHUNK ? (ntile + 7) / 8 : 1;
     const int tpw = CHUNK ? (ntile + nz - 1) / nz : 0;
-    hipLaunchKernelGGL(kern, dim3(h, B, nz), dim3(VIT_ATTN_THREADS), lds, s, qkv, B, T, h, scale, out, tpw, out_hl);
+    hipLaunchKernelGGL(kern, dim3(h, B, nz), dim3(VIT_ATTN_THREADS), lds, s, qkv, B, T, h, scale, out, tpw, out_hl, lse);
     return snf::check_launch("vit_attention_mfma_kernel");
+}
+
+// the launch tables of the two arithmetics (lse nullable: the per-row log-sum-exp [B, h, T] a backward needs)
+int vit_mfma_bf16(const void* qkv, int b, int t, int h, float scale, void* out, hipStream_t s, float* lse) {
+    const int nkb = (t + 31) / 32;
+    if (nkb <= 2) return launch_vit_mfma<2, false, false>(qkv, b, t, h, scale, out, s, 0, lse);
+    if (nkb <= 4) return launch_vit_mfma<4, false, false>(qkv, b, t, h, scale, out, s, 0, lse);
+    if (nkb <= 7) return launch_vit_mfma<7, false, false>(qkv, b, t, h, scale, out, s, 0, lse);
+    if (nkb <= 8) return launch_vit_mfma<8, false, false>(qkv, b, t, h, scale, out, s, 0, lse);
+    return launch_vit_mfma<8, true, false>(qkv, b, t, h, scale, out, s, 0, lse);   // keys in chunks of 256 (patch 8: t = 785)
+}
+
+int vit_mfma_x3(const void* qkv, int b, int t, int h, float scale, void* out, hipStream_t s, int out_hl, float* lse) {
+    const int nkb = (t + 31) / 32;
+    if (nkb <= 2) return launch_vit_mfma<2, false, true>(qkv, b, t, h, scale, out, s, out_hl, lse);
+    if (nkb <= 4) return launch_vit_mfma<4, false, true>(qkv, b, t, h, scale, out, s, out_hl, lse);
+    if (nkb <= 7) return launch_vit_mfma<7, false, true>(qkv, b, t, h, scale, out, s, out_hl, lse);
+    return launch_vit_mfma<7, true, true>(qkv, b, t, h, scale, out, s, out_hl, lse);               // keys in chunks of 224
 }
 
 inline int grid_for(int64_t work_items, int per_block) {
@@ -731,13 +751,7 @@ int snf_vit_attention_mfma(const void* qkv_bf16, int b, int t, int h, int dk, fl
         return SNF_EUNSUPPORTED;
     }
     SNF_REQUIRE((reinterpret_cast<uintptr_t>(qkv_bf16) & 15) == 0, "snf_vit_attention_mfma: qkv must be 16-byte aligned");
-    hipStream_t s = snf::as_stream(stream);
-    const int nkb = (t + 31) / 32;
-    if (nkb <= 2) return launch_vit_mfma<2, false, false>(qkv_bf16, b, t, h, scale, out_bf16, s);
-    if (nkb <= 4) return launch_vit_mfma<4, false, false>(qkv_bf16, b, t, h, scale, out_bf16, s);
-    if (nkb <= 7) return launch_vit_mfma<7, false, false>(qkv_bf16, b, t, h, scale, out_bf16, s);
-    if (nkb <= 8) return launch_vit_mfma<8, false, false>(qkv_bf16, b, t, h, scale, out_bf16, s);
-    return launch_vit_mfma<8, true, false>(qkv_bf16, b, t, h, scale, out_bf16, s);   // keys in chunks of 256 (patch 8: t = 785)
+    return vit_mfma_bf16(qkv_bf16, b, t, h, scale, out_bf16, snf::as_stream(stream), nullptr);
 }
 
 int snf_vit_attention_x3_f32(const float* qkv, int b, int t, int h, int dk, float scale, void* out, int out_dtype, snf_stream_t stream) {
@@ -750,12 +764,21 @@ int snf_vit_attention_x3_f32(const float* qkv, int b, int t, int h, int dk, floa
         return SNF_EUNSUPPORTED;
     }
     SNF_REQUIRE((reinterpret_cast<uintptr_t>(qkv) & 15) == 0, "snf_vit_attention_x3_f32: qkv must be 16-byte aligned");
-    hipStream_t s = snf::as_stream(stream);
-    const int nkb = (t + 31) / 32;
-    if (nkb <= 2) return launch_vit_mfma<2, false, true>(qkv, b, t, h, scale, out, s, out_hl);
-    if (nkb <= 4) return launch_vit_mfma<4, false, true>(qkv, b, t, h, scale, out, s, out_hl);
-    if (nkb <= 7) return launch_vit_mfma<7, false, true>(qkv, b, t, h, scale, out, s, out_hl);
-    return launch_vit_mfma<7, true, true>(qkv, b, t, h, scale, out, s, out_hl);               // keys in chunks of 224
+    return vit_mfma_x3(qkv, b, t, h, scale, out, snf::as_stream(stream), out_hl, nullptr);
+}
+
+int snf_vit_attention_fwd_lse(const void* qkv, int dtype, int b, int t, int h, int dk, float scale, void* out, float* lse,
+                              snf_stream_t stream) {
+    SNF_REQUIRE(qkv && out && lse, "snf_vit_attention_fwd_lse: null pointer");
+    SNF_REQUIRE(dtype == SNF_DT_F32 || dtype == SNF_DT_BF16, "snf_vit_attention_fwd_lse: dtype is f32 (fp32 class) or bf16 (got %d)", dtype);
+    SNF_REQUIRE(b >= 1 && t >= 1 && h >= 1, "snf_vit_attention_fwd_lse: bad shape");
+    if (dk != 64 || t > SNF_VIT_MFMA_MAX_T || b > 65535) {
+        snf::set_error("snf_vit_attention_fwd_lse: unsupported shape dk=%d t=%d (need dk == 64, t <= %d)", dk, t, SNF_VIT_MFMA_MAX_T);
+        return SNF_EUNSUPPORTED;
+    }
+    SNF_REQUIRE((reinterpret_cast<uintptr_t>(qkv) & 15) == 0, "snf_vit_attention_fwd_lse: qkv must be 16-byte aligned");
+    if (dtype == SNF_DT_F32) return vit_mfma_x3(qkv, b, t, h, scale, out, snf::as_stream(stream), 0, lse);
+    return vit_mfma_bf16(qkv, b, t, h, scale, out, snf::as_stream(stream), lse);
 }
 
 }  // extern "C"

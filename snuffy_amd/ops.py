@@ -2294,6 +2294,66 @@ def vit_mfma_attention_supported(t, dk):
     return dk == 64 and t <= VIT_MFMA_MAX_T
 
 
+VIT_BWD_MAX_T = 256      # SNF_VIT_BWD_MAX_T of include/snuffy_hip.h: the keys of an (image, head) in one LDS image
+
+
+def vit_attention_bwd_supported(t, dk):
+    """Shapes snf_vit_attention_bwd serves (pure host): everything else trains on the autograd composition."""
+    return dk == 64 and 1 <= t <= VIT_BWD_MAX_T
+
+
+def _vit_train_dims(qkv, b, t, heads, what):
+    if not isinstance(qkv, torch.Tensor) or qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("%s: qkv must be a float32 (fp32 class) or bfloat16 tensor" % what)
+    qkv = _req(qkv, qkv.dtype, "qkv", 2)
+    d3 = qkv.shape[1]
+    if qkv.shape[0] != b * t or d3 % (3 * heads) != 0:
+        raise ValueError("%s: qkv has shape %s, need [b * t, 3 * heads * dk] with b=%d t=%d heads=%d"
+                         % (what, tuple(qkv.shape), b, t, heads))
+    return qkv, d3 // 3, d3 // 3 // heads
+
+
+def vit_attention_fwd_lse(qkv, b, t, heads, scale=None, arithmetic=None):
+    """The MFMA self-attention forward of `vit_attention` with the row statistic a backward needs: (out [B*T, D], lse [B, h, T] f32,
+    natural log).  fp32 qkv -> fp32-class arithmetic ("x3"), bf16 qkv -> bf16 ("bf16"); `arithmetic`, when given, must name the
+    form of qkv's dtype.  `out` is bit for bit what `vit_attention` returns in that form.  dk == 64, T <= VIT_MFMA_MAX_T."""
+    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, "vit_attention_fwd_lse")
+    form = "x3" if qkv.dtype == torch.float32 else "bf16"
+    if arithmetic is not None and arithmetic != form:
+        raise ValueError("vit_attention_fwd_lse: arithmetic=%r needs %s qkv, got %s"
+                         % (arithmetic, "float32" if arithmetic == "x3" else "bfloat16", qkv.dtype))
+    scale = dk ** -0.5 if scale is None else scale
+    out = torch.empty(b * t, d, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
+    check(_ffi.load().snf_vit_attention_fwd_lse(_p(qkv), DT_F32 if form == "x3" else DT_BF16, b, t, heads, dk, float(scale), _p(out),
+                                                _p(lse), _stream()), "snf_vit_attention_fwd_lse")
+    return out, lse
+
+
+def vit_attention_bwd(qkv, dout, lse, b, t, heads, scale=None, out=None):
+    """dqkv [B*T, 3*D] (dQ | dK | dV, the layout of qkv) from the qkv given to `vit_attention_fwd_lse`, its lse and dout [B*T, D].
+    The form follows qkv's dtype (fp32: fp32 class; bf16: bf16).  Deterministic; dk == 64 and 1 <= T <= VIT_BWD_MAX_T, anything
+    else raises (ask `vit_attention_bwd_supported`).  `out`: a contiguous tensor of qkv's shape and dtype to write into (every element
+    is written; default: a new one)."""
+    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, "vit_attention_bwd")
+    dout = _req(dout, qkv.dtype, "dout", 2)
+    lse = _req(lse, torch.float32, "lse", 3)
+    if tuple(dout.shape) != (b * t, d):
+        raise ValueError("vit_attention_bwd: dout has shape %s, need %s" % (tuple(dout.shape), (b * t, d)))
+    if tuple(lse.shape) != (b, heads, t):
+        raise ValueError("vit_attention_bwd: lse has shape %s, need %s" % (tuple(lse.shape), (b, heads, t)))
+    scale = dk ** -0.5 if scale is None else scale
+    if out is None:
+        dqkv = torch.empty_like(qkv)
+    else:
+        dqkv = _req(out, qkv.dtype, "out", 2)
+        if dqkv is not out or out.shape != qkv.shape:
+            raise ValueError("vit_attention_bwd: out must be a contiguous tensor of qkv's shape %s" % (tuple(qkv.shape),))
+    check(_ffi.load().snf_vit_attention_bwd(_p(qkv), _p(dout), _p(lse), DT_F32 if qkv.dtype == torch.float32 else DT_BF16, b, t, heads,
+                                            dk, float(scale), _p(dqkv), _stream()), "snf_vit_attention_bwd")
+    return dqkv
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # ResNet-18 patch extractor (csrc/resnet.hip): NHWC activations, implicit-GEMM convolutions on the matrix cores
 # ----------------------------------------------------------------------------------------------------------------------

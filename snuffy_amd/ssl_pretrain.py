@@ -12,8 +12,13 @@ Counterparts in the reference (what a user of `dino_adapter/main_dino_adapter.py
   MAEPretrainModel (encoder + decoder + masked-patch loss)        mae_adapter/models_mae.py:21-246
   dino_train_step / mae_train_step                                main_dino_adapter.py:485-552, mae_adapter/engine_pretrain.py:21-81
 
-This is a TRAINING path: it runs on PyTorch-ROCm autograd (library GEMMs); the hand-written inference kernels of the extractor
-(snuffy_amd/vit.py under torch.no_grad) are not differentiable and are not used here.  State-dict keys are the reference's, so a
+This is a TRAINING path on PyTorch-ROCm autograd.  The self-attention of every block runs on the project's own kernels
+(ViTAttentionFn: csrc/vit.hip forward with its row log-sum-exp, csrc/vit_attn_bwd.hip backward; fp32-class arithmetic for fp32
+tensors, bf16 under torch.autocast(bfloat16)), which keep qkv and one fp32 per query row instead of the [B, h, T, T] probabilities;
+that holds for dk == 64 and T <= 256 on the GPU (switch: FUSED_ATTENTION).  T = 785 (patch 8), the MAE decoder (dk = 32), CPU
+tensors and a block that needs no gradient stay on the composition of torch ops, as do every Linear, LayerNorm and GELU (library
+GEMMs); the other hand-written inference kernels of the extractor (snuffy_amd/vit.py under torch.no_grad) are not differentiable
+and are not used here.  State-dict keys are the reference's, so a
 checkpoint written here ('teacher' / 'model') loads into compute_feats exactly like the reference's (compute_feats.py:441-504).
 Several ranks: one process per GPU, gradients of the trainable (adapter + head) parameters averaged with ONE flat all-reduce per
 step (train.FlatGradAllReduce; backend "nccl" = RCCL), the DINO centre with one all-reduce of [1, out_dim].
@@ -24,8 +29,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
-from . import vit
+from . import ops, vit
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -37,10 +43,38 @@ def _patch_tokens(model, x):
     return F.conv2d(x, pe.proj.weight, pe.proj.bias, stride=pe.patch_size).flatten(2).transpose(1, 2)
 
 
+# Self-attention of a training step on the MFMA kernels (dk == 64, T <= 256, GPU, a gradient asked for).  Off: the composition of
+# torch ops everywhere, as before the kernels existed.  DESIGN.md section 4 has the measurements behind the shipped value.
+FUSED_ATTENTION = True
+
+
+class ViTAttentionFn(torch.autograd.Function):
+    """softmax(q k^T * scale) v on the qkv Linear output [B*T, 3*D] -> [B*T, D]; saves qkv and lse [B, h, T] only."""
+
+    @staticmethod
+    def forward(ctx, qkv, b, t, heads, scale):
+        out, lse = ops.vit_attention_fwd_lse(qkv, b, t, heads, scale)
+        ctx.save_for_backward(qkv, lse)
+        ctx.dims = (b, t, heads, scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        qkv, lse = ctx.saved_tensors
+        b, t, heads, scale = ctx.dims
+        return ops.vit_attention_bwd(qkv, dout.contiguous(), lse, b, t, heads, scale), None, None, None, None
+
+
 def _attention(attn, x):
     b, t, d = x.shape
     h = attn.num_heads
-    qkv = F.linear(x, attn.qkv.weight, attn.qkv.bias).view(b, t, 3, h, d // h).permute(2, 0, 3, 1, 4)
+    qkv = F.linear(x, attn.qkv.weight, attn.qkv.bias)
+    if (FUSED_ATTENTION and qkv.is_cuda and qkv.requires_grad and qkv.dtype in (torch.float32, torch.bfloat16)
+            and ops.vit_attention_bwd_supported(t, d // h)):
+        o = ViTAttentionFn.apply(qkv.view(b * t, 3 * d), b, t, h, attn.scale)
+        return F.linear(o.view(b, t, d), attn.proj.weight, attn.proj.bias)
+    qkv = qkv.view(b, t, 3, h, d // h).permute(2, 0, 3, 1, 4)
     p = ((qkv[0] @ qkv[1].transpose(-2, -1)) * attn.scale).softmax(dim=-1)
     return F.linear((p @ qkv[2]).transpose(1, 2).reshape(b, t, d), attn.proj.weight, attn.proj.bias)
 

@@ -1,0 +1,221 @@
+"""What the differentiable MFMA self-attention (ssl_pretrain.ViTAttentionFn: csrc/vit.hip forward with lse, csrc/vit_attn_bwd.hip
+backward) buys adapter pre-training, against the parent's path -- the composition of torch ops under autograd (ssl_pretrain.FUSED_ATTENTION off).
+
+    python tools/vit_attn_train_time.py [--rounds 3] [--window 0.5] [--out profiles/vit_attn_train.txt] [--only errors|attention|dino|mae]
+
+  errors      lse and dQ / dK / dV of both arithmetics against float64 autograd over the table of tests/test_gpu_vit_attn_train.py, the torch
+              composition of the same dtype beside them (the figures that test bounds)
+  attention   forward + backward of ssl_pretrain._attention (qkv Linear, attention, proj Linear; fp32) at the recipes' shapes:
+              DINO ViT-S/16 global views B = 128, T = 197, h = 6; local views B = 512, T = 37, h = 6; MAE ViT-B/16 encoder at 75 % masking
+              B = 64, T = 50, h = 12
+  dino        one dino_train_step of ViT-S/16 + adapters at 64 tiles (2 x 224^2 + 8 x 96^2), adapter tuning (trunk frozen)
+  mae         one mae_train_step of the ViT-B/16 MAE-adapter model at batch 64, adapters training (trunk frozen)
+
+One process; switch off and on alternate round by round; every leg is warmed, then timed with device events over a window of at least
+--window seconds; the spread is min / median / max of the rounds.  A row is BEHIND when the medians' ratio is under 1 and the ranges do
+not overlap, LEVEL when they do.  Peak memory: torch.cuda.max_memory_allocated over one step after a warm step."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+TABLE = [(1, 1, 1), (2, 17, 1), (2, 32, 2), (2, 33, 1), (2, 37, 2), (3, 50, 3), (2, 197, 6), (2, 224, 2), (2, 225, 2), (2, 256, 2)]
+FWD_ONLY = [(2, 785, 2), (1, 257, 2)]
+
+
+def composition(qkv, b, t, h):
+    d = qkv.shape[1] // 3
+    q, k, v = qkv.view(b, t, 3, h, d // h).permute(2, 0, 3, 1, 4)
+    s = (q @ k.transpose(-2, -1)) * (d // h) ** -0.5
+    return (s.softmax(-1) @ v).transpose(1, 2).reshape(b * t, d), s
+
+
+def errors(say, dev):
+    import torch
+    from snuffy_amd import ops
+
+    def rel(a, b):
+        return float((a.double() - b).abs().max() / b.abs().max().clamp_min(1e-30))
+
+    say("kernels against float64 autograd on the same operands (bf16 form: operands rounded to bf16 first); rel = max |a - b| / max |b|;")
+    say("'torch' = the composition of torch ops in the form's dtype on the device")
+    say("%-6s %-14s %10s | %10s %10s %10s | %10s %10s %10s" % ("form", "(b, t, h)", "lse abs", "dQ rel", "dK rel", "dV rel", "torch dQ", "torch dK", "torch dV"))
+    worst = {}
+    for form in ("x3", "bf16"):
+        for b, t, h in TABLE + FWD_ONLY:
+            g = torch.Generator().manual_seed(1000 * t + 10 * h + b)
+            qkv = torch.randn(b * t, 3 * h * 64, generator=g) * 1.5
+            dout = torch.randn(b * t, h * 64, generator=g)
+            if form == "bf16":
+                qkv, dout = qkv.bfloat16(), dout.bfloat16()
+            q64 = qkv.to(dev).double().requires_grad_(True)
+            out, s = composition(q64, b, t, h)
+            out.backward(dout.to(dev).double())
+            qd, dd = qkv.to(dev), dout.to(dev)
+            _, lse = ops.vit_attention_fwd_lse(qd, b, t, h)
+            e_lse = float((lse.double() - torch.logsumexp(s.detach(), -1)).abs().max())
+            worst[(form, "lse")] = max(worst.get((form, "lse"), 0.0), e_lse)
+            if (b, t, h) in FWD_ONLY:
+                say("%-6s %-14s %10.3g | (forward only: above the backward's T)" % (form, (b, t, h), e_lse))
+                continue
+            dqkv = ops.vit_attention_bwd(qd, dd, lse, b, t, h)
+            qc = qd.clone().requires_grad_(True)
+            composition(qc, b, t, h)[0].backward(dd)
+            d = h * 64
+            cols = []
+            for got in (dqkv, qc.grad):
+                for lo in (0, d, 2 * d):
+                    want = q64.grad[:, lo:lo + d]
+                    cols.append(rel(got[:, lo:lo + d], want) if float(want.abs().max()) > 0 else float(got[:, lo:lo + d].abs().max()))
+            worst[(form, "bwd")] = max([worst.get((form, "bwd"), 0.0)] + cols[:3])
+            say("%-6s %-14s %10.3g | %10.3g %10.3g %10.3g | %10.3g %10.3g %10.3g" % ((form, (b, t, h), e_lse) + tuple(cols)))
+    for form in ("x3", "bf16"):
+        say("largest over the table, %s: lse %.3g, backward %.3g" % (form, worst[(form, "lse")], worst[(form, "bwd")]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--window", type=float, default=0.5)
+    ap.add_argument("--out")
+    ap.add_argument("--only", help="'errors', 'attention', 'dino' or 'mae'")
+    args = ap.parse_args()
+    import torch
+    from snuffy_amd import ssl_pretrain as S
+    from snuffy_amd import vit
+    if not torch.cuda.is_available():
+        print("no GPU: nothing measured")
+        return 1
+    dev = torch.device("cuda:0")
+    lines = []
+
+    def say(s):
+        lines.append(s + "\n")
+        print(s, flush=True)
+        if args.out:
+            open(args.out, "w").writelines(lines)
+
+    def window(fn):
+        """ms per call: device events around batches of calls until --window seconds of device time have been covered."""
+        fn()
+        torch.cuda.synchronize()
+        total, n, batch = 0.0, 0, 1
+        while total < 1e3 * args.window or n < 2:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(batch):
+                fn()
+            e1.record()
+            e1.synchronize()
+            dt = e0.elapsed_time(e1)
+            total, n = total + dt, n + batch
+            batch = max(1, min(256, int(batch * 50.0 / max(dt, 1e-3))))      # batches of ~50 ms
+        return total / n
+
+    def alternate(fn):
+        t = {False: [], True: []}
+        for _ in range(args.rounds):
+            for on in (False, True):
+                S.FUSED_ATTENTION = on
+                torch.manual_seed(5)
+                t[on].append(window(fn))
+        return sorted(t[False]), sorted(t[True])
+
+    def peaks(fn):
+        peak = {}
+        for on in (False, True):
+            S.FUSED_ATTENTION = on
+            fn()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            fn()
+            torch.cuda.synchronize()
+            peak[on] = torch.cuda.max_memory_allocated() / 2 ** 20
+        return peak
+
+    def fmt(ts):
+        return "%9.3f %9.3f %9.3f" % (ts[0], ts[len(ts) // 2], ts[-1])
+
+    behind_rows = []
+
+    def row(tag, fn, with_peak):
+        peak = peaks(fn) if with_peak else None
+        off, on_ = alternate(fn)
+        sp = off[len(off) // 2] / on_[len(on_) // 2]
+        behind = sp < 1.0 and on_[0] > off[-1]
+        if behind:
+            behind_rows.append(tag)
+        note = "   BEHIND" if behind else ("" if sp >= 1.0 else "   (level: ranges overlap)")
+        say("%-44s %s %s %7.2fx%s%s" % (tag, fmt(off), fmt(on_), sp, ("  %8.0f -> %-7.0f" % (peak[False], peak[True])) if peak else "", note))
+
+    shipped = S.FUSED_ATTENTION
+    say("adapter pre-training, self-attention on the MFMA kernels (on) against the autograd composition (off); fp32; %s" % torch.cuda.get_device_name(0))
+    if not args.only or args.only == "errors":
+        say("")
+        errors(say, dev)
+    head = "%-44s %29s %29s %8s" % ("ms (min / median / max of %d alternating rounds)" % args.rounds, "off  min    median       max",
+                                    "on   min    median       max", "speedup")
+    if not args.only or args.only == "attention":
+        say("")
+        say("forward + backward of ssl_pretrain._attention (qkv Linear, attention, proj Linear), gradient to the input")
+        say(head)
+        for tag, b, t, d, h in (("DINO ViT-S/16 global B=128 T=197 h=6", 128, 197, 384, 6), ("DINO ViT-S/16 local  B=512 T=37  h=6", 512, 37, 384, 6),
+                                ("MAE  ViT-B/16 enc 75% B=64  T=50  h=12", 64, 50, 768, 12)):
+            torch.manual_seed(1)
+            attn = vit.Attention(d, num_heads=h, qkv_bias=True).to(dev)
+            x = torch.randn(b, t, d, device=dev, requires_grad=True)
+            dy = torch.randn(b, t, d, device=dev)
+
+            def one():
+                x.grad = None
+                S._attention(attn, x).backward(dy)
+
+            row(tag, one, False)
+            del attn, x, dy
+    if not args.only or args.only == "dino":
+        say("")
+        say("one dino_train_step: ViT-S/16 + adapters (adapter tuning), 64 tiles as 2 x 224^2 + 8 x 96^2 crops, out_dim 65536; peak MB off -> on")
+        say(head + "  peak MB off -> on")
+        torch.manual_seed(2)
+
+        def net():
+            bb = vit.vit_small(16, adapter_ffn_layernorm_option="none", adapter_ffn_init_option="lora", adapter_ffn_scalar="0.1",
+                               adapter_ffn_num=64, adapter_d_model=384)
+            return S.MultiCropWrapper(bb, S.DINOHead(384, 65536)).to(dev).train()
+
+        student, teacher = net(), net()
+        teacher.load_state_dict(student.state_dict())
+        for p in teacher.parameters():
+            p.requires_grad = False
+        S.freeze_for_adapter_tuning(student)
+        loss_mod = S.DINOLoss(65536, 10, 0.04, 0.04, 0, 10).to(dev)
+        opt = torch.optim.AdamW(S.get_params_groups(student), lr=1e-5)
+        crops = [torch.randn(64, 3, 224, 224, device=dev) for _ in range(2)] + [torch.randn(64, 3, 96, 96, device=dev) for _ in range(8)]
+        row("dino_train_step 64 tiles", lambda: S.dino_train_step(student, teacher, loss_mod, crops, opt, 1, clip_grad=3.0), True)
+        del student, teacher, loss_mod, opt, crops
+        torch.cuda.empty_cache()
+    if not args.only or args.only == "mae":
+        say("")
+        say("one mae_train_step: ViT-B/16 MAE-adapter model (decoder 512 x 8, 16 heads: dk = 32 stays on the composition), batch 64, mask 0.75")
+        say(head + "  peak MB off -> on")
+        torch.manual_seed(3)
+        model = S.MAEPretrainModel(img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12, decoder_embed_dim=512, decoder_depth=8,
+                                   decoder_num_heads=16, norm_pix_loss=True, adapter_ffn_num=64, adapter_d_model=768).to(dev).train()
+        for n, p in model.named_parameters():
+            p.requires_grad = "adaptmlp" in n
+        opt = torch.optim.AdamW([p for p in model.parameters() if p.requires_grad], lr=1e-5, betas=(0.9, 0.95))
+        imgs = torch.randn(64, 3, 224, 224, device=dev)
+        row("mae_train_step batch 64", lambda: S.mae_train_step(model, imgs, opt), True)
+        del model, opt, imgs
+    S.FUSED_ATTENTION = shipped
+    if not args.only:
+        say("")
+        say("ship rule (on only if no step row is behind outside the spread): the timing lets FUSED_ATTENTION ship %s%s"
+            % ("OFF" if behind_rows else "ON", (" -- behind at " + ", ".join(behind_rows)) if behind_rows else ""))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
