@@ -627,12 +627,20 @@ int snf_vit_attention_x3_f32(const float* qkv, int b, int t, int h, int dk, floa
  *       cores with fp32 accumulation (P and dS split in registers); SNF_DT_BF16: bf16 tensors, P and dS rounded to bf16 as operands,
  *       fp32 accumulation.  Neither the probabilities nor the forward's output are needed: P is rebuilt from q, k and lse, and
  *       D_i = sum_j P_ij dP_ij.  Deterministic (no atomics, one summation order).  dk == 64, 1 <= t <= SNF_VIT_BWD_MAX_T (the keys
- *       of an (image, head) in one LDS image), b <= 65535, qkv / dout / dqkv 16-byte aligned; anything else: SNF_EUNSUPPORTED. */
+ *       of an (image, head) in one LDS image), b <= 65535, qkv / dout / dqkv 16-byte aligned; anything else: SNF_EUNSUPPORTED.
+ *   snf_vit_attention_bwd_long the same backward for SNF_VIT_BWD_MAX_T < t <= SNF_VIT_BWD_LONG_MAX_T, as two launches on `stream`
+ *       (D and dQ per query tile over 256-key chunks, then dK and dV per key tile over 256-query chunks).  dwork [b, h, t] f32 is
+ *       scratch the first launch fills (D, every row) and the second reads.  Same operands, arithmetics, determinism and refusals
+ *       otherwise; t <= SNF_VIT_BWD_MAX_T is SNF_EUNSUPPORTED here (snf_vit_attention_bwd serves it). */
 #define SNF_VIT_BWD_MAX_T 256
+#define SNF_VIT_BWD_LONG_MAX_T 4096
 int snf_vit_attention_fwd_lse(const void* qkv, int dtype, int b, int t, int h, int dk, float scale, void* out, float* lse,
                               snf_stream_t stream);
 int snf_vit_attention_bwd(const void* qkv, const void* dout, const float* lse, int dtype, int b, int t, int h, int dk, float scale,
                           void* dqkv, snf_stream_t stream);
+int snf_vit_attention_bwd_long(const void* qkv, const void* dout, const float* lse, int dtype, int b, int t, int h, int dk,
+                               float scale, float* dwork /* [b, h, t] f32, scratch, fully overwritten for rows < t */,
+                               void* dqkv, snf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Tile preprocessing for the extractor, batched on the device     replaces the per-tile CPU transforms of

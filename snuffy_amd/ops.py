@@ -2354,6 +2354,38 @@ def vit_attention_bwd(qkv, dout, lse, b, t, heads, scale=None, out=None):
     return dqkv
 
 
+VIT_BWD_LONG_MAX_T = 4096    # SNF_VIT_BWD_LONG_MAX_T of include/snuffy_hip.h
+
+
+def vit_attention_bwd_long_supported(t, dk):
+    """Shapes snf_vit_attention_bwd_long serves (pure host): the token counts above `vit_attention_bwd_supported`'s."""
+    return dk == 64 and VIT_BWD_MAX_T < t <= VIT_BWD_LONG_MAX_T
+
+
+def vit_attention_bwd_long(qkv, dout, lse, b, t, heads, scale=None, out=None):
+    """`vit_attention_bwd` for VIT_BWD_MAX_T < T <= VIT_BWD_LONG_MAX_T (two launches over 256-row chunks, csrc/vit_attn_bwd_long.hip):
+    same operands, forms, determinism and `out=` contract; anything else raises (ask `vit_attention_bwd_long_supported`).  The
+    [B, h, T] fp32 workspace the two launches share is allocated here."""
+    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, "vit_attention_bwd_long")
+    dout = _req(dout, qkv.dtype, "dout", 2)
+    lse = _req(lse, torch.float32, "lse", 3)
+    if tuple(dout.shape) != (b * t, d):
+        raise ValueError("vit_attention_bwd_long: dout has shape %s, need %s" % (tuple(dout.shape), (b * t, d)))
+    if tuple(lse.shape) != (b, heads, t):
+        raise ValueError("vit_attention_bwd_long: lse has shape %s, need %s" % (tuple(lse.shape), (b, heads, t)))
+    scale = dk ** -0.5 if scale is None else scale
+    if out is None:
+        dqkv = torch.empty_like(qkv)
+    else:
+        dqkv = _req(out, qkv.dtype, "out", 2)
+        if dqkv is not out or out.shape != qkv.shape:
+            raise ValueError("vit_attention_bwd_long: out must be a contiguous tensor of qkv's shape %s" % (tuple(qkv.shape),))
+    dwork = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
+    check(_ffi.load().snf_vit_attention_bwd_long(_p(qkv), _p(dout), _p(lse), DT_F32 if qkv.dtype == torch.float32 else DT_BF16, b, t,
+                                                 heads, dk, float(scale), _p(dwork), _p(dqkv), _stream()), "snf_vit_attention_bwd_long")
+    return dqkv
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # ResNet-18 patch extractor (csrc/resnet.hip): NHWC activations, implicit-GEMM convolutions on the matrix cores
 # ----------------------------------------------------------------------------------------------------------------------

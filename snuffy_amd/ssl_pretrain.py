@@ -15,9 +15,10 @@ Counterparts in the reference (what a user of `dino_adapter/main_dino_adapter.py
 This is a TRAINING path on PyTorch-ROCm autograd.  The self-attention of every block runs on the project's own kernels
 (ViTAttentionFn: csrc/vit.hip forward with its row log-sum-exp, csrc/vit_attn_bwd.hip backward; fp32-class arithmetic for fp32
 tensors, bf16 under torch.autocast(bfloat16)), which keep qkv and one fp32 per query row instead of the [B, h, T, T] probabilities;
-that holds for dk == 64 and T <= 256 on the GPU (switch: FUSED_ATTENTION).  T = 785 (patch 8), the MAE decoder (dk = 32), CPU
-tensors and a block that needs no gradient stay on the composition of torch ops, as do every Linear, LayerNorm and GELU (library
-GEMMs); the other hand-written inference kernels of the extractor (snuffy_amd/vit.py under torch.no_grad) are not differentiable
+that holds for dk == 64 and T <= 256 on the GPU (switch: FUSED_ATTENTION).  256 < T <= 4096 (T = 785 of patch 8) has the same
+forward and the two-launch backward of csrc/vit_attn_bwd_long.hip behind a switch of its own (FUSED_ATTENTION_LONG, shipped on:
+DESIGN.md section 4 has the measurements).  The MAE decoder (dk = 32), CPU tensors and a block that needs no gradient stay on the
+composition of torch ops, as do every Linear, LayerNorm and GELU (library GEMMs); the other hand-written inference kernels of the extractor (snuffy_amd/vit.py under torch.no_grad) are not differentiable
 and are not used here.  State-dict keys are the reference's, so a
 checkpoint written here ('teacher' / 'model') loads into compute_feats exactly like the reference's (compute_feats.py:441-504).
 Several ranks: one process per GPU, gradients of the trainable (adapter + head) parameters averaged with ONE flat all-reduce per
@@ -44,8 +45,11 @@ def _patch_tokens(model, x):
 
 
 # Self-attention of a training step on the MFMA kernels (dk == 64, T <= 256, GPU, a gradient asked for).  Off: the composition of
-# torch ops everywhere, as before the kernels existed.  DESIGN.md section 4 has the measurements behind the shipped value.
+# torch ops at those T, as before the kernels existed.  DESIGN.md section 4 has the measurements behind the shipped value.
 FUSED_ATTENTION = True
+# The same for 256 < T <= 4096 (patch 8: T = 785) on the chunked forward and the two-launch backward (ops.vit_attention_bwd_long).
+# Off: such T run the composition.
+FUSED_ATTENTION_LONG = True
 
 
 class ViTAttentionFn(torch.autograd.Function):
@@ -63,15 +67,17 @@ class ViTAttentionFn(torch.autograd.Function):
     def backward(ctx, dout):
         qkv, lse = ctx.saved_tensors
         b, t, heads, scale = ctx.dims
-        return ops.vit_attention_bwd(qkv, dout.contiguous(), lse, b, t, heads, scale), None, None, None, None
+        bwd = ops.vit_attention_bwd if t <= ops.VIT_BWD_MAX_T else ops.vit_attention_bwd_long
+        return bwd(qkv, dout.contiguous(), lse, b, t, heads, scale), None, None, None, None
 
 
 def _attention(attn, x):
     b, t, d = x.shape
     h = attn.num_heads
     qkv = F.linear(x, attn.qkv.weight, attn.qkv.bias)
-    if (FUSED_ATTENTION and qkv.is_cuda and qkv.requires_grad and qkv.dtype in (torch.float32, torch.bfloat16)
-            and ops.vit_attention_bwd_supported(t, d // h)):
+    if (qkv.is_cuda and qkv.requires_grad and qkv.dtype in (torch.float32, torch.bfloat16)
+            and ((FUSED_ATTENTION and ops.vit_attention_bwd_supported(t, d // h))
+                 or (FUSED_ATTENTION_LONG and ops.vit_attention_bwd_long_supported(t, d // h)))):
         o = ViTAttentionFn.apply(qkv.view(b * t, 3 * d), b, t, h, attn.scale)
         return F.linear(o.view(b, t, d), attn.proj.weight, attn.proj.bias)
     qkv = qkv.view(b, t, 3, h, d // h).permute(2, 0, 3, 1, 4)

@@ -13,7 +13,14 @@ backward) buys adapter pre-training, against the parent's path -- the compositio
 
 One process; switch off and on alternate round by round; every leg is warmed, then timed with device events over a window of at least
 --window seconds; the spread is min / median / max of the rounds.  A row is BEHIND when the medians' ratio is under 1 and the ranges do
-not overlap, LEVEL when they do.  Peak memory: torch.cuda.max_memory_allocated over one step after a warm step."""
+not overlap, LEVEL when they do.  Peak memory: torch.cuda.max_memory_allocated over one step after a warm step.
+
+    python tools/vit_attn_train_time.py --long [--out profiles/vit_attn_long_train.txt] [--only errors|attention|dino]
+
+  the same method for 256 < T <= 4096 (csrc/vit_attn_bwd_long.hip; the switch is ssl_pretrain.FUSED_ATTENTION_LONG, FUSED_ATTENTION stays on):
+  errors      dQ / dK / dV over the table of tests/test_gpu_vit_attn_long.py
+  attention   forward + backward of _attention at ViT-S/8 global views B = 32, T = 785, h = 6, in fp32 and under bf16 autocast
+  dino        one dino_train_step of ViT-S/8 + adapters at 64 tiles (2 x 224^2 at T = 785 + 8 x 96^2 at T = 145)"""
 import argparse
 import os
 import sys
@@ -23,6 +30,7 @@ sys.path.insert(0, ROOT)
 
 TABLE = [(1, 1, 1), (2, 17, 1), (2, 32, 2), (2, 33, 1), (2, 37, 2), (3, 50, 3), (2, 197, 6), (2, 224, 2), (2, 225, 2), (2, 256, 2)]
 FWD_ONLY = [(2, 785, 2), (1, 257, 2)]
+LONG_TABLE = [(2, 257, 1), (1, 288, 2), (1, 511, 1), (2, 512, 1), (1, 513, 2), (2, 785, 2), (1, 1030, 1), (1, 2049, 1)]
 
 
 def composition(qkv, b, t, h):
@@ -32,19 +40,21 @@ def composition(qkv, b, t, h):
     return (s.softmax(-1) @ v).transpose(1, 2).reshape(b * t, d), s
 
 
-def errors(say, dev):
+def errors(say, dev, long_=False):
     import torch
     from snuffy_amd import ops
+    from tests.helpers import rel_err
 
     def rel(a, b):
-        return float((a.double() - b).abs().max() / b.abs().max().clamp_min(1e-30))
+        return rel_err(a.cpu(), b.cpu()) if long_ else float((a.double() - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
-    say("kernels against float64 autograd on the same operands (bf16 form: operands rounded to bf16 first); rel = max |a - b| / max |b|;")
+    say("kernels against float64 autograd on the same operands (bf16 form: operands rounded to bf16 first); rel = %s;"
+        % ("tests.helpers.rel_err" if long_ else "max |a - b| / max |b|"))
     say("'torch' = the composition of torch ops in the form's dtype on the device")
     say("%-6s %-14s %10s | %10s %10s %10s | %10s %10s %10s" % ("form", "(b, t, h)", "lse abs", "dQ rel", "dK rel", "dV rel", "torch dQ", "torch dK", "torch dV"))
     worst = {}
     for form in ("x3", "bf16"):
-        for b, t, h in TABLE + FWD_ONLY:
+        for b, t, h in (LONG_TABLE if long_ else TABLE + FWD_ONLY):
             g = torch.Generator().manual_seed(1000 * t + 10 * h + b)
             qkv = torch.randn(b * t, 3 * h * 64, generator=g) * 1.5
             dout = torch.randn(b * t, h * 64, generator=g)
@@ -57,10 +67,10 @@ def errors(say, dev):
             _, lse = ops.vit_attention_fwd_lse(qd, b, t, h)
             e_lse = float((lse.double() - torch.logsumexp(s.detach(), -1)).abs().max())
             worst[(form, "lse")] = max(worst.get((form, "lse"), 0.0), e_lse)
-            if (b, t, h) in FWD_ONLY:
+            if not long_ and (b, t, h) in FWD_ONLY:
                 say("%-6s %-14s %10.3g | (forward only: above the backward's T)" % (form, (b, t, h), e_lse))
                 continue
-            dqkv = ops.vit_attention_bwd(qd, dd, lse, b, t, h)
+            dqkv = (ops.vit_attention_bwd_long if long_ else ops.vit_attention_bwd)(qd, dd, lse, b, t, h)
             qc = qd.clone().requires_grad_(True)
             composition(qc, b, t, h)[0].backward(dd)
             d = h * 64
@@ -81,6 +91,7 @@ def main():
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--out")
     ap.add_argument("--only", help="'errors', 'attention', 'dino' or 'mae'")
+    ap.add_argument("--long", action="store_true", help="the shapes above 256 tokens and the switch FUSED_ATTENTION_LONG")
     args = ap.parse_args()
     import torch
     from snuffy_amd import ssl_pretrain as S
@@ -90,6 +101,7 @@ def main():
         return 1
     dev = torch.device("cuda:0")
     lines = []
+    switch = "FUSED_ATTENTION_LONG" if args.long else "FUSED_ATTENTION"
 
     def say(s):
         lines.append(s + "\n")
@@ -118,7 +130,7 @@ def main():
         t = {False: [], True: []}
         for _ in range(args.rounds):
             for on in (False, True):
-                S.FUSED_ATTENTION = on
+                setattr(S, switch, on)
                 torch.manual_seed(5)
                 t[on].append(window(fn))
         return sorted(t[False]), sorted(t[True])
@@ -126,7 +138,7 @@ def main():
     def peaks(fn):
         peak = {}
         for on in (False, True):
-            S.FUSED_ATTENTION = on
+            setattr(S, switch, on)
             fn()
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
@@ -150,14 +162,56 @@ def main():
         note = "   BEHIND" if behind else ("" if sp >= 1.0 else "   (level: ranges overlap)")
         say("%-44s %s %s %7.2fx%s%s" % (tag, fmt(off), fmt(on_), sp, ("  %8.0f -> %-7.0f" % (peak[False], peak[True])) if peak else "", note))
 
-    shipped = S.FUSED_ATTENTION
-    say("adapter pre-training, self-attention on the MFMA kernels (on) against the autograd composition (off); fp32; %s" % torch.cuda.get_device_name(0))
+    shipped = getattr(S, switch)
+    say("adapter pre-training, self-attention on the MFMA kernels (on) against the autograd composition (off); %s; %s"
+        % ("T > 256, switch FUSED_ATTENTION_LONG" if args.long else "fp32", torch.cuda.get_device_name(0)))
     if not args.only or args.only == "errors":
         say("")
-        errors(say, dev)
+        errors(say, dev, args.long)
     head = "%-44s %29s %29s %8s" % ("ms (min / median / max of %d alternating rounds)" % args.rounds, "off  min    median       max",
                                     "on   min    median       max", "speedup")
-    if not args.only or args.only == "attention":
+    if args.long and (not args.only or args.only == "attention"):
+        say("")
+        say("forward + backward of ssl_pretrain._attention (qkv Linear, attention, proj Linear), gradient to the input")
+        say(head + "  peak MB off -> on")
+        for tag, cast in (("DINO ViT-S/8 global B=32 T=785 h=6 fp32", False), ("DINO ViT-S/8 global B=32 T=785 h=6 autocast bf16", True)):
+            torch.manual_seed(1)
+            attn = vit.Attention(384, num_heads=6, qkv_bias=True).to(dev)
+            x = torch.randn(32, 785, 384, device=dev, requires_grad=True)
+            dy = torch.randn(32, 785, 384, device=dev)
+
+            def one():
+                x.grad = None
+                with torch.autocast("cuda", torch.bfloat16, enabled=cast):
+                    y = S._attention(attn, x)
+                y.backward(dy.to(y.dtype))
+
+            row(tag, one, True)
+            del attn, x, dy
+    if args.long and (not args.only or args.only == "dino"):
+        say("")
+        say("one dino_train_step: ViT-S/8 + adapters (adapter tuning), 64 tiles as 2 x 224^2 (T = 785) + 8 x 96^2 (T = 145, the short kernels "
+            "in both legs) crops, out_dim 65536")
+        say(head + "  peak MB off -> on")
+        torch.manual_seed(2)
+
+        def net8():
+            bb = vit.vit_small(8, adapter_ffn_layernorm_option="none", adapter_ffn_init_option="lora", adapter_ffn_scalar="0.1",
+                               adapter_ffn_num=64, adapter_d_model=384)
+            return S.MultiCropWrapper(bb, S.DINOHead(384, 65536)).to(dev).train()
+
+        student, teacher = net8(), net8()
+        teacher.load_state_dict(student.state_dict())
+        for p in teacher.parameters():
+            p.requires_grad = False
+        S.freeze_for_adapter_tuning(student)
+        loss_mod = S.DINOLoss(65536, 10, 0.04, 0.04, 0, 10).to(dev)
+        opt = torch.optim.AdamW(S.get_params_groups(student), lr=1e-5)
+        crops = [torch.randn(64, 3, 224, 224, device=dev) for _ in range(2)] + [torch.randn(64, 3, 96, 96, device=dev) for _ in range(8)]
+        row("dino_train_step ViT-S/8 64 tiles", lambda: S.dino_train_step(student, teacher, loss_mod, crops, opt, 1, clip_grad=3.0), True)
+        del student, teacher, loss_mod, opt, crops
+        torch.cuda.empty_cache()
+    if not args.long and (not args.only or args.only == "attention"):
         say("")
         say("forward + backward of ssl_pretrain._attention (qkv Linear, attention, proj Linear), gradient to the input")
         say(head)
@@ -174,7 +228,7 @@ def main():
 
             row(tag, one, False)
             del attn, x, dy
-    if not args.only or args.only == "dino":
+    if not args.long and (not args.only or args.only == "dino"):
         say("")
         say("one dino_train_step: ViT-S/16 + adapters (adapter tuning), 64 tiles as 2 x 224^2 + 8 x 96^2 crops, out_dim 65536; peak MB off -> on")
         say(head + "  peak MB off -> on")
@@ -196,7 +250,7 @@ def main():
         row("dino_train_step 64 tiles", lambda: S.dino_train_step(student, teacher, loss_mod, crops, opt, 1, clip_grad=3.0), True)
         del student, teacher, loss_mod, opt, crops
         torch.cuda.empty_cache()
-    if not args.only or args.only == "mae":
+    if not args.long and (not args.only or args.only == "mae"):
         say("")
         say("one mae_train_step: ViT-B/16 MAE-adapter model (decoder 512 x 8, 16 heads: dk = 32 stays on the composition), batch 64, mask 0.75")
         say(head + "  peak MB off -> on")
@@ -209,11 +263,11 @@ def main():
         imgs = torch.randn(64, 3, 224, 224, device=dev)
         row("mae_train_step batch 64", lambda: S.mae_train_step(model, imgs, opt), True)
         del model, opt, imgs
-    S.FUSED_ATTENTION = shipped
+    setattr(S, switch, shipped)
     if not args.only:
         say("")
-        say("ship rule (on only if no step row is behind outside the spread): the timing lets FUSED_ATTENTION ship %s%s"
-            % ("OFF" if behind_rows else "ON", (" -- behind at " + ", ".join(behind_rows)) if behind_rows else ""))
+        say("ship rule (on only if no step row is behind outside the spread): the timing lets %s ship %s%s"
+            % (switch, "OFF" if behind_rows else "ON", (" -- behind at " + ", ".join(behind_rows)) if behind_rows else ""))
     return 0
 
 
