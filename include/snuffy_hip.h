@@ -641,6 +641,20 @@ int snf_vit_attention_bwd(const void* qkv, const void* dout, const float* lse, i
 int snf_vit_attention_bwd_long(const void* qkv, const void* dout, const float* lse, int dtype, int b, int t, int h, int dk,
                                float scale, float* dwork /* [b, h, t] f32, scratch, fully overwritten for rows < t */,
                                void* dqkv, snf_stream_t stream);
+/* The same training pair at head width 32 (the MAE decoder of adapter pre-training: 512 wide, 16 heads, t = 197), csrc/vit_attn_dk32.hip.
+ *   snf_vit_attention_dk32_fwd_lse  qkv [b*t, 3*h*32] (q | k | v) -> out [b*t, h*32] and lse [b, h, t] f32 (natural log, required).
+ *       One workgroup per (image, head), online softmax over 32-key blocks.  SNF_DT_BF16: bf16 in / out; SNF_DT_F32: fp32 in / out
+ *       in the fp32-class arithmetic (hi hi + hi lo + lo hi on the bf16 matrix cores, fp32 accumulation).
+ *   snf_vit_attention_dk32_bwd      qkv as given to the forward, dout [b*t, h*32], lse from the forward -> dqkv [b*t, 3*h*32] laid out
+ *       as qkv (dQ | dK | dV), every element written.  The arithmetics, the rebuilt P, D_i = sum_j P_ij dP_ij and the determinism
+ *       (no atomics, one summation order) are those of snf_vit_attention_bwd; t == 1 is an exact copy (dQ = dK = 0, dV = dout).
+ *   Both: dk == 32 (the argument is kept so the call shape matches the 64-wide pair), 1 <= t <= SNF_VIT_DK32_MAX_T, b <= 65535,
+ *       qkv / out / dout / dqkv 16-byte aligned; anything else: SNF_EUNSUPPORTED. */
+#define SNF_VIT_DK32_MAX_T 256
+int snf_vit_attention_dk32_fwd_lse(const void* qkv, int dtype, int b, int t, int h, int dk, float scale,
+                                   void* out, float* lse, snf_stream_t stream);
+int snf_vit_attention_dk32_bwd(const void* qkv, const void* dout, const float* lse, int dtype, int b, int t,
+                               int h, int dk, float scale, void* dqkv, snf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Tile preprocessing for the extractor, batched on the device     replaces the per-tile CPU transforms of

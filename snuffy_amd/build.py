@@ -24,6 +24,7 @@ EXTRA_FLAGS = {"sparse_attn_mfma.hip": ["-fno-honor-nans", "-fno-slp-vectorize"]
                "sparse_attn_mfma_varlen.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
                "sparse_attn_mfma_varlen_dk64.hip": ["-fno-honor-nans", "-fno-slp-vectorize"], "vit.hip": ["-fno-honor-nans"],
                "vit_attn_bwd.hip": ["-fno-honor-nans"], "vit_attn_bwd_long.hip": ["-fno-honor-nans"],
+               "vit_attn_dk32.hip": ["-fno-honor-nans"],
                "sparse_attn_mfma_varlen_chunks.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
                "sparse_attn_mfma_varlen_dk192.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
                "sparse_attn_mfma_varlen_chunks_dk64.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],

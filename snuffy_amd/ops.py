@@ -2386,6 +2386,54 @@ def vit_attention_bwd_long(qkv, dout, lse, b, t, heads, scale=None, out=None):
     return dqkv
 
 
+VIT_DK32_MAX_T = 256     # SNF_VIT_DK32_MAX_T of include/snuffy_hip.h
+
+
+def vit_attention_dk32_supported(t, dk):
+    """Shapes the 32-wide training pair serves (pure host; csrc/vit_attn_dk32.hip: the MAE decoder's heads)."""
+    return dk == 32 and 1 <= t <= VIT_DK32_MAX_T
+
+
+def vit_attention_dk32_fwd_lse(qkv, b, t, heads, scale=None, arithmetic=None):
+    """`vit_attention_fwd_lse` at head width 32: (out [B*T, D], lse [B, h, T] f32, natural log).  fp32 qkv -> fp32-class arithmetic
+    ("x3"), bf16 qkv -> bf16 ("bf16"); `arithmetic`, when given, must name the form of qkv's dtype.  dk == 32 and
+    1 <= T <= VIT_DK32_MAX_T, anything else raises (ask `vit_attention_dk32_supported`)."""
+    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, "vit_attention_dk32_fwd_lse")
+    form = "x3" if qkv.dtype == torch.float32 else "bf16"
+    if arithmetic is not None and arithmetic != form:
+        raise ValueError("vit_attention_dk32_fwd_lse: arithmetic=%r needs %s qkv, got %s"
+                         % (arithmetic, "float32" if arithmetic == "x3" else "bfloat16", qkv.dtype))
+    scale = dk ** -0.5 if scale is None else scale
+    out = torch.empty(b * t, d, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
+    check(_ffi.load().snf_vit_attention_dk32_fwd_lse(_p(qkv), DT_F32 if form == "x3" else DT_BF16, b, t, heads, dk, float(scale),
+                                                     _p(out), _p(lse), _stream()), "snf_vit_attention_dk32_fwd_lse")
+    return out, lse
+
+
+def vit_attention_dk32_bwd(qkv, dout, lse, b, t, heads, scale=None, out=None):
+    """`vit_attention_bwd` at head width 32: dqkv [B*T, 3*D] (dQ | dK | dV) from the qkv given to `vit_attention_dk32_fwd_lse`, its
+    lse and dout [B*T, D].  Same forms, determinism and `out=` contract; dk == 32 and 1 <= T <= VIT_DK32_MAX_T, anything else
+    raises."""
+    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, "vit_attention_dk32_bwd")
+    dout = _req(dout, qkv.dtype, "dout", 2)
+    lse = _req(lse, torch.float32, "lse", 3)
+    if tuple(dout.shape) != (b * t, d):
+        raise ValueError("vit_attention_dk32_bwd: dout has shape %s, need %s" % (tuple(dout.shape), (b * t, d)))
+    if tuple(lse.shape) != (b, heads, t):
+        raise ValueError("vit_attention_dk32_bwd: lse has shape %s, need %s" % (tuple(lse.shape), (b, heads, t)))
+    scale = dk ** -0.5 if scale is None else scale
+    if out is None:
+        dqkv = torch.empty_like(qkv)
+    else:
+        dqkv = _req(out, qkv.dtype, "out", 2)
+        if dqkv is not out or out.shape != qkv.shape:
+            raise ValueError("vit_attention_dk32_bwd: out must be a contiguous tensor of qkv's shape %s" % (tuple(qkv.shape),))
+    check(_ffi.load().snf_vit_attention_dk32_bwd(_p(qkv), _p(dout), _p(lse), DT_F32 if qkv.dtype == torch.float32 else DT_BF16, b, t,
+                                                 heads, dk, float(scale), _p(dqkv), _stream()), "snf_vit_attention_dk32_bwd")
+    return dqkv
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # ResNet-18 patch extractor (csrc/resnet.hip): NHWC activations, implicit-GEMM convolutions on the matrix cores
 # ----------------------------------------------------------------------------------------------------------------------

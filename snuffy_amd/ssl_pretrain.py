@@ -17,7 +17,9 @@ This is a TRAINING path on PyTorch-ROCm autograd.  The self-attention of every b
 tensors, bf16 under torch.autocast(bfloat16)), which keep qkv and one fp32 per query row instead of the [B, h, T, T] probabilities;
 that holds for dk == 64 and T <= 256 on the GPU (switch: FUSED_ATTENTION).  256 < T <= 4096 (T = 785 of patch 8) has the same
 forward and the two-launch backward of csrc/vit_attn_bwd_long.hip behind a switch of its own (FUSED_ATTENTION_LONG, shipped on:
-DESIGN.md section 4 has the measurements).  The MAE decoder (dk = 32), CPU tensors and a block that needs no gradient stay on the
+DESIGN.md section 4 has the measurements).  The MAE decoder (512 wide, 16 heads: dk = 32, T = 197) runs the 32-wide pair of
+csrc/vit_attn_dk32.hip (dk == 32, T <= 256; switch: FUSED_ATTENTION_DK32).  Other head widths (dk = 16, 96, ...), dk = 32 above
+256 tokens, CPU tensors and a block that needs no gradient stay on the
 composition of torch ops, as do every Linear, LayerNorm and GELU (library GEMMs); the other hand-written inference kernels of the extractor (snuffy_amd/vit.py under torch.no_grad) are not differentiable
 and are not used here.  State-dict keys are the reference's, so a
 checkpoint written here ('teacher' / 'model') loads into compute_feats exactly like the reference's (compute_feats.py:441-504).
@@ -50,6 +52,8 @@ FUSED_ATTENTION = True
 # The same for 256 < T <= 4096 (patch 8: T = 785) on the chunked forward and the two-launch backward (ops.vit_attention_bwd_long).
 # Off: such T run the composition.
 FUSED_ATTENTION_LONG = True
+# Heads 32 wide at T <= 256 (the MAE decoder: 16 heads over 512, T = 197) on the pair of csrc/vit_attn_dk32.hip.  Off: the composition.
+FUSED_ATTENTION_DK32 = True
 
 
 class ViTAttentionFn(torch.autograd.Function):
@@ -57,7 +61,8 @@ class ViTAttentionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, b, t, heads, scale):
-        out, lse = ops.vit_attention_fwd_lse(qkv, b, t, heads, scale)
+        fwd = ops.vit_attention_dk32_fwd_lse if qkv.shape[1] // 3 // heads == 32 else ops.vit_attention_fwd_lse
+        out, lse = fwd(qkv, b, t, heads, scale)
         ctx.save_for_backward(qkv, lse)
         ctx.dims = (b, t, heads, scale)
         return out
@@ -67,7 +72,10 @@ class ViTAttentionFn(torch.autograd.Function):
     def backward(ctx, dout):
         qkv, lse = ctx.saved_tensors
         b, t, heads, scale = ctx.dims
-        bwd = ops.vit_attention_bwd if t <= ops.VIT_BWD_MAX_T else ops.vit_attention_bwd_long
+        if qkv.shape[1] // 3 // heads == 32:
+            bwd = ops.vit_attention_dk32_bwd
+        else:
+            bwd = ops.vit_attention_bwd if t <= ops.VIT_BWD_MAX_T else ops.vit_attention_bwd_long
         return bwd(qkv, dout.contiguous(), lse, b, t, heads, scale), None, None, None, None
 
 
@@ -77,7 +85,8 @@ def _attention(attn, x):
     qkv = F.linear(x, attn.qkv.weight, attn.qkv.bias)
     if (qkv.is_cuda and qkv.requires_grad and qkv.dtype in (torch.float32, torch.bfloat16)
             and ((FUSED_ATTENTION and ops.vit_attention_bwd_supported(t, d // h))
-                 or (FUSED_ATTENTION_LONG and ops.vit_attention_bwd_long_supported(t, d // h)))):
+                 or (FUSED_ATTENTION_LONG and ops.vit_attention_bwd_long_supported(t, d // h))
+                 or (FUSED_ATTENTION_DK32 and ops.vit_attention_dk32_supported(t, d // h)))):
         o = ViTAttentionFn.apply(qkv.view(b * t, 3 * d), b, t, h, attn.scale)
         return F.linear(o.view(b, t, d), attn.proj.weight, attn.proj.bias)
     qkv = qkv.view(b, t, 3, h, d // h).permute(2, 0, 3, 1, 4)
