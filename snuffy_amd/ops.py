@@ -2313,21 +2313,49 @@ def _vit_train_dims(qkv, b, t, heads, what):
     return qkv, d3 // 3, d3 // 3 // heads
 
 
+def _vit_fwd_lse(entry, what, qkv, b, t, heads, scale, arithmetic):
+    """The shared part of the `*_fwd_lse` wrappers: `entry` is the C entry point's name, `what` the public function the errors name."""
+    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, what)
+    form = "x3" if qkv.dtype == torch.float32 else "bf16"
+    if arithmetic is not None and arithmetic != form:
+        raise ValueError("%s: arithmetic=%r needs %s qkv, got %s"
+                         % (what, arithmetic, "float32" if arithmetic == "x3" else "bfloat16", qkv.dtype))
+    scale = dk ** -0.5 if scale is None else scale
+    out = torch.empty(b * t, d, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
+    check(getattr(_ffi.load(), entry)(_p(qkv), DT_F32 if form == "x3" else DT_BF16, b, t, heads, dk, float(scale), _p(out), _p(lse),
+                                      _stream()), entry)
+    return out, lse
+
+
+def _vit_bwd(entry, what, qkv, dout, lse, b, t, heads, scale, out, workspace=False):
+    """The shared part of the backward wrappers (names as in `_vit_fwd_lse`).  `workspace`: the entry point takes a [B, h, T] fp32
+    scratch tensor before dqkv; it is allocated here."""
+    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, what)
+    dout = _req(dout, qkv.dtype, "dout", 2)
+    lse = _req(lse, torch.float32, "lse", 3)
+    if tuple(dout.shape) != (b * t, d):
+        raise ValueError("%s: dout has shape %s, need %s" % (what, tuple(dout.shape), (b * t, d)))
+    if tuple(lse.shape) != (b, heads, t):
+        raise ValueError("%s: lse has shape %s, need %s" % (what, tuple(lse.shape), (b, heads, t)))
+    scale = dk ** -0.5 if scale is None else scale
+    if out is None:
+        dqkv = torch.empty_like(qkv)
+    else:
+        dqkv = _req(out, qkv.dtype, "out", 2)
+        if dqkv is not out or out.shape != qkv.shape:
+            raise ValueError("%s: out must be a contiguous tensor of qkv's shape %s" % (what, tuple(qkv.shape)))
+    dwork = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device) if workspace else None
+    check(getattr(_ffi.load(), entry)(_p(qkv), _p(dout), _p(lse), DT_F32 if qkv.dtype == torch.float32 else DT_BF16, b, t, heads, dk,
+                                      float(scale), *([_p(dwork)] if workspace else []), _p(dqkv), _stream()), entry)
+    return dqkv
+
+
 def vit_attention_fwd_lse(qkv, b, t, heads, scale=None, arithmetic=None):
     """The MFMA self-attention forward of `vit_attention` with the row statistic a backward needs: (out [B*T, D], lse [B, h, T] f32,
     natural log).  fp32 qkv -> fp32-class arithmetic ("x3"), bf16 qkv -> bf16 ("bf16"); `arithmetic`, when given, must name the
     form of qkv's dtype.  `out` is bit for bit what `vit_attention` returns in that form.  dk == 64, T <= VIT_MFMA_MAX_T."""
-    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, "vit_attention_fwd_lse")
-    form = "x3" if qkv.dtype == torch.float32 else "bf16"
-    if arithmetic is not None and arithmetic != form:
-        raise ValueError("vit_attention_fwd_lse: arithmetic=%r needs %s qkv, got %s"
-                         % (arithmetic, "float32" if arithmetic == "x3" else "bfloat16", qkv.dtype))
-    scale = dk ** -0.5 if scale is None else scale
-    out = torch.empty(b * t, d, dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
-    check(_ffi.load().snf_vit_attention_fwd_lse(_p(qkv), DT_F32 if form == "x3" else DT_BF16, b, t, heads, dk, float(scale), _p(out),
-                                                _p(lse), _stream()), "snf_vit_attention_fwd_lse")
-    return out, lse
+    return _vit_fwd_lse("snf_vit_attention_fwd_lse", "vit_attention_fwd_lse", qkv, b, t, heads, scale, arithmetic)
 
 
 def vit_attention_bwd(qkv, dout, lse, b, t, heads, scale=None, out=None):
@@ -2335,23 +2363,7 @@ def vit_attention_bwd(qkv, dout, lse, b, t, heads, scale=None, out=None):
     The form follows qkv's dtype (fp32: fp32 class; bf16: bf16).  Deterministic; dk == 64 and 1 <= T <= VIT_BWD_MAX_T, anything
     else raises (ask `vit_attention_bwd_supported`).  `out`: a contiguous tensor of qkv's shape and dtype to write into (every element
     is written; default: a new one)."""
-    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, "vit_attention_bwd")
-    dout = _req(dout, qkv.dtype, "dout", 2)
-    lse = _req(lse, torch.float32, "lse", 3)
-    if tuple(dout.shape) != (b * t, d):
-        raise ValueError("vit_attention_bwd: dout has shape %s, need %s" % (tuple(dout.shape), (b * t, d)))
-    if tuple(lse.shape) != (b, heads, t):
-        raise ValueError("vit_attention_bwd: lse has shape %s, need %s" % (tuple(lse.shape), (b, heads, t)))
-    scale = dk ** -0.5 if scale is None else scale
-    if out is None:
-        dqkv = torch.empty_like(qkv)
-    else:
-        dqkv = _req(out, qkv.dtype, "out", 2)
-        if dqkv is not out or out.shape != qkv.shape:
-            raise ValueError("vit_attention_bwd: out must be a contiguous tensor of qkv's shape %s" % (tuple(qkv.shape),))
-    check(_ffi.load().snf_vit_attention_bwd(_p(qkv), _p(dout), _p(lse), DT_F32 if qkv.dtype == torch.float32 else DT_BF16, b, t, heads,
-                                            dk, float(scale), _p(dqkv), _stream()), "snf_vit_attention_bwd")
-    return dqkv
+    return _vit_bwd("snf_vit_attention_bwd", "vit_attention_bwd", qkv, dout, lse, b, t, heads, scale, out)
 
 
 VIT_BWD_LONG_MAX_T = 4096    # SNF_VIT_BWD_LONG_MAX_T of include/snuffy_hip.h
@@ -2366,24 +2378,7 @@ def vit_attention_bwd_long(qkv, dout, lse, b, t, heads, scale=None, out=None):
     """`vit_attention_bwd` for VIT_BWD_MAX_T < T <= VIT_BWD_LONG_MAX_T (two launches over 256-row chunks, csrc/vit_attn_bwd_long.hip):
     same operands, forms, determinism and `out=` contract; anything else raises (ask `vit_attention_bwd_long_supported`).  The
     [B, h, T] fp32 workspace the two launches share is allocated here."""
-    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, "vit_attention_bwd_long")
-    dout = _req(dout, qkv.dtype, "dout", 2)
-    lse = _req(lse, torch.float32, "lse", 3)
-    if tuple(dout.shape) != (b * t, d):
-        raise ValueError("vit_attention_bwd_long: dout has shape %s, need %s" % (tuple(dout.shape), (b * t, d)))
-    if tuple(lse.shape) != (b, heads, t):
-        raise ValueError("vit_attention_bwd_long: lse has shape %s, need %s" % (tuple(lse.shape), (b, heads, t)))
-    scale = dk ** -0.5 if scale is None else scale
-    if out is None:
-        dqkv = torch.empty_like(qkv)
-    else:
-        dqkv = _req(out, qkv.dtype, "out", 2)
-        if dqkv is not out or out.shape != qkv.shape:
-            raise ValueError("vit_attention_bwd_long: out must be a contiguous tensor of qkv's shape %s" % (tuple(qkv.shape),))
-    dwork = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
-    check(_ffi.load().snf_vit_attention_bwd_long(_p(qkv), _p(dout), _p(lse), DT_F32 if qkv.dtype == torch.float32 else DT_BF16, b, t,
-                                                 heads, dk, float(scale), _p(dwork), _p(dqkv), _stream()), "snf_vit_attention_bwd_long")
-    return dqkv
+    return _vit_bwd("snf_vit_attention_bwd_long", "vit_attention_bwd_long", qkv, dout, lse, b, t, heads, scale, out, workspace=True)
 
 
 VIT_DK32_MAX_T = 256     # SNF_VIT_DK32_MAX_T of include/snuffy_hip.h
@@ -2398,40 +2393,14 @@ def vit_attention_dk32_fwd_lse(qkv, b, t, heads, scale=None, arithmetic=None):
     """`vit_attention_fwd_lse` at head width 32: (out [B*T, D], lse [B, h, T] f32, natural log).  fp32 qkv -> fp32-class arithmetic
     ("x3"), bf16 qkv -> bf16 ("bf16"); `arithmetic`, when given, must name the form of qkv's dtype.  dk == 32 and
     1 <= T <= VIT_DK32_MAX_T, anything else raises (ask `vit_attention_dk32_supported`)."""
-    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, "vit_attention_dk32_fwd_lse")
-    form = "x3" if qkv.dtype == torch.float32 else "bf16"
-    if arithmetic is not None and arithmetic != form:
-        raise ValueError("vit_attention_dk32_fwd_lse: arithmetic=%r needs %s qkv, got %s"
-                         % (arithmetic, "float32" if arithmetic == "x3" else "bfloat16", qkv.dtype))
-    scale = dk ** -0.5 if scale is None else scale
-    out = torch.empty(b * t, d, dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
-    check(_ffi.load().snf_vit_attention_dk32_fwd_lse(_p(qkv), DT_F32 if form == "x3" else DT_BF16, b, t, heads, dk, float(scale),
-                                                     _p(out), _p(lse), _stream()), "snf_vit_attention_dk32_fwd_lse")
-    return out, lse
+    return _vit_fwd_lse("snf_vit_attention_dk32_fwd_lse", "vit_attention_dk32_fwd_lse", qkv, b, t, heads, scale, arithmetic)
 
 
 def vit_attention_dk32_bwd(qkv, dout, lse, b, t, heads, scale=None, out=None):
     """`vit_attention_bwd` at head width 32: dqkv [B*T, 3*D] (dQ | dK | dV) from the qkv given to `vit_attention_dk32_fwd_lse`, its
     lse and dout [B*T, D].  Same forms, determinism and `out=` contract; dk == 32 and 1 <= T <= VIT_DK32_MAX_T, anything else
     raises."""
-    qkv, d, dk = _vit_train_dims(qkv, b, t, heads, "vit_attention_dk32_bwd")
-    dout = _req(dout, qkv.dtype, "dout", 2)
-    lse = _req(lse, torch.float32, "lse", 3)
-    if tuple(dout.shape) != (b * t, d):
-        raise ValueError("vit_attention_dk32_bwd: dout has shape %s, need %s" % (tuple(dout.shape), (b * t, d)))
-    if tuple(lse.shape) != (b, heads, t):
-        raise ValueError("vit_attention_dk32_bwd: lse has shape %s, need %s" % (tuple(lse.shape), (b, heads, t)))
-    scale = dk ** -0.5 if scale is None else scale
-    if out is None:
-        dqkv = torch.empty_like(qkv)
-    else:
-        dqkv = _req(out, qkv.dtype, "out", 2)
-        if dqkv is not out or out.shape != qkv.shape:
-            raise ValueError("vit_attention_dk32_bwd: out must be a contiguous tensor of qkv's shape %s" % (tuple(qkv.shape),))
-    check(_ffi.load().snf_vit_attention_dk32_bwd(_p(qkv), _p(dout), _p(lse), DT_F32 if qkv.dtype == torch.float32 else DT_BF16, b, t,
-                                                 heads, dk, float(scale), _p(dqkv), _stream()), "snf_vit_attention_dk32_bwd")
-    return dqkv
+    return _vit_bwd("snf_vit_attention_dk32_bwd", "vit_attention_dk32_bwd", qkv, dout, lse, b, t, heads, scale, out)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
