@@ -3,6 +3,7 @@
 PyTorch is plumbing here: it owns device memory and the HIP stream; every kernel is ours.  All functions require CUDA
 (ROCm) tensors and raise otherwise -- there is no CPU path in the product.
 """
+import collections
 import ctypes
 import math
 
@@ -2287,19 +2288,56 @@ def vit_attention(qkv, b, t, heads, scale=None, need_attn=False, arithmetic="exa
     return out, None
 
 
-VIT_MFMA_MAX_T = 4096    # SNF_VIT_MFMA_MAX_T of include/snuffy_hip.h
+# The forms of the differentiable self-attention (ssl_pretrain.ViTAttentionFn), one record each: head width, the token counts served
+# (inclusive), the names of the forward and backward wrappers below and of their C entry points, and whether the backward takes the
+# [B, h, T] fp32 workspace.  The bounds are written here and nowhere else in Python: t_max mirrors SNF_VIT_BWD_MAX_T,
+# SNF_VIT_BWD_LONG_MAX_T and SNF_VIT_DK32_MAX_T of include/snuffy_hip.h (tests/test_vit_attn_forms_host.py compares them).  A further
+# form is one more record, its two wrappers and its kernels.
+ViTTrainForm = collections.namedtuple("ViTTrainForm", "name dk t_min t_max fwd bwd c_fwd c_bwd workspace")
+VIT_TRAIN_FORMS = (
+    # the keys of an (image, head) in one LDS image (csrc/vit_attn_bwd.hip)
+    ViTTrainForm("short", 64, 1, 256, "vit_attention_fwd_lse", "vit_attention_bwd", "snf_vit_attention_fwd_lse", "snf_vit_attention_bwd", False),
+    # two launches over 256-row chunks (csrc/vit_attn_bwd_long.hip); the forward is the short form's, which chunks its keys above 256
+    ViTTrainForm("long", 64, 257, 4096, "vit_attention_fwd_lse", "vit_attention_bwd_long", "snf_vit_attention_fwd_lse",
+                 "snf_vit_attention_bwd_long", True),
+    # the MAE decoder's heads (csrc/vit_attn_dk32.hip)
+    ViTTrainForm("dk32", 32, 1, 256, "vit_attention_dk32_fwd_lse", "vit_attention_dk32_bwd", "snf_vit_attention_dk32_fwd_lse",
+                 "snf_vit_attention_dk32_bwd", False),
+)
+_VIT_SHORT, _VIT_LONG, _VIT_DK32 = VIT_TRAIN_FORMS
+VIT_BWD_MAX_T, VIT_BWD_LONG_MAX_T, VIT_DK32_MAX_T = _VIT_SHORT.t_max, _VIT_LONG.t_max, _VIT_DK32.t_max
+VIT_MFMA_MAX_T = _VIT_LONG.t_max     # SNF_VIT_MFMA_MAX_T: the 64-wide forward, with or without lse, ends where its longest backward does
+
+
+def _vit_form_serves(form, t, dk):
+    return dk == form.dk and form.t_min <= t <= form.t_max
+
+
+def vit_attention_train_form(t, dk):
+    """The record of VIT_TRAIN_FORMS that trains T tokens at head width dk (pure host), or None: the autograd composition."""
+    for form in VIT_TRAIN_FORMS:
+        if _vit_form_serves(form, t, dk):
+            return form
+    return None
 
 
 def vit_mfma_attention_supported(t, dk):
     return dk == 64 and t <= VIT_MFMA_MAX_T
 
 
-VIT_BWD_MAX_T = 256      # SNF_VIT_BWD_MAX_T of include/snuffy_hip.h: the keys of an (image, head) in one LDS image
-
-
 def vit_attention_bwd_supported(t, dk):
     """Shapes snf_vit_attention_bwd serves (pure host): everything else trains on the autograd composition."""
-    return dk == 64 and 1 <= t <= VIT_BWD_MAX_T
+    return _vit_form_serves(_VIT_SHORT, t, dk)
+
+
+def vit_attention_bwd_long_supported(t, dk):
+    """Shapes snf_vit_attention_bwd_long serves (pure host): the token counts above `vit_attention_bwd_supported`'s."""
+    return _vit_form_serves(_VIT_LONG, t, dk)
+
+
+def vit_attention_dk32_supported(t, dk):
+    """Shapes the 32-wide training pair serves (pure host; csrc/vit_attn_dk32.hip: the MAE decoder's heads)."""
+    return _vit_form_serves(_VIT_DK32, t, dk)
 
 
 def _vit_train_dims(qkv, b, t, heads, what):
@@ -2313,8 +2351,10 @@ def _vit_train_dims(qkv, b, t, heads, what):
     return qkv, d3 // 3, d3 // 3 // heads
 
 
-def _vit_fwd_lse(entry, what, qkv, b, t, heads, scale, arithmetic):
-    """The shared part of the `*_fwd_lse` wrappers: `entry` is the C entry point's name, `what` the public function the errors name."""
+def _vit_fwd_lse(train_form, qkv, b, t, heads, scale, arithmetic):
+    """The shared part of the `*_fwd_lse` wrappers, over a record of VIT_TRAIN_FORMS: its C entry point, and its wrapper's name in the
+    errors."""
+    entry, what = train_form.c_fwd, train_form.fwd
     qkv, d, dk = _vit_train_dims(qkv, b, t, heads, what)
     form = "x3" if qkv.dtype == torch.float32 else "bf16"
     if arithmetic is not None and arithmetic != form:
@@ -2328,9 +2368,10 @@ def _vit_fwd_lse(entry, what, qkv, b, t, heads, scale, arithmetic):
     return out, lse
 
 
-def _vit_bwd(entry, what, qkv, dout, lse, b, t, heads, scale, out, workspace=False):
-    """The shared part of the backward wrappers (names as in `_vit_fwd_lse`).  `workspace`: the entry point takes a [B, h, T] fp32
-    scratch tensor before dqkv; it is allocated here."""
+def _vit_bwd(train_form, qkv, dout, lse, b, t, heads, scale, out):
+    """The shared part of the backward wrappers (as `_vit_fwd_lse`).  A form with `workspace` has an entry point that takes a
+    [B, h, T] fp32 scratch tensor before dqkv; it is allocated here."""
+    entry, what, workspace = train_form.c_bwd, train_form.bwd, train_form.workspace
     qkv, d, dk = _vit_train_dims(qkv, b, t, heads, what)
     dout = _req(dout, qkv.dtype, "dout", 2)
     lse = _req(lse, torch.float32, "lse", 3)
@@ -2355,7 +2396,7 @@ def vit_attention_fwd_lse(qkv, b, t, heads, scale=None, arithmetic=None):
     """The MFMA self-attention forward of `vit_attention` with the row statistic a backward needs: (out [B*T, D], lse [B, h, T] f32,
     natural log).  fp32 qkv -> fp32-class arithmetic ("x3"), bf16 qkv -> bf16 ("bf16"); `arithmetic`, when given, must name the
     form of qkv's dtype.  `out` is bit for bit what `vit_attention` returns in that form.  dk == 64, T <= VIT_MFMA_MAX_T."""
-    return _vit_fwd_lse("snf_vit_attention_fwd_lse", "vit_attention_fwd_lse", qkv, b, t, heads, scale, arithmetic)
+    return _vit_fwd_lse(_VIT_SHORT, qkv, b, t, heads, scale, arithmetic)
 
 
 def vit_attention_bwd(qkv, dout, lse, b, t, heads, scale=None, out=None):
@@ -2363,44 +2404,28 @@ def vit_attention_bwd(qkv, dout, lse, b, t, heads, scale=None, out=None):
     The form follows qkv's dtype (fp32: fp32 class; bf16: bf16).  Deterministic; dk == 64 and 1 <= T <= VIT_BWD_MAX_T, anything
     else raises (ask `vit_attention_bwd_supported`).  `out`: a contiguous tensor of qkv's shape and dtype to write into (every element
     is written; default: a new one)."""
-    return _vit_bwd("snf_vit_attention_bwd", "vit_attention_bwd", qkv, dout, lse, b, t, heads, scale, out)
-
-
-VIT_BWD_LONG_MAX_T = 4096    # SNF_VIT_BWD_LONG_MAX_T of include/snuffy_hip.h
-
-
-def vit_attention_bwd_long_supported(t, dk):
-    """Shapes snf_vit_attention_bwd_long serves (pure host): the token counts above `vit_attention_bwd_supported`'s."""
-    return dk == 64 and VIT_BWD_MAX_T < t <= VIT_BWD_LONG_MAX_T
+    return _vit_bwd(_VIT_SHORT, qkv, dout, lse, b, t, heads, scale, out)
 
 
 def vit_attention_bwd_long(qkv, dout, lse, b, t, heads, scale=None, out=None):
     """`vit_attention_bwd` for VIT_BWD_MAX_T < T <= VIT_BWD_LONG_MAX_T (two launches over 256-row chunks, csrc/vit_attn_bwd_long.hip):
     same operands, forms, determinism and `out=` contract; anything else raises (ask `vit_attention_bwd_long_supported`).  The
     [B, h, T] fp32 workspace the two launches share is allocated here."""
-    return _vit_bwd("snf_vit_attention_bwd_long", "vit_attention_bwd_long", qkv, dout, lse, b, t, heads, scale, out, workspace=True)
-
-
-VIT_DK32_MAX_T = 256     # SNF_VIT_DK32_MAX_T of include/snuffy_hip.h
-
-
-def vit_attention_dk32_supported(t, dk):
-    """Shapes the 32-wide training pair serves (pure host; csrc/vit_attn_dk32.hip: the MAE decoder's heads)."""
-    return dk == 32 and 1 <= t <= VIT_DK32_MAX_T
+    return _vit_bwd(_VIT_LONG, qkv, dout, lse, b, t, heads, scale, out)
 
 
 def vit_attention_dk32_fwd_lse(qkv, b, t, heads, scale=None, arithmetic=None):
     """`vit_attention_fwd_lse` at head width 32: (out [B*T, D], lse [B, h, T] f32, natural log).  fp32 qkv -> fp32-class arithmetic
     ("x3"), bf16 qkv -> bf16 ("bf16"); `arithmetic`, when given, must name the form of qkv's dtype.  dk == 32 and
     1 <= T <= VIT_DK32_MAX_T, anything else raises (ask `vit_attention_dk32_supported`)."""
-    return _vit_fwd_lse("snf_vit_attention_dk32_fwd_lse", "vit_attention_dk32_fwd_lse", qkv, b, t, heads, scale, arithmetic)
+    return _vit_fwd_lse(_VIT_DK32, qkv, b, t, heads, scale, arithmetic)
 
 
 def vit_attention_dk32_bwd(qkv, dout, lse, b, t, heads, scale=None, out=None):
     """`vit_attention_bwd` at head width 32: dqkv [B*T, 3*D] (dQ | dK | dV) from the qkv given to `vit_attention_dk32_fwd_lse`, its
     lse and dout [B*T, D].  Same forms, determinism and `out=` contract; dk == 32 and 1 <= T <= VIT_DK32_MAX_T, anything else
     raises."""
-    return _vit_bwd("snf_vit_attention_dk32_bwd", "vit_attention_dk32_bwd", qkv, dout, lse, b, t, heads, scale, out)
+    return _vit_bwd(_VIT_DK32, qkv, dout, lse, b, t, heads, scale, out)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -18,7 +18,9 @@ tensors, bf16 under torch.autocast(bfloat16)), which keep qkv and one fp32 per q
 that holds for dk == 64 and T <= 256 on the GPU (switch: FUSED_ATTENTION).  256 < T <= 4096 (T = 785 of patch 8) has the same
 forward and the two-launch backward of csrc/vit_attn_bwd_long.hip behind a switch of its own (FUSED_ATTENTION_LONG, shipped on:
 DESIGN.md section 4 has the measurements).  The MAE decoder (512 wide, 16 heads: dk = 32, T = 197) runs the 32-wide pair of
-csrc/vit_attn_dk32.hip (dk == 32, T <= 256; switch: FUSED_ATTENTION_DK32).  Other head widths (dk = 16, 96, ...), dk = 32 above
+csrc/vit_attn_dk32.hip (dk == 32, T <= 256; switch: FUSED_ATTENTION_DK32).  The three are the records of ops.VIT_TRAIN_FORMS: `_attention`
+asks ops.vit_attention_train_form(t, dk) once and reads the form's switch (FORM_SWITCH); ViTAttentionFn asks once in forward and runs
+the backward of the record it kept.  Other head widths (dk = 16, 96, ...), dk = 32 above
 256 tokens, CPU tensors and a block that needs no gradient stay on the
 composition of torch ops, as do every Linear, LayerNorm and GELU (library GEMMs); the other hand-written inference kernels of the extractor (snuffy_amd/vit.py under torch.no_grad) are not differentiable
 and are not used here.  State-dict keys are the reference's, so a
@@ -56,39 +58,41 @@ FUSED_ATTENTION_LONG = True
 FUSED_ATTENTION_DK32 = True
 
 
+# The switch each form of ops.VIT_TRAIN_FORMS answers to; `_attention` reads it by name when called.
+FORM_SWITCH = {"short": "FUSED_ATTENTION", "long": "FUSED_ATTENTION_LONG", "dk32": "FUSED_ATTENTION_DK32"}
+
+
 class ViTAttentionFn(torch.autograd.Function):
-    """softmax(q k^T * scale) v on the qkv Linear output [B*T, 3*D] -> [B*T, D]; saves qkv and lse [B, h, T] only."""
+    """softmax(q k^T * scale) v on the qkv Linear output [B*T, 3*D] -> [B*T, D]; saves qkv and lse [B, h, T] only.  The form
+    (ops.vit_attention_train_form) is asked for once, in forward; backward runs the record forward kept."""
 
     @staticmethod
     def forward(ctx, qkv, b, t, heads, scale):
-        fwd = ops.vit_attention_dk32_fwd_lse if qkv.shape[1] // 3 // heads == 32 else ops.vit_attention_fwd_lse
-        out, lse = fwd(qkv, b, t, heads, scale)
+        form = ops.vit_attention_train_form(t, qkv.shape[1] // 3 // heads)
+        if form is None:
+            raise ops._ffi.SnuffyHipError("ViTAttentionFn: unsupported shape: no training form serves t = %d at head width %d"
+                                          % (t, qkv.shape[1] // 3 // heads))
+        out, lse = getattr(ops, form.fwd)(qkv, b, t, heads, scale)
         ctx.save_for_backward(qkv, lse)
-        ctx.dims = (b, t, heads, scale)
+        ctx.form, ctx.dims = form, (b, t, heads, scale)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
         qkv, lse = ctx.saved_tensors
-        b, t, heads, scale = ctx.dims
-        if qkv.shape[1] // 3 // heads == 32:
-            bwd = ops.vit_attention_dk32_bwd
-        else:
-            bwd = ops.vit_attention_bwd if t <= ops.VIT_BWD_MAX_T else ops.vit_attention_bwd_long
-        return bwd(qkv, dout.contiguous(), lse, b, t, heads, scale), None, None, None, None
+        return getattr(ops, ctx.form.bwd)(qkv, dout.contiguous(), lse, *ctx.dims), None, None, None, None
 
 
 def _attention(attn, x):
     b, t, d = x.shape
     h = attn.num_heads
     qkv = F.linear(x, attn.qkv.weight, attn.qkv.bias)
-    if (qkv.is_cuda and qkv.requires_grad and qkv.dtype in (torch.float32, torch.bfloat16)
-            and ((FUSED_ATTENTION and ops.vit_attention_bwd_supported(t, d // h))
-                 or (FUSED_ATTENTION_LONG and ops.vit_attention_bwd_long_supported(t, d // h))
-                 or (FUSED_ATTENTION_DK32 and ops.vit_attention_dk32_supported(t, d // h)))):
-        o = ViTAttentionFn.apply(qkv.view(b * t, 3 * d), b, t, h, attn.scale)
-        return F.linear(o.view(b, t, d), attn.proj.weight, attn.proj.bias)
+    if qkv.is_cuda and qkv.requires_grad and qkv.dtype in (torch.float32, torch.bfloat16):
+        form = ops.vit_attention_train_form(t, d // h)
+        if form is not None and globals()[FORM_SWITCH[form.name]]:
+            o = ViTAttentionFn.apply(qkv.view(b * t, 3 * d), b, t, h, attn.scale)
+            return F.linear(o.view(b, t, d), attn.proj.weight, attn.proj.bias)
     qkv = qkv.view(b, t, 3, h, d // h).permute(2, 0, 3, 1, 4)
     p = ((qkv[0] @ qkv[1].transpose(-2, -1)) * attn.scale).softmax(dim=-1)
     return F.linear((p @ qkv[2]).transpose(1, 2).reshape(b, t, d), attn.proj.weight, attn.proj.bias)

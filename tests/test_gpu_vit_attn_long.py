@@ -1,115 +1,42 @@
 """Backward of the MFMA ViT self-attention above 256 tokens (csrc/vit_attn_bwd_long.hip: a dQ launch over key chunks and a dK / dV launch
-over query chunks, ops.vit_attention_bwd_long, ssl_pretrain.FUSED_ATTENTION_LONG) on the GPU: both arithmetics against float64 autograd
-at the shapes where the chunk walk can go wrong, determinism, buffer edges, independence of images and heads, refusals, and the autograd
-layer with the switch on and off.
-
-Measured on an MI355X (profiles/vit_attn_long_train.txt has every figure), largest over the table, and the gates chosen from it:
-  dQ / dK / dV rel_err      fp32 class 2.4e-5 (dQ at (1, 2049, 1); 2.3e-5 at (2, 512, 1), 1.3e-5 at the recipe's (2, 785, 2): no clear growth
-                            with T) -> 4 x, one digit: 1e-4 (cap 2e-4);  bf16 4.2e-3 -> 2 x, one digit: 9e-3 (cap 3e-2)
-  the torch composition of the same dtype on the same inputs: fp32 5.7e-7 ... 2.3e-6, bf16 5.5e-3 ... 1.6e-2
-  block_autograd on against off (D = 128, h = 2, T = 257 and 785): <= 1.9e-6 (gate 2e-4, the short suite's)
-"""
+over query chunks, ops.vit_attention_bwd_long, ssl_pretrain.FUSED_ATTENTION_LONG) on the GPU: the `long` row of tests/vit_attn_forms.py.
+Both arithmetics against float64 autograd at the shapes where the chunk walk can go wrong, determinism, buffer edges, refusals, and the
+autograd layer with the switch on and off.  The shared bodies, the gates and the figures behind them are in the table module; the
+independence of images and heads is this form's own."""
 import pytest
 import torch
-import torch.nn.functional as F
 
-from tests.helpers import rel_err
-from tests.test_gpu_vit_attn_train import _case, _composition, _thirds, _vit
+from tests import vit_attn_forms as V
+from tests.helpers import DEV, _ops
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-BF = torch.bfloat16
-
-FORMS = ("x3", "bf16")
-# (b, t, h): one key in the second chunk with seven idle waves; one full tile in the second chunk; around exactly two chunks; the patch-8
-# recipe (25 tiles, 4 chunks, batch stride); the forward suite's longest; nine chunks with one row in the last
-SHAPES = [(2, 257, 1), (1, 288, 2), (1, 511, 1), (2, 512, 1), (1, 513, 2), (2, 785, 2), (1, 1030, 1), (1, 2049, 1)]
-BWD_GATE = {"x3": 1e-4, "bf16": 9e-3}           # tests.helpers.rel_err; caps of the issue: 2e-4 / 3e-2
+ROW = V.LONG
 
 
-def _ops():
-    from snuffy_amd import ops
-    return ops
-
-
-def _ssl():
-    from snuffy_amd import ssl_pretrain
-    return ssl_pretrain
-
-
-def _lse(qd, b, t, h):
-    return _ops().vit_attention_fwd_lse(qd, b, t, h)[1]
-
-
-@pytest.mark.parametrize("b,t,h", SHAPES)
-@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("b,t,h", ROW.shapes)
+@pytest.mark.parametrize("form", V.ARITHMETICS)
 def test_backward_against_float64(form, b, t, h):
-    qkv, dout, _, _, dref = _case(form, b, t, h)
-    for name, want in _thirds(dref):                        # the yardstick is sane: no third of the reference is zero or non-finite
-        assert bool(torch.isfinite(want).all()) and float(want.norm()) > 0, name
-    qd, dd = qkv.to(DEV), dout.to(DEV)
-    dqkv = _ops().vit_attention_bwd_long(qd, dd, _lse(qd, b, t, h), b, t, h)
-    assert dqkv.dtype == qkv.dtype and dqkv.shape == qkv.shape
-    # the torch composition in the same dtype on the same device: not a yardstick, printed for scale
-    qc = qd.clone().requires_grad_(True)
-    _composition(qc, b, t, h)[0].backward(dd)
-    errs = []
-    for (name, got), (_, comp), (_, want) in zip(_thirds(dqkv.cpu()), _thirds(qc.grad.cpu()), _thirds(dref)):
-        e = rel_err(got, want)
-        errs.append(e)
-        print("MEASURED vit attention bwd long", form, (b, t, h), name, "kernel %.3e  torch composition %.3e" % (e, rel_err(comp, want)))
-    assert max(errs) < BWD_GATE[form], errs
+    V.check_backward_against_float64(ROW, form, b, t, h)
 
 
-@pytest.mark.parametrize("b,t,h", SHAPES)
-@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("b,t,h", ROW.shapes)
+@pytest.mark.parametrize("form", V.ARITHMETICS)
 def test_backward_is_deterministic_and_writes_everything(form, b, t, h):
-    qkv, dout, _, _, _ = _case(form, b, t, h)
-    qd, dd = qkv.to(DEV), dout.to(DEV)
-    lse = _lse(qd, b, t, h)
-    first = torch.full_like(qd, float("nan"))
-    second = torch.full_like(qd, float("nan"))
-    assert _ops().vit_attention_bwd_long(qd, dd, lse, b, t, h, out=first) is first
-    _ops().vit_attention_bwd_long(qd, dd, lse, b, t, h, out=second)
-    assert not bool(torch.isnan(first).any())
-    assert torch.equal(first, second)
+    V.check_backward_is_deterministic_and_writes_everything(ROW, form, b, t, h)
 
 
-@pytest.mark.parametrize("b,t,h", [(2, 257, 1), (1, 513, 2)])
-@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("b,t,h", ROW.carve)
+@pytest.mark.parametrize("form", V.ARITHMETICS)
 def test_backward_stays_inside_its_buffers_and_padding_never_leaks(form, b, t, h):
-    """Every tensor sits between two runs of NaN: nothing outside is written, and the NaN after each tensor's last row (where rows past
-    T of the last chunk would be) reaches no result."""
-    qkv, dout, _, _, _ = _case(form, b, t, h)
-    pad = 256                                               # elements: keeps the carved tensors 16-byte aligned
-
-    def carve(src):
-        buf = torch.full((src.numel() + 2 * pad,), float("nan"), dtype=src.dtype, device=DEV)
-        view = buf[pad:pad + src.numel()].view(src.shape)
-        view.copy_(src)
-        return buf, view
-
-    qbuf, qd = carve(qkv)
-    dbuf, dd = carve(dout)
-    lse = _lse(qkv.to(DEV), b, t, h)
-    lbuf, ld = carve(lse)
-    obuf, od = carve(torch.zeros_like(qkv))
-    od.fill_(float("nan"))
-    _ops().vit_attention_bwd_long(qd, dd, ld, b, t, h, out=od)
-    want = _ops().vit_attention_bwd_long(qkv.to(DEV), dout.to(DEV), lse, b, t, h)
-    assert not bool(torch.isnan(od).any())
-    assert torch.equal(od, want)
-    for buf in (qbuf, dbuf, lbuf, obuf):
-        assert bool(torch.isnan(buf[:pad]).all()) and bool(torch.isnan(buf[-pad:]).all())
-    assert torch.equal(qd, qkv.to(DEV)) and torch.equal(dd, dout.to(DEV)) and torch.equal(ld, lse)     # inputs untouched
+    V.check_kernels_stay_inside_their_buffers(ROW, form, b, t, h)
 
 
-@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("form", V.ARITHMETICS)
 def test_images_and_heads_are_independent(form):
     b, t, h = 2, 785, 2
-    qkv, dout, _, _, _ = _case(form, b, t, h)
+    qkv, dout, _, _, _ = V.case(ROW, form, b, t, h)
     qd, dd = qkv.to(DEV), dout.to(DEV)
-    lse = _lse(qd, b, t, h)
+    lse = _ops().vit_attention_fwd_lse(qd, b, t, h)[1]
     full = _ops().vit_attention_bwd_long(qd, dd, lse, b, t, h)
     # image 1, head 1 as a (1, 785, 1) problem on that slice's operands
     q1 = qd.view(b, t, 3, h, 64)[1, :, :, 1].reshape(t, 192).contiguous()
@@ -119,107 +46,20 @@ def test_images_and_heads_are_independent(form):
     assert torch.equal(full.view(b, t, 3, h, 64)[1, :, :, 1].reshape(t, 192), alone)
 
 
-@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("form", V.ARITHMETICS)
 def test_backward_refuses_what_it_does_not_serve(form):
-    ops = _ops()
-    dt = torch.float32 if form == "x3" else BF
-
-    def call(b, t, h, dk, shift=0):
-        n = b * t * 3 * h * dk
-        qkv = torch.zeros(n + 8, dtype=dt, device=DEV)[shift:shift + n].view(b * t, 3 * h * dk)
-        dout = torch.zeros(b * t, h * dk, dtype=dt, device=DEV)
-        lse = torch.zeros(b, h, t, dtype=torch.float32, device=DEV)
-        return ops.vit_attention_bwd_long(qkv, dout, lse, b, t, h)
-
-    assert call(1, 257, 1, 64).shape == (257, 192)          # the edge of the domain is served
-    assert ops.vit_attention_bwd_long_supported(257, 64) and ops.vit_attention_bwd_long_supported(4096, 64)
-    shift = 4 // torch.zeros((), dtype=dt).element_size()   # 4 bytes
-    for kw, supported in ((dict(t=256, dk=64), False), (dict(t=4097, dk=64), False), (dict(t=300, dk=32), False),
-                          (dict(t=300, dk=64, shift=shift), True)):     # a pointer is not a shape
-        assert ops.vit_attention_bwd_long_supported(kw["t"], kw["dk"]) is supported
-        with pytest.raises(ops._ffi.SnuffyHipError, match=r"code -3\): snf_vit_attention_bwd_long: unsupported"):
-            call(1, kw["t"], 2, kw["dk"], kw.get("shift", 0))
-    with pytest.raises(ops._ffi.SnuffyHipError, match="GPU tensor"):
-        ops.vit_attention_bwd_long(torch.zeros(300, 192), torch.zeros(300, 64), torch.zeros(1, 1, 300), 1, 300, 1)
+    V.check_refuses_what_it_does_not_serve(ROW, form)
 
 
 # ---- autograd layer ----------------------------------------------------------------------------------------------------------------------
-def _count(monkeypatch, name):
-    """Wrap ops.<name> in a recorder of its (qkv shape, heads) -> the list."""
-    ops = _ops()
-    calls, real = [], getattr(ops, name)
-
-    def wrapped(qkv, *args, **kw):
-        calls.append((tuple(qkv.shape), args[4]))
-        return real(qkv, *args, **kw)
-
-    monkeypatch.setattr(ops, name, wrapped)
-    return calls
-
-
 def test_saved_state_is_qkv_and_one_float_per_row(monkeypatch):
-    S = _ssl()
-    b, t, h = 1, 257, 2
-    attn = _vit(128, h, 1, bott=8).blocks[0].attn
-    x = torch.randn(b, t, 128, device=DEV, generator=torch.Generator(DEV).manual_seed(3), requires_grad=True)
-    saved = []
-
-    def run(fn):
-        del saved[:]
-        with torch.autograd.graph.saved_tensors_hooks(lambda ten: (saved.append(ten), ten)[1], lambda ten: ten):
-            return fn()
-
-    qkv = F.linear(x, attn.qkv.weight, attn.qkv.bias).view(b * t, 3 * 128)
-    out = run(lambda: S.ViTAttentionFn.apply(qkv, b, t, h, attn.scale))
-    assert len(saved) == 2
-    assert saved[0].data_ptr() == qkv.data_ptr() and saved[0].shape == qkv.shape
-    assert saved[1].dtype == torch.float32 and saved[1].numel() == b * h * t
-    out.sum().backward()
-    assert x.grad is not None and bool(torch.isfinite(x.grad).all())
-    for flag, expect in ((True, False), (False, True)):
-        monkeypatch.setattr(S, "FUSED_ATTENTION_LONG", flag)
-        run(lambda: S._attention(attn, x))
-        assert any(ten.numel() == b * h * t * t for ten in saved) is expect, (flag, [tuple(ten.shape) for ten in saved])
+    V.check_saved_state_is_qkv_and_one_float_per_row(monkeypatch, ROW)
 
 
-@pytest.mark.parametrize("t", [257, 785])
-def test_block_with_the_kernels_matches_the_composition(monkeypatch, t):
-    S = _ssl()
-    b, d, h = 1, 128, 2
-    blk = _vit(d, h, 1, bott=8).blocks[0]
-    g = torch.Generator().manual_seed(5)
-    x0, dy = torch.randn(b, t, d, generator=g).to(DEV), torch.randn(b, t, d, generator=g).to(DEV)
-    long_calls, short_calls = _count(monkeypatch, "vit_attention_bwd_long"), _count(monkeypatch, "vit_attention_bwd")
-    res = {}
-    for flag in (True, False):
-        monkeypatch.setattr(S, "FUSED_ATTENTION_LONG", flag)
-        blk.zero_grad(set_to_none=True)
-        x = x0.clone().requires_grad_(True)
-        y = S.block_autograd(blk, x, True)
-        y.backward(dy)
-        res[flag] = [("y", y.detach()), ("dx", x.grad)] + [(n, p.grad.clone()) for n, p in blk.adaptmlp.named_parameters() if p.grad is not None and p.numel() > 1]
-        assert long_calls == [((b * t, 3 * d), h)], (flag, long_calls)      # once with the switch on, not at all with it off
-        assert not short_calls
-    assert len(res[True]) == 6                              # output, d/dx, the adapter's two weights and two biases
-    for (name, on), (_, off) in zip(res[True], res[False]):
-        e = rel_err(on, off)
-        print("MEASURED vit attention long block on vs off", t, name, "%.3e" % e)
-        assert e < 2e-4, name
+@pytest.mark.parametrize("b,t,d,h,bott", ROW.blocks, ids=[str(dims[1]) for dims in ROW.blocks])
+def test_block_with_the_kernels_matches_the_composition(monkeypatch, b, t, d, h, bott):
+    V.check_block_with_the_kernels_matches_the_composition(monkeypatch, ROW, b, t, d, h, bott)
 
 
 def test_autocast_runs_the_bf16_kernels(monkeypatch):
-    """The form follows the dtype of the qkv Linear's output: under torch.autocast(bfloat16) both kernels get bf16 tensors."""
-    S, ops = _ssl(), _ops()
-    b, t, h = 1, 257, 2
-    attn = _vit(128, h, 1, bott=8).blocks[0].attn
-    seen = []
-    real_f, real_b = ops.vit_attention_fwd_lse, ops.vit_attention_bwd_long
-    monkeypatch.setattr(ops, "vit_attention_fwd_lse", lambda qkv, *a, **k: (seen.append(("fwd", qkv.dtype)), real_f(qkv, *a, **k))[1])
-    monkeypatch.setattr(ops, "vit_attention_bwd_long", lambda qkv, dout, *a, **k: (seen.append(("bwd", qkv.dtype, dout.dtype)), real_b(qkv, dout, *a, **k))[1])
-    monkeypatch.setattr(S, "FUSED_ATTENTION_LONG", True)
-    x = torch.randn(b, t, 128, device=DEV, generator=torch.Generator(DEV).manual_seed(9), requires_grad=True)
-    with torch.autocast("cuda", BF):
-        y = S._attention(attn, x)
-    y.float().sum().backward()
-    assert seen == [("fwd", BF), ("bwd", BF, BF)]
-    assert y.dtype == BF and x.grad.dtype == torch.float32 and bool(torch.isfinite(x.grad).all()) and bool(x.grad.any())
+    V.check_autocast_runs_the_bf16_kernels(monkeypatch, ROW)
