@@ -10,6 +10,7 @@ Semantics follow the reference in train mode:
   * encoder dropout (default 0) after the attention output, inside the FFN and after it, snuffy.py:108,110,225
   * no gradient flows through the selection (snuffy.py:128-147); x itself is data (no grad) in layer 0
 """
+import collections
 import math
 
 import torch
@@ -209,6 +210,36 @@ def x3u_train_ok(k, dk):
     return bool(X3U_TRAINING and SF.FP32_ATTENTION != "exact" and not ops.x3_attn_supported(k, dk) and ops.x3u_attn_supported(k, dk))
 
 
+def _fp32_train_attn_fwd(q, kp, v, h, drop, want_p, bf16_operands=False):
+    """The training forward with P materialised for the exact backward (SparseAttnFn's second route, EncoderLayer0X3Fn):
+    (out, undropped P, mask tensor or None, regen).  Fp32-class where the shape allows -- the x 3 kernel, the unfused pair at the other
+    widths -- else the exact vector-ALU kernel; bf16_operands: the MFMA forward where it takes the shape.  drop = (p, seed, offset) or None.
+    regen: the forward applied the mask itself and nobody asked for the dropped P (want_p), so the backward regenerates it from the same
+    Philox state too and no [h, n, k] tensor is written and read twice; otherwise the same mask is written out as a tensor, and where the
+    forward did not apply it, out = (P o M)^T V is one bmm."""
+    n, d = q.shape
+    k = kp.shape[0]
+    dk = d // h
+    in_kernel = False
+    if bf16_operands and ops.mfma_attn_supported(k, dk):
+        out, p, _ = ops.sparse_attn_fwd_mfma(q.to(torch.bfloat16), v.to(torch.bfloat16), kp, n, h, need_attn=True)
+    elif ops.x3_attn_supported(k, dk) and SF.FP32_ATTENTION != "exact":
+        in_kernel = drop is not None and ops.x3_attn_dropout_supported(k, dk)       # mask applied to P in registers, P written undropped
+        out, p, _ = ops.sparse_attn_fwd_x3(q, v, kp, h, need_attn=True, dropout=drop if in_kernel else None)
+    elif not bf16_operands and x3u_train_ok(k, dk):                                 # never together with x3
+        in_kernel = drop is not None and ops.x3u_attn_dropout_supported(k, dk)      # mask applied in the pooling pass, P written undropped
+        out, p, _ = ops.sparse_attn_fwd_x3u(q, kp, v, h, need_attn=True, dropout=drop if in_kernel else None)
+    else:
+        out, p, _ = ops.sparse_attn_fwd(q, kp, v, h, need_attn=True)
+    regen = bool(in_kernel and not want_p and ops.attn_bwd_dropout_supported(k, dk))
+    mask = None
+    if drop is not None and not regen:
+        mask = ops.dropout_mask(h, n, k, drop[0], drop[1], drop[2], q.device)
+        if not in_kernel:
+            out = torch.bmm((p * mask).transpose(1, 2), v.float().reshape(n, h, dk).transpose(0, 1)).transpose(0, 1).reshape(k, d)
+    return out, p, mask, regen
+
+
 class SparseAttnFn(torch.autograd.Function):
     """O = dropout(softmax_K(Q Kp^T / sqrt(dk)))^T V per head (snuffy.py:160-168).
 
@@ -230,44 +261,17 @@ class SparseAttnFn(torch.autograd.Function):
         dk = d // h
         drop = (float(dropout_p),) + draw_dropout_state() if dropout_p > 0.0 else None
         ctx.h, ctx.drop = h, drop
-        ctx.fast_bwd = bool(bf16_operands and ops.mfma_attn_supported(k, dk) and ops.mfma_attn_bwd_supported(k, dk))
-        # SPARSE_ATTN_FN_WIDE: the same branch at the native head widths (any key count of theirs: the backward runs over key chunks)
-        wide = bool(SPARSE_ATTN_FN_WIDE and bf16_operands and not ctx.fast_bwd
-                    and ((dk == 192 and d == 192 * h and ops.mfma_attn_dk192_supported(k, n, d))
-                         or (dk == 256 and d == 256 * h and ops.mfma_attn_dk256_train_supported(k, n, d))))
-        if wide:
-            ctx.fast_bwd = True
-            q16, v16 = q.to(torch.bfloat16), v.to(torch.bfloat16)
-            if dk == 256:
-                out, p, lse = ops.sparse_attn_fwd_mfma_dk256(q16, v16, kp, h, need_attn=want_p, need_lse=True, dropout=drop)
-            else:
-                out, p, lse = ops.sparse_attn_fwd_mfma(q16, v16, kp, n, h, need_attn=want_p, need_lse=True, dropout=drop)
-            ctx.save_for_backward(q16, kp, v16, lse)
-            return out, p
+        form = ops.sparse_attn_form("bf16", dk) if bf16_operands else None
+        if form is not None and form.by_dk:
+            ctx.fast_bwd = bool(ops.mfma_attn_supported(k, dk) and ops.mfma_attn_bwd_supported(k, dk))
+        else:   # SPARSE_ATTN_FN_WIDE: the same branch at the native head widths (any key count of theirs: the backward runs over key chunks)
+            ctx.fast_bwd = bool(SPARSE_ATTN_FN_WIDE and form is not None and d == dk * h and ops.sparse_attn_form_trains(form, k, n, d))
         if ctx.fast_bwd:
             q16, v16 = q.to(torch.bfloat16), v.to(torch.bfloat16)
-            out, p, lse = ops.sparse_attn_fwd_mfma(q16, v16, kp, n, h, need_attn=want_p, need_lse=True, dropout=drop)
+            out, p, lse = ops.sparse_attn_fwd_form(form, q16, v16, kp, h, need_attn=want_p, need_lse=True, dropout=drop)
             ctx.save_for_backward(q16, kp, v16, lse)        # P is recomputed from lse, the mask from (seed, offset)
             return out, p
-        in_kernel = False
-        if bf16_operands and ops.mfma_attn_supported(k, dk):
-            out, p, _ = ops.sparse_attn_fwd_mfma(q.to(torch.bfloat16), v.to(torch.bfloat16), kp, n, h, need_attn=True)
-        elif ops.x3_attn_supported(k, dk) and SF.FP32_ATTENTION != "exact":
-            in_kernel = drop is not None and ops.x3_attn_dropout_supported(k, dk)       # mask applied to P in registers, P written undropped
-            out, p, _ = ops.sparse_attn_fwd_x3(q, v, kp, h, need_attn=True, dropout=drop if in_kernel else None)
-        elif not bf16_operands and x3u_train_ok(k, dk):
-            in_kernel = drop is not None and ops.x3u_attn_dropout_supported(k, dk)      # mask applied in the pooling pass, P written undropped
-            out, p, _ = ops.sparse_attn_fwd_x3u(q, kp, v, h, need_attn=True, dropout=drop if in_kernel else None)
-        else:
-            out, p, _ = ops.sparse_attn_fwd(q, kp, v, h, need_attn=True)
-        mask = None
-        # (round 6) nobody asked for the dropped P and the forward applied the mask itself: the backward regenerates it too, no tensor
-        ctx.regen = bool(in_kernel and not want_p and ops.attn_bwd_dropout_supported(k, dk))
-        if drop is not None and not ctx.regen:
-            mask = ops.dropout_mask(h, n, k, drop[0], drop[1], drop[2], q.device)
-            if not in_kernel:
-                vh = v.float().reshape(n, h, dk).transpose(0, 1)
-                out = torch.bmm((p * mask).transpose(1, 2), vh).transpose(0, 1).reshape(k, d)
+        out, p, mask, ctx.regen = _fp32_train_attn_fwd(q, kp, v, h, drop, want_p, bf16_operands)
         ctx.save_for_backward(q, kp, v, p, mask)
         return out, (p * mask if mask is not None else p)
 
@@ -435,12 +439,8 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
             kp = torch.addmm(fw["bk"], xs16, fw["wk"].t()).float()
         p_drop = mha.dropout.p if layer.training else 0.0
         drop = (float(p_drop),) + draw_dropout_state() if p_drop > 0.0 else None
-        if dkp == 256:                                                                 # the width's own entry point (fused_layer0_dk256_ok)
-            o, attn, lse = ops.sparse_attn_fwd_mfma_dk256(q, v, kp, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn, need_lse=True,
-                                                          dropout=drop)
-        else:
-            o, attn, lse = ops.sparse_attn_fwd_mfma(q, v, kp, n, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn, need_lse=True,
-                                                    dropout=drop)
+        o, attn, lse = ops.sparse_attn_fwd_form(ops.sparse_attn_form("bf16", dkp), q, v, kp, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn,
+                                                need_lse=True, dropout=drop)           # the record's wrapper (_FUSED_LAYER0_ADMISSIONS)
         # encoder dropout: A = after the attention output (snuffy.py:108), H = inside the FFN (:225), Z = after it (:110)
         p_a, p_h, p_z = _encoder_dropout_ps(layer)
         drop_a = (p_a,) + draw_dropout_state() if p_a > 0.0 else None
@@ -557,9 +557,28 @@ class EncoderLayer0Bf16Fn(torch.autograd.Function):
         return (None, None, None, None, dg0, db0, dg1, db1, dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo, dw1, db1f, dw2, db2)
 
 
-def _fused_layer0_base_ok(layer, n, d, k=None):
-    """fused_layer0_shape_ok without its word on encoder dropout."""
-    if not FUSED_BF16_TRAINING:
+# What EncoderLayer0Bf16Fn admits, one record per admission: (name, the switch beside FUSED_BF16_TRAINING or None, head width or None =
+# the widths the 64 / 128 kernels serve, whether a width between them rides zero-padded (functional.head_pad), whether forward and
+# backward have to be one launch each).  The key counts are those of the width's record in ops.SPARSE_ATTN_FORMS.
+_Layer0Admission = collections.namedtuple("_Layer0Admission", "name switch dk pad one_launch")
+_FUSED_LAYER0_ADMISSIONS = (
+    _Layer0Admission("train", None, None, False, True),
+    # up to 8 key chunks -- forward with in-kernel dropout, backward over chunks -- and padded heads (dk = 96 -> 128).  dk = 192 (the
+    # README's MAE recipe) has no padded form and is declined here
+    _Layer0Admission("chunked", "FUSED_BF16_KEY_CHUNKS", None, True, False),
+    # the width's own kernels, unpadded: the forward over chunks of 128 keys, the backward on the chunked kernel at any key count
+    _Layer0Admission("dk192", "FUSED_BF16_DK192", 192, False, False),
+    _Layer0Admission("dk256", "FUSED_BF16_DK256", 256, False, False),
+)
+_L0_TRAIN, _L0_CHUNKED, _L0_DK192, _L0_DK256 = _FUSED_LAYER0_ADMISSIONS
+
+
+def _fused_layer0_admits(adm, layer, n, d, k=None, encoder_dropout=True):
+    """EncoderLayer0Bf16Fn takes the layer under one admission: its switches on, ReLU FFN, one eps, a head width and a key count (k =
+    number of selected rows; default: the layer's Lambda capped by n) the admission's attention kernels train at, all parameters
+    trainable.  encoder_dropout -- True: the three encoder-dropout p's anywhere in [0, 1) with FUSED_BF16_ENCODER_DROPOUT and shapes the
+    dropout kernels take; False: the dropout-free chain only (a train-mode layer with a p > 0 is declined); None: no word on it."""
+    if not (FUSED_BF16_TRAINING and (adm.switch is None or globals()[adm.switch])):
         return False
     mha, ff = layer.self_attn, layer.feed_forward
     n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
@@ -567,96 +586,48 @@ def _fused_layer0_base_ok(layer, n, d, k=None):
         return False
     if k is None:
         k = min(int(layer.big_lambda), n)
-    dk = d // mha.h
-    return (k >= 1 and ops.mfma_attn_supported(k, dk, n, 2 * d) and k <= (224 if dk == 128 else 256)
-            and ops.mfma_attn_bwd_supported(k, dk) and all(p.requires_grad for p in layer.parameters()))
+    dkp = SF.head_pad(d // mha.h) if adm.pad else d // mha.h
+    form = ops.sparse_attn_form("bf16", dkp, adm.dk is None) if adm.dk in (None, dkp) else None
+    if form is None or not (ops.sparse_attn_form_trains(form, k, n, 2 * mha.h * dkp, adm.one_launch)      # 2 h dkp: the pitch of Q | V
+                            and all(p.requires_grad for p in layer.parameters())):
+        return False
+    ps = _encoder_dropout_ps(layer)
+    # A site is off at p == 0.  The one-launch admission has always asked "no p > 0" instead, which differs for p < 0 only, a value
+    # nn.Dropout cannot hold: each admission keeps the answer it gave
+    if encoder_dropout is None or not any(p > 0 if adm.one_launch else p != 0.0 for p in ps):
+        return True
+    return bool(encoder_dropout and FUSED_BF16_ENCODER_DROPOUT and all(0.0 <= p < 1.0 for p in ps)
+                and ops.bf16_encoder_dropout_supported(n, d, ff.w_1.weight.shape[0]))
+
+
+def _fused_layer0_base_ok(layer, n, d, k=None):
+    """fused_layer0_shape_ok without its word on encoder dropout."""
+    return _fused_layer0_admits(_L0_TRAIN, layer, n, d, k, None)
 
 
 def fused_layer0_shape_ok(layer, n, d, k=None):
-    """Settings / shapes the dropout-free EncoderLayer0Bf16Fn covers (k = number of selected rows; default: the layer's Lambda capped
-    by n).  A train-mode layer with encoder dropout is declined here; fused_layer0_train_ok is the predicate that admits it."""
-    if layer.training and (layer.sublayer[0].dropout.p > 0 or layer.sublayer[1].dropout.p > 0 or layer.feed_forward.dropout.p > 0):
-        return False
-    return _fused_layer0_base_ok(layer, n, d, k)
+    """Settings / shapes the dropout-free EncoderLayer0Bf16Fn covers; fused_layer0_train_ok admits a train-mode layer with encoder dropout."""
+    return _fused_layer0_admits(_L0_TRAIN, layer, n, d, k, False)
 
 
 def fused_layer0_train_ok(layer, n, d, k=None):
-    """EncoderLayer0Bf16Fn takes the layer: the dropout-free chain's settings / shapes, or -- with FUSED_BF16_ENCODER_DROPOUT -- the same
-    with the three encoder-dropout p's anywhere in [0, 1) and shapes the dropout kernels take."""
-    if fused_layer0_shape_ok(layer, n, d, k):
-        return True
-    return (FUSED_BF16_ENCODER_DROPOUT and all(0.0 <= p < 1.0 for p in _encoder_dropout_ps(layer)) and _fused_layer0_base_ok(layer, n, d, k)
-            and ops.bf16_encoder_dropout_supported(n, d, layer.feed_forward.w_1.weight.shape[0]))
+    """EncoderLayer0Bf16Fn takes the layer: one launch of the attention each way at 64 / 128, encoder dropout as the chain fuses it."""
+    return _fused_layer0_admits(_L0_TRAIN, layer, n, d, k)
 
 
 def fused_layer0_chunked_ok(layer, n, d, k=None):
-    """EncoderLayer0Bf16Fn takes the layer beyond fused_layer0_train_ok (FUSED_BF16_KEY_CHUNKS): the same settings (ReLU FFN, one eps, all
-    parameters trainable, encoder dropout as fused_layer0_train_ok admits it) with up to 8 key chunks of the MFMA attention instead of one
-    and with a head width that is 64 or 128 after functional.head_pad.  dk = 192 (the README's MAE recipe) has no padded form and is
-    declined here: it runs unpadded on kernel variants of its own, which fused_layer0_dk192_ok admits."""
-    if not (FUSED_BF16_TRAINING and FUSED_BF16_KEY_CHUNKS):
-        return False
-    mha, ff = layer.self_attn, layer.feed_forward
-    n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
-    if ff.activation_name != "relu" or n0.eps != n1.eps or d % mha.h:
-        return False
-    if k is None:
-        k = min(int(layer.big_lambda), n)
-    dk = d // mha.h
-    dkp = SF.head_pad(dk)
-    if dkp is None:
-        return False
-    dp = mha.h * dkp
-    if not (k >= 1 and ops.mfma_attn_supported(k, dkp, n, 2 * dp) and ops.mfma_attn_train_chunks_supported(k, dkp)
-            and all(p.requires_grad for p in layer.parameters())):
-        return False
-    ps = _encoder_dropout_ps(layer)
-    if any(p != 0.0 for p in ps):
-        return (FUSED_BF16_ENCODER_DROPOUT and all(0.0 <= p < 1.0 for p in ps)
-                and ops.bf16_encoder_dropout_supported(n, d, ff.w_1.weight.shape[0]))
-    return True
+    """... beyond fused_layer0_train_ok (FUSED_BF16_KEY_CHUNKS): up to 8 key chunks, head widths that are 64 or 128 after head_pad."""
+    return _fused_layer0_admits(_L0_CHUNKED, layer, n, d, k)
 
 
 def fused_layer0_dk192_ok(layer, n, d, k=None):
-    """EncoderLayer0Bf16Fn takes the layer at head width 192, unpadded (FUSED_BF16_DK192): the settings of fused_layer0_chunked_ok (ReLU
-    FFN, one eps, all parameters trainable, encoder dropout as admitted there) with the key counts of ops.mfma_attn_dk192_supported --
-    the forward over up to 8 chunks of 128 keys, the backward on the chunked kernel at any key count."""
-    if not (FUSED_BF16_TRAINING and FUSED_BF16_DK192):
-        return False
-    mha, ff = layer.self_attn, layer.feed_forward
-    n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
-    if ff.activation_name != "relu" or n0.eps != n1.eps or d % mha.h or d // mha.h != 192:
-        return False
-    if k is None:
-        k = min(int(layer.big_lambda), n)
-    if not (ops.mfma_attn_dk192_supported(k, n, 2 * d) and all(p.requires_grad for p in layer.parameters())):
-        return False
-    ps = _encoder_dropout_ps(layer)
-    if any(p != 0.0 for p in ps):
-        return (FUSED_BF16_ENCODER_DROPOUT and all(0.0 <= p < 1.0 for p in ps)
-                and ops.bf16_encoder_dropout_supported(n, d, ff.w_1.weight.shape[0]))
-    return True
+    """... at head width 192, unpadded (FUSED_BF16_DK192), with the key counts of ops.mfma_attn_dk192_supported."""
+    return _fused_layer0_admits(_L0_DK192, layer, n, d, k)
 
 
 def fused_layer0_dk256_ok(layer, n, d, k=None):
-    """EncoderLayer0Bf16Fn takes the layer at head width 256 (FUSED_BF16_DK256): the settings of fused_layer0_dk192_ok (ReLU FFN, one
-    eps, all parameters trainable, encoder dropout as admitted there) with the key counts of ops.mfma_attn_dk256_train_supported -- the
-    forward over up to 8 chunks of 128 keys with in-kernel dropout, the backward on the chunked kernel at any key count."""
-    if not (FUSED_BF16_TRAINING and FUSED_BF16_DK256):
-        return False
-    mha, ff = layer.self_attn, layer.feed_forward
-    n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
-    if ff.activation_name != "relu" or n0.eps != n1.eps or d % mha.h or d // mha.h != 256:
-        return False
-    if k is None:
-        k = min(int(layer.big_lambda), n)
-    if not (ops.mfma_attn_dk256_train_supported(k, n, 2 * d) and all(p.requires_grad for p in layer.parameters())):
-        return False
-    ps = _encoder_dropout_ps(layer)
-    if any(p != 0.0 for p in ps):
-        return (FUSED_BF16_ENCODER_DROPOUT and all(0.0 <= p < 1.0 for p in ps)
-                and ops.bf16_encoder_dropout_supported(n, d, ff.w_1.weight.shape[0]))
-    return True
+    """... at head width 256 (FUSED_BF16_DK256), with the key counts of ops.mfma_attn_dk256_train_supported."""
+    return _fused_layer0_admits(_L0_DK256, layer, n, d, k)
 
 
 def fused_layer0_ok(x2, sel, layer, precision):
@@ -664,10 +635,7 @@ def fused_layer0_ok(x2, sel, layer, precision):
     everything else keeps the generic autograd chain below."""
     if precision != "bf16" or x2.requires_grad or sel.numel() == 0:
         return False
-    return (fused_layer0_train_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
-            or fused_layer0_chunked_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
-            or fused_layer0_dk192_ok(layer, x2.shape[0], x2.shape[1], sel.numel())
-            or fused_layer0_dk256_ok(layer, x2.shape[0], x2.shape[1], sel.numel()))
+    return any(_fused_layer0_admits(adm, layer, x2.shape[0], x2.shape[1], sel.numel()) for adm in _FUSED_LAYER0_ADMISSIONS)
 
 
 def _x3_train_weights(layer, hl=False):
@@ -769,7 +737,6 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
         n, d = x2.shape
         mha = layer.self_attn
         h = mha.h
-        dk = d // h
         k = sel.numel()
         eps = layer.sublayer[0].norm.eps
         hl = _x3_train_hl_ok(n, d, w1.shape[0])
@@ -787,24 +754,7 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
         kp = F.linear(xs, wk, bk)
         p_drop = mha.dropout.p if layer.training else 0.0
         drop = (float(p_drop),) + draw_dropout_state() if p_drop > 0.0 else None
-        x3 = ops.x3_attn_supported(k, dk) and SF.FP32_ATTENTION != "exact"
-        x3u = x3u_train_ok(k, dk)                                                         # never together with x3
-        in_kernel = drop is not None and ((x3 and ops.x3_attn_dropout_supported(k, dk)) or (x3u and ops.x3u_attn_dropout_supported(k, dk)))
-        if x3:
-            # training: the kernel applies the Philox mask to P in registers (O = (P o M)^T V) and writes the undropped P for the backward
-            o, p, _ = ops.sparse_attn_fwd_x3(q, v, kp, h, need_attn=True, dropout=drop if in_kernel else None)
-        elif x3u:
-            # the widths outside those kernels: the unfused pair, the mask applied in its pooling pass
-            o, p, _ = ops.sparse_attn_fwd_x3u(q, kp, v, h, need_attn=True, dropout=drop if in_kernel else None)
-        else:
-            o, p, _ = ops.sparse_attn_fwd(q, kp, v, h, need_attn=True)
-        mask = None
-        # the backward regenerates the mask from the same Philox state where it can (round 6: no [h, n, k] tensor written and read twice)
-        regen = in_kernel and not need_attn and ops.attn_bwd_dropout_supported(k, dk)
-        if drop is not None and not regen:
-            mask = ops.dropout_mask(h, n, k, drop[0], drop[1], drop[2], x2.device)         # the same mask as a tensor: the backward reads it
-            if not in_kernel:
-                o = torch.bmm((p * mask).transpose(1, 2), v.reshape(n, h, dk).transpose(0, 1)).transpose(0, 1).reshape(k, d)
+        o, p, mask, regen = _fp32_train_attn_fwd(q, kp, v, h, drop, need_attn)
         # encoder dropout (hl chain only, fused_layer0_x3_ok): one Philox state per site, drawn in the order A, H, Z after the attention's
         # own draw; a site with p == 0 draws nothing.  A = after the attention output (snuffy.py:108), H = inside the FFN (:225), Z = after it (:110)
         p_a, p_h, p_z = _encoder_dropout_ps(layer)

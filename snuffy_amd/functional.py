@@ -65,27 +65,25 @@ X3_ATTN_DK192 = False
 # (tools/x3_dk256_time.py) has the fused kernel at 0.76 - 0.88x the pair at N = 8000 / 32768 (eight key chunks at Lambda = 900, GEMM1
 # run twice).  The packed route (packed.PACK_X3_DK256) does not consult this switch.
 X3_ATTN_DK256 = False
-# The native head widths: (precision, head width, switch of the single-bag route, its predicate, its op, predicate of the packed route),
-# all by name -- the switches and ops are looked up when a layer runs.  bf16 at 192 has no op of its own: ops.sparse_attn_fwd_mfma
-# takes the width.  A packed bag asks the last column only (its switches are packed.PACK_*).
-_WIDE = (("fp32", 192, "X3_ATTN_DK192", "x3_attn_dk192_supported", "sparse_attn_fwd_x3_dk192", "varlen_attn_x3_dk192_supported"),
-         ("fp32", 256, "X3_ATTN_DK256", "x3_attn_dk256_supported", "sparse_attn_fwd_x3_dk256", "varlen_attn_x3_dk256_supported"),
-         ("bf16", 192, "MFMA_ATTN_DK192", "mfma_attn_dk192_supported", None, "varlen_attn_dk192_supported"),
-         ("bf16", 256, "MFMA_ATTN_DK256", "mfma_attn_dk256_supported", "sparse_attn_fwd_mfma_dk256", "varlen_attn_dk256_supported"))
+# The native head widths: (precision, head width, switch of the single-bag route), the switch by name -- it is looked up when a layer
+# runs.  Key counts, row limits and the op are those of the width's record in ops.SPARSE_ATTN_FORMS.  A packed bag asks the record
+# only (its switches are packed.PACK_*).
+_WIDE = (("fp32", 192, "X3_ATTN_DK192"), ("fp32", 256, "X3_ATTN_DK256"), ("bf16", 192, "MFMA_ATTN_DK192"), ("bf16", 256, "MFMA_ATTN_DK256"))
 
 
 def _wide_single(precision, d, h, *shape):
-    """The row of _WIDE a single bag of d = width * h takes: its switch is on and its predicate takes shape = (k[, n, ld]); or None."""
-    for row in _WIDE:
-        prec, width, switch, supported = row[:4]
-        if prec == precision and globals()[switch] and d == width * h and getattr(ops, supported)(*shape):
-            return row
+    """The record of ops.SPARSE_ATTN_FORMS a single bag of d = width * h takes: the switch of its row in _WIDE is on and it serves
+    shape = (k[, n, ld]); or None."""
+    for prec, width, switch in _WIDE:
+        if prec == precision and globals()[switch] and d == width * h and ops.sparse_attn_form_serves(ops.sparse_attn_form(prec, width), *shape):
+            return ops.sparse_attn_form(prec, width)
     return None
 
 
 def _wide_varlen_supported(precision, d, h, kb):
     """A packed bag of kb keys is inside the varlen kernel of a native head width."""
-    return any(prec == precision and d == width * h and getattr(ops, supported)(kb) for prec, width, _, _, _, supported in _WIDE)
+    return any(prec == precision and d == width * h and ops.sparse_attn_form_serves(ops.sparse_attn_form(prec, width), kb)
+               for prec, width, _ in _WIDE)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -756,7 +754,7 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
         elif FP32_ATTENTION == "x3" and ops.x3_attn_supported(k, d // h):
             o, attn, _ = ops.sparse_attn_fwd_x3(q, v, kp, h, need_attn=need_attn)    # snuffy.py:160-168
         elif FP32_ATTENTION == "x3" and (wide := _wide_single("fp32", d, h, k)) is not None:
-            o, attn, _ = getattr(ops, wide[4])(q, v, kp, h, need_attn=need_attn)   # q, v: halves of the fused projection, in place
+            o, attn, _ = ops.sparse_attn_fwd_form(wide, q, v, kp, h, need_attn=need_attn)   # q, v: halves of the fused projection, in place
         elif FP32_ATTENTION == "x3" and ops.x3u_attn_supported(k, d // h):
             # head widths no pipelined kernel takes (dk = 192: the README recipe D = 768 / h = 4): the unfused fp32-class pair
             o, attn, _ = ops.sparse_attn_fwd_x3u(q, kp, v, h, need_attn=need_attn)      # q, v: halves of the fused projection, in place
@@ -869,8 +867,8 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             kp = torch.addmm(fw["bk"], xs16, fw["wk"].t())
         if packed is not None:
             o, attn, _ = ops.sparse_attn_fwd_mfma_varlen(q, v, kp, packed, kb, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
-        elif wide is not None and wide[4] is not None:
-            o, attn, _ = getattr(ops, wide[4])(q, v, kp, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
+        elif wide is not None:
+            o, attn, _ = ops.sparse_attn_fwd_form(wide, q, v, kp, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
         else:
             o, attn, _ = ops.sparse_attn_fwd_mfma(q, v, kp, n, h, scale=1.0 / math.sqrt(dk), need_attn=need_attn)
     else:

@@ -664,15 +664,109 @@ def sparse_attn_bwd(q, kp, v, p, dout, h, mask=None, scale=None, dropout=None):
     return dq, dkp, dv
 
 
+# The forms of the tiled sparse attention, one record per (family, head width): what the predicates, the forward wrappers, the varlen
+# plans and the routing in autograd / functional / packed differ in.  The bounds -- keys per launch, key chunks, the row limits below --
+# are written here and nowhere else in Python, error messages included (tests/test_sparse_attn_forms_host.py holds every record against
+# what the library answers on the host).  Everything is a name, looked up when it is used: tests replace the wrappers with spies.
+#   family         "bf16" (the mfma kernels) or "x3" (fp32 class: split-bf16 x 3); callers may say "fp32" for "x3" (sparse_attn_form)
+#   keys, chunks   a launch holds `keys` keys in LDS; up to `chunks` launches run back to back with exact cross-chunk softmax statistics
+#   row_limits     the kernels address the rows of q / v with 32-bit element offsets (_rows_addressable)
+#   by_dk          True: the predicates that take dk answer for the width and its varlen entry points take dk; False: a later width
+#                  with predicates and varlen entry points of its own, which the older predicates keep declining
+#   wrapper, takes_n   the public single-bag forward and whether it takes the row count n after kp (sparse_attn_fwd_form passes it)
+#   c_fwd, c_dropout, c_workspace   the C names behind the wrapper (c_dropout None: no in-kernel dropout forward)
+#   varlen         (plan kind of PackedBags.plan, C plan function, C entry point, the plan also returns (chunks, keys per chunk)): by_dk
+#                  forms have a one-launch entry and a key-chunked one, in that order; the later widths one that does both
+#   dropout_chunks key chunks the in-kernel Philox dropout forward takes (0: none, 1: one launch only)
+#   bwd_one_launch, bwd_chunked   the MFMA backward exists as one launch (k <= keys) / over key chunks (sparse_attn_bwd_mfma)
+# A further width is one more record, its wrapper and its kernels.
+SparseAttnVarlen = collections.namedtuple("SparseAttnVarlen", "kind c_plan c_fwd chunk_outputs")
+SparseAttnForm = collections.namedtuple("SparseAttnForm", "family dk keys chunks row_limits by_dk wrapper takes_n c_fwd c_dropout c_workspace "
+                                                          "varlen dropout_chunks bwd_one_launch bwd_chunked")
+_MFMA_VARLEN = (SparseAttnVarlen("mfma", "snf_sparse_attn_varlen_plan", "snf_sparse_attn_fwd_mfma_varlen", False),
+                SparseAttnVarlen("mfma_chunks", "snf_sparse_attn_varlen_chunked_plan", "snf_sparse_attn_fwd_mfma_varlen_chunked", True))
+_X3_VARLEN = (SparseAttnVarlen("x3", "snf_sparse_attn_x3_varlen_plan", "snf_sparse_attn_fwd_x3_varlen", False),
+              SparseAttnVarlen("x3_chunks", "snf_sparse_attn_x3_varlen_chunked_plan", "snf_sparse_attn_fwd_x3_varlen_chunked", True))
+_MFMA_C = ("snf_sparse_attn_fwd_mfma", "snf_sparse_attn_fwd_mfma_dropout", "snf_sparse_attn_fwd_workspace_bytes")
+_X3_C = ("snf_sparse_attn_fwd_x3", "snf_sparse_attn_fwd_x3_dropout", "snf_sparse_attn_fwd_x3_workspace_bytes")
+SPARSE_ATTN_FORMS = (
+    # 256 keys next to the P and V images in the 160 KiB LDS of a CU
+    SparseAttnForm("bf16", 64, 256, 8, True, True, "sparse_attn_fwd_mfma", True, *_MFMA_C, _MFMA_VARLEN, 8, True, True),
+    # ... 224 at this width
+    SparseAttnForm("bf16", 128, 224, 8, True, True, "sparse_attn_fwd_mfma", True, *_MFMA_C, _MFMA_VARLEN, 8, True, True),
+    # the README's MAE recipe (D = 768, h = 4), no padded form: Kp 48 + P 40 + V 48 KiB of LDS.  The single bag rides the 64 / 128 entry
+    # points (forward with or without dropout; the backward on the chunked kernel at any key count), the varlen form has its own
+    SparseAttnForm("bf16", 192, 128, 8, True, False, "sparse_attn_fwd_mfma", True, *_MFMA_C,
+                   (SparseAttnVarlen("mfma_dk192", "snf_sparse_attn_varlen_dk192_plan", "snf_sparse_attn_fwd_mfma_varlen_dk192", True),), 8, False, True),
+    # the README's SimCLR ResNet-18 recipe (D = 512, h = 2, Lambda = 900).  The backward addresses rows in 64 bits; the forward sets the limit
+    SparseAttnForm("bf16", 256, 128, 8, True, False, "sparse_attn_fwd_mfma_dk256", False, "snf_sparse_attn_fwd_mfma_dk256",
+                   "snf_sparse_attn_fwd_mfma_dk256_dropout", "snf_sparse_attn_fwd_mfma_dk256_workspace_bytes",
+                   (SparseAttnVarlen("mfma_dk256", "snf_sparse_attn_varlen_dk256_plan", "snf_sparse_attn_fwd_mfma_varlen_dk256", True),), 8, False, True),
+    # the bf16 budgets (the operands are split on the fly); the kernel is built for 2, 4, 7 (8) key blocks and applies the training
+    # dropout mask itself within one launch
+    SparseAttnForm("x3", 64, 256, 8, False, True, "sparse_attn_fwd_x3", False, *_X3_C, _X3_VARLEN, 1, False, False),
+    SparseAttnForm("x3", 128, 224, 8, False, True, "sparse_attn_fwd_x3", False, *_X3_C, _X3_VARLEN, 1, False, False),
+    # fused (no materialised [h, n, k] probabilities between the softmax and P^T V), the MAE recipe
+    SparseAttnForm("x3", 192, 128, 8, False, False, "sparse_attn_fwd_x3_dk192", False, "snf_sparse_attn_fwd_x3_dk192", None,
+                   "snf_sparse_attn_fwd_x3_dk192_workspace_bytes",
+                   (SparseAttnVarlen("x3_dk192", "snf_sparse_attn_x3_varlen_dk192_plan", "snf_sparse_attn_fwd_x3_varlen_dk192", True),), 0, False, False),
+    # ... the SimCLR ResNet-18 recipe: the key range of the unfused pair (x3u_attn_supported)
+    SparseAttnForm("x3", 256, 128, 8, False, False, "sparse_attn_fwd_x3_dk256", False, "snf_sparse_attn_fwd_x3_dk256", None,
+                   "snf_sparse_attn_fwd_x3_dk256_workspace_bytes",
+                   (SparseAttnVarlen("x3_dk256", "snf_sparse_attn_x3_varlen_dk256_plan", "snf_sparse_attn_fwd_x3_varlen_dk256", True),), 0, False, False),
+)
+_FORM_OF = {(f.family, f.dk): f for f in SPARSE_ATTN_FORMS}
+_VARLEN_PLANS = {e.kind: e for f in SPARSE_ATTN_FORMS for e in f.varlen}
+
+
+def sparse_attn_form(family, dk, by_dk=None):
+    """The record of SPARSE_ATTN_FORMS for a family ("bf16", "x3" or, as a model's precision, "fp32") and head width, or None (pure
+    host).  by_dk: only a record with that value of the field."""
+    form = _FORM_OF.get(("x3" if family == "fp32" else family, dk))
+    return form if form is not None and by_dk in (None, form.by_dk) else None
+
+
+def _rows_addressable(n, ld=None):
+    """n rows of pitch ld (elements) are within the 32-bit element offsets the bf16 family addresses the rows of q and v with."""
+    return not (n > 0xffff00 or (ld is not None and (ld >= (1 << 24) or n * ld >= 0x7fffffff)))
+
+
+def sparse_attn_form_serves(form, k, n=None, ld=None, chunks="chunks", need=()):
+    """1 <= k <= keys per launch x chunks of a record (chunks: a count, or the field that holds it), with the fields named in `need`
+    set and, where n (and ld) are given, rows within the record's limits.  No record: False."""
+    if form is None or not all(getattr(form, f) for f in need):
+        return False
+    if not 1 <= k <= form.keys * (getattr(form, chunks) if isinstance(chunks, str) else chunks):
+        return False
+    return not (form.row_limits and n is not None and not _rows_addressable(n, ld))
+
+
+def sparse_attn_form_trains(form, k, n=None, ld=None, one_launch=False):
+    """A bf16 record trains at k keys (n rows of pitch ld): the forward with in-kernel Philox dropout over its key chunks and the MFMA
+    backward over chunks -- one_launch: each in one launch.  No record: False."""
+    if one_launch:
+        return sparse_attn_form_serves(form, k, n, ld, 1, need=("dropout_chunks", "bwd_one_launch"))
+    return sparse_attn_form_serves(form, k, n, ld, "dropout_chunks", need=("bwd_chunked",))
+
+
+def sparse_attn_fwd_form(form, q, v, kp, h, scale=None, need_attn=False, need_lse=False, dropout=None):
+    """The single-bag forward of a record: its public wrapper, looked up on this module when called, with n = q's rows where the wrapper
+    takes it.  dropout is handed on where the wrapper has the parameter (c_dropout)."""
+    kw = {"dropout": dropout} if form.c_dropout is not None else {}
+    if dropout is not None and not kw:
+        raise ValueError("%s has no in-kernel dropout" % form.wrapper)
+    fn = globals()[form.wrapper]
+    return fn(q, v, kp, *((q.shape[0],) if form.takes_n else ()), h, scale=scale, need_attn=need_attn, need_lse=need_lse, **kw)
+
+
 def mfma_attn_bwd_supported(k, dk):
-    return (dk == 128 and 1 <= k <= 224) or (dk == 64 and 1 <= k <= 256)
+    """The one-launch MFMA backward (snf_sparse_attn_bwd_mfma_ex): one key chunk at 64 / 128."""
+    return sparse_attn_form_serves(sparse_attn_form("bf16", dk, True), k, chunks=1, need=("bwd_one_launch",))
 
 
 def mfma_attn_train_chunks_supported(k, dk):
-    """Key counts the MFMA attention trains at with in-kernel Philox dropout, forward and backward: the forward's up to 8 key chunks
-    (snf_sparse_attn_fwd_mfma_dropout over chunks, snf_sparse_attn_bwd_mfma_chunked).  One chunk is what mfma_attn_dropout_supported
-    and mfma_attn_bwd_supported describe."""
-    return (dk == 128 and 1 <= k <= 8 * 224) or (dk == 64 and 1 <= k <= 8 * 256)
+    """Key counts the MFMA attention trains at with in-kernel Philox dropout at 64 / 128: the forward's chunks, the chunked backward."""
+    return sparse_attn_form_trains(sparse_attn_form("bf16", dk, True), k)
 
 
 def sparse_attn_bwd_mfma(q, v, kp, dout, lse, h, mask=None, scale=None, dropout=None, fused_bf16_grads=False):
@@ -742,84 +836,77 @@ def sparse_attn_bwd_mfma(q, v, kp, dout, lse, h, mask=None, scale=None, dropout=
 
 
 def mfma_attn_supported(k, dk, n=None, ld=None):
-    """Shapes the MFMA attention kernel takes.  One launch holds 256 (dk = 64) / 224 (dk = 128) keys next to the P and V
-    images in the 160 KiB LDS of a CU; up to 8 key chunks are run back to back with exact cross-chunk softmax statistics.
-    n / ld (rows and row pitch of q, v) are optional: the kernel addresses rows with 32-bit element offsets."""
-    if not ((dk == 64 and 1 <= k <= 8 * 256) or (dk == 128 and 1 <= k <= 8 * 224)):
-        return False
-    if n is not None and (n > 0xffff00 or (ld is not None and (ld >= (1 << 24) or n * ld >= 0x7fffffff))):
-        return False
-    return True
-
-
-WIDE_KEYS = 8 * 128      # the native head widths (192, 256), both families: one launch holds 128 keys, up to 8 key chunks
-
-
-def _wide_attn_supported(k, n=None, ld=None):
-    """The key range of the native head widths; n / ld (bf16 only) as in mfma_attn_supported."""
-    if not 1 <= k <= WIDE_KEYS:
-        return False
-    if n is not None and (n > 0xffff00 or (ld is not None and (ld >= (1 << 24) or n * ld >= 0x7fffffff))):
-        return False
-    return True
+    """Shapes the MFMA attention kernel takes at 64 / 128, over key chunks; n / ld: rows and row pitch of q, v (optional)."""
+    return sparse_attn_form_serves(sparse_attn_form("bf16", dk, True), k, n, ld)
 
 
 def mfma_attn_dk192_supported(k, n=None, ld=None):
-    """Shapes the MFMA attention takes at head width 192 (the README's MAE recipe: D = 768, h = 4), forward -- with or without in-kernel
-    dropout -- and backward (ops.sparse_attn_fwd_mfma / sparse_attn_bwd_mfma): one launch holds 128 keys (Kp 48 + P 40 + V 48 KiB of
-    LDS), up to 8 key chunks.  n / ld as in mfma_attn_supported.  The older predicates keep answering for dk = 64 / 128 only."""
-    return _wide_attn_supported(k, n, ld)
+    """Shapes the MFMA attention takes at head width 192, forward -- with or without in-kernel dropout -- and backward."""
+    return sparse_attn_form_serves(sparse_attn_form("bf16", 192, False), k, n, ld)
 
 
 def mfma_attn_dk256_supported(k, n=None, ld=None):
-    """Shapes the bf16 MFMA attention takes at head width 256 (snf_sparse_attn_fwd_mfma_dk256; the README's SimCLR ResNet-18 recipe:
-    D = 512, h = 2, Lambda = 900), forward: one launch holds 128 keys, up to 8 key chunks.  n / ld as in mfma_attn_supported.
-    mfma_attn_supported() keeps answering for dk = 64 / 128 only.  Training: mfma_attn_dk256_train_supported."""
-    return _wide_attn_supported(k, n, ld)
+    """Shapes the bf16 MFMA attention takes at head width 256, forward.  Training: mfma_attn_dk256_train_supported."""
+    return sparse_attn_form_serves(sparse_attn_form("bf16", 256, False), k, n, ld)
 
 
 def mfma_attn_dk256_train_supported(k, n=None, ld=None):
-    """Shapes the bf16 MFMA attention TRAINS at at head width 256: the forward with in-kernel Philox dropout
-    (sparse_attn_fwd_mfma_dk256(dropout=...), snf_sparse_attn_fwd_mfma_dk256_dropout) and the backward over key chunks of up to 128 keys
-    (sparse_attn_bwd_mfma, snf_sparse_attn_bwd_mfma_chunked) -- the forward's key range, 1 <= k <= 8 x 128.  n / ld as in
-    mfma_attn_supported (the backward addresses rows in 64 bits; the forward sets the limit)."""
-    return _wide_attn_supported(k, n, ld)
+    """Shapes the bf16 MFMA attention TRAINS at at head width 256: the forward with in-kernel dropout, the backward over key chunks."""
+    return sparse_attn_form_trains(sparse_attn_form("bf16", 256, False), k, n, ld)
 
 
-def _sparse_attn_fwd_mfma_wide(dk, q, v, kp, h, scale, need_attn, need_lse, dropout=None):
-    """The bf16 single-bag forward of a native head width (snf_sparse_attn_fwd_mfma_dk<dk>; dropout = (p, seed, offset): its _dropout
-    form, which needs lse or attn)."""
-    me = "sparse_attn_fwd_mfma_dk%d" % dk
-    if q.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
-        raise TypeError("%s: q and v must be bfloat16" % me)
+def mfma_attn_dropout_supported(k, dk):
+    """One key chunk of the in-kernel Philox dropout at 64 / 128 (forward and the one-launch backward)."""
+    return sparse_attn_form_trains(sparse_attn_form("bf16", dk, True), k, one_launch=True)
+
+
+def _attn_fwd_operands(me, family, q, v, kp, f32_too=False):
+    """The operand checks of the sparse attention forwards, single bag and varlen (me: the wrapper named in the errors): q, v of the
+    family's dtype (f32_too: or both f32, which the older bf16 entry point converts) as row-pitch views (_rows16); kp contiguous,
+    f32 -- or bf16 in the bf16 family."""
+    bf16 = family == "bf16"
+    if f32_too:
+        if q.dtype not in (torch.float32, torch.bfloat16) or v.dtype != q.dtype:
+            raise TypeError("%s: q and v must both be float32 or both bfloat16" % me)
+    elif q.dtype != v.dtype or q.dtype != (torch.bfloat16 if bf16 else torch.float32):
+        raise TypeError("%s: q and v must be %s" % (me, "bfloat16" if bf16 else "float32"))
     q = _rows16(q, "q")
     v = _rows16(v, "v")
-    if kp.dtype not in (torch.float32, torch.bfloat16):
+    if bf16 and kp.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError("%s: kp must be float32 or bfloat16" % me)
-    kp = _req(kp, kp.dtype, "kp", 2)
+    return q, v, _req(kp, kp.dtype if bf16 else torch.float32, "kp", 2)
+
+
+def _attn_fwd_outputs(rows, n, k, h, d, need_attn, need_lse, device):
+    """(out [rows, d], attn [h, n, k] or None, lse [h, n] or None), fp32."""
+    return (torch.empty(rows, d, dtype=torch.float32, device=device),
+            torch.empty(h, n, k, dtype=torch.float32, device=device) if need_attn else None,
+            torch.empty(h, n, dtype=torch.float32, device=device) if need_lse else None)
+
+
+def _sparse_attn_fwd_own_width(form, q, v, kp, h, scale, need_attn, need_lse, dropout=None):
+    """The single-bag forward of a record whose C entry points carry the width in their names (dropout = (p, seed, offset): c_dropout,
+    which needs lse or attn).  The two families keep the exception classes they had."""
+    me, dk, bf16 = form.wrapper, form.dk, form.family == "bf16"
+    q, v, kp = _attn_fwd_operands(me, form.family, q, v, kp)
     n, d = q.shape
     k = kp.shape[0]
-    if h < 1 or d != dk * h or kp.shape[1] != d or v.shape != q.shape:
-        raise _ffi.SnuffyHipError("%s: inconsistent shapes q %s v %s kp %s h %d (d_model must be %d h)"
-                                  % (me, tuple(q.shape), tuple(v.shape), tuple(kp.shape), h, dk))
+    error = _ffi.SnuffyHipError if bf16 else ValueError
+    if (bf16 and h < 1) or d != dk * h or kp.shape[1] != d or v.shape != q.shape:
+        raise error("%s: inconsistent shapes q %s v %s kp %s h %d (d_model must be %d h)"
+                    % (me, tuple(q.shape), tuple(v.shape), tuple(kp.shape), h, dk))
     scale = 1.0 / math.sqrt(dk) if scale is None else scale
     lib = _ffi.load()
-    wsb = getattr(lib, "snf_%s_workspace_bytes" % me)(n, k, h)
+    wsb = getattr(lib, form.c_workspace)(n, k, h)
     if wsb == 0:
-        raise _ffi.SnuffyHipError("%s: unsupported shape n=%d k=%d h=%d (1 <= k <= %d)" % (me, n, k, h, WIDE_KEYS))
-    out = torch.empty(k, d, dtype=torch.float32, device=q.device)
-    attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
-    lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
+        raise error("%s: unsupported shape n=%d k=%d h=%d (1 <= k <= %d)" % (me, n, k, h, form.keys * form.chunks))
+    out, attn, lse = _attn_fwd_outputs(k, n, k, h, d, need_attn, need_lse, q.device)
     ws = _ws(wsb, q.device)
-    kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
-    if dropout is not None:
-        pdrop, seed, offset = dropout
-        check(getattr(lib, "snf_%s_dropout" % me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, n, k, h, float(scale), _p(out), _p(attn),
-                                                  _p(lse), _p(ws), wsb, _stream(), float(pdrop), int(seed) & (2 ** 64 - 1),
-                                                  int(offset) & (2 ** 64 - 1)), "snf_%s_dropout" % me)
-        return out, attn, lse
-    check(getattr(lib, "snf_" + me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, n, k, h, float(scale), _p(out), _p(attn), _p(lse),
-                                    _p(ws), wsb, _stream()), "snf_" + me)
+    entry = form.c_fwd if dropout is None else form.c_dropout
+    kdt = (DT_F32 if kp.dtype == torch.float32 else DT_BF16,) if bf16 else ()
+    state = () if dropout is None else (float(dropout[0]), int(dropout[1]) & (2 ** 64 - 1), int(dropout[2]) & (2 ** 64 - 1))
+    check(getattr(lib, entry)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), *kdt, n, k, h, float(scale), _p(out), _p(attn), _p(lse),
+                              _p(ws), wsb, _stream(), *state), entry)
     return out, attn, lse
 
 
@@ -828,13 +915,7 @@ def sparse_attn_fwd_mfma_dk256(q, v, kp, h, scale=None, need_attn=False, need_ls
     views allowed: the halves of a fused [Q | V] projection), kp [k, 256 h] f32 or bf16 (the same bits either way)
     -> (out [k, d] f32, attn [h, n, k] or None, lse [h, n] or None).  dropout = (p, seed, offset): the training form
     (snf_sparse_attn_fwd_mfma_dk256_dropout) -- the Philox mask in registers, attn = P o M, lse that of P; it needs need_lse or need_attn."""
-    return _sparse_attn_fwd_mfma_wide(256, q, v, kp, h, scale, need_attn, need_lse, dropout)
-
-
-def mfma_attn_dropout_supported(k, dk):
-    """One key chunk of the in-kernel Philox dropout (forward and the single-launch MFMA backward); more keys, up to 8 chunks:
-    mfma_attn_train_chunks_supported."""
-    return (dk == 64 and 1 <= k <= 256) or (dk == 128 and 1 <= k <= 224)
+    return _sparse_attn_fwd_own_width(sparse_attn_form("bf16", 256), q, v, kp, h, scale, need_attn, need_lse, dropout)
 
 
 def _rows16(t, name):
@@ -932,14 +1013,23 @@ def sparse_attn_fwd_x3u(q, kp, v, h, scale=None, need_attn=False, need_lse=False
 
 
 def x3_attn_supported(k, dk):
-    """Shapes of the fp32-class (split-bf16 x 3) MFMA attention kernel: 224 (dk = 128) / 256 (dk = 64) keys per launch, up to 8
-    key chunks with exact cross-chunk softmax statistics."""
-    return (dk == 128 and 1 <= k <= 8 * 224) or (dk == 64 and 1 <= k <= 8 * 256)
+    """Shapes of the fp32-class (split-bf16 x 3) MFMA attention kernel at 64 / 128, over key chunks."""
+    return sparse_attn_form_serves(sparse_attn_form("x3", dk, True), k)
 
 
 def x3_attn_dropout_supported(k, dk):
     """The fp32-class kernel applies the training dropout mask itself (one key chunk)."""
-    return (dk == 128 and 1 <= k <= 224) or (dk == 64 and 1 <= k <= 256)
+    return sparse_attn_form_serves(sparse_attn_form("x3", dk, True), k, chunks="dropout_chunks")
+
+
+def x3_attn_dk192_supported(k):
+    """Shapes of the fused fp32-class attention kernel at head width 192 (snf_sparse_attn_fwd_x3_dk192)."""
+    return sparse_attn_form_serves(sparse_attn_form("x3", 192, False), k)
+
+
+def x3_attn_dk256_supported(k):
+    """Shapes of the fused fp32-class attention kernel at head width 256 (snf_sparse_attn_fwd_x3_dk256)."""
+    return sparse_attn_form_serves(sparse_attn_form("x3", 256, False), k)
 
 
 def sparse_attn_fwd_x3(q, v, kp, h, scale=None, need_attn=False, need_lse=False, dropout=None):
@@ -947,11 +1037,7 @@ def sparse_attn_fwd_x3(q, v, kp, h, scale=None, need_attn=False, need_lse=False,
     kp [k, d] f32 -> (out [k, d], attn [h, n, k] or None, lse [h, n] or None).  dropout = (p, seed, offset): the training forward
     (snf_sparse_attn_fwd_x3_dropout, x3_attn_dropout_supported shapes): out = (P o M)^T V with M the mask ops.dropout_mask writes for the
     same (p, seed, offset); attn stays the UNDROPPED P."""
-    if q.dtype != torch.float32 or v.dtype != torch.float32:
-        raise TypeError("sparse_attn_fwd_x3: q and v must be float32")
-    q = _rows16(q, "q")
-    v = _rows16(v, "v")
-    kp = _req(kp, torch.float32, "kp", 2)
+    q, v, kp = _attn_fwd_operands("sparse_attn_fwd_x3", "x3", q, v, kp)
     n, d = q.shape
     k = kp.shape[0]
     if d % h or kp.shape[1] != d or v.shape != q.shape:
@@ -960,59 +1046,17 @@ def sparse_attn_fwd_x3(q, v, kp, h, scale=None, need_attn=False, need_lse=False,
     dk = d // h
     scale = 1.0 / math.sqrt(dk) if scale is None else scale
     lib = _ffi.load()
-    out = torch.empty(k, d, dtype=torch.float32, device=q.device)
-    attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
-    lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
-    wsb = lib.snf_sparse_attn_fwd_x3_workspace_bytes(n, k, h, dk)
+    c_fwd, c_dropout, c_workspace = _X3_C
+    out, attn, lse = _attn_fwd_outputs(k, n, k, h, d, need_attn, need_lse, q.device)
+    wsb = getattr(lib, c_workspace)(n, k, h, dk)
     ws = _ws(wsb, q.device)
     if dropout is not None and dropout[0] > 0.0:
-        check(lib.snf_sparse_attn_fwd_x3_dropout(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), n, k, h, dk, float(scale), float(dropout[0]),
-                                                 int(dropout[1]) & (2 ** 64 - 1), int(dropout[2]) & (2 ** 64 - 1), _p(out), _p(attn), _p(lse), _p(ws), wsb, _stream()),
-              "snf_sparse_attn_fwd_x3_dropout")
+        check(getattr(lib, c_dropout)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), n, k, h, dk, float(scale), float(dropout[0]),
+                                      int(dropout[1]) & (2 ** 64 - 1), int(dropout[2]) & (2 ** 64 - 1), _p(out), _p(attn), _p(lse), _p(ws), wsb,
+                                      _stream()), c_dropout)
         return out, attn, lse
-    check(lib.snf_sparse_attn_fwd_x3(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), n, k, h, dk, float(scale), _p(out), _p(attn),
-                                     _p(lse), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_x3")
-    return out, attn, lse
-
-
-def x3_attn_dk192_supported(k):
-    """Shapes of the fused fp32-class attention kernel at head width 192 (snf_sparse_attn_fwd_x3_dk192; the README's MAE recipe D = 768,
-    h = 4): 128 keys per launch, up to 8 key chunks with exact cross-chunk softmax statistics.  x3_attn_supported() keeps answering for
-    dk = 64 / 128 only."""
-    return _wide_attn_supported(k)
-
-
-def x3_attn_dk256_supported(k):
-    """Shapes of the fused fp32-class attention kernel at head width 256 (snf_sparse_attn_fwd_x3_dk256; the README's SimCLR ResNet-18
-    recipe D = 512, h = 2, Lambda = 900): 128 keys per launch, up to 8 key chunks with exact cross-chunk softmax statistics -- the key
-    range of the unfused pair (x3u_attn_supported).  x3_attn_supported() keeps answering for dk = 64 / 128 only."""
-    return _wide_attn_supported(k)
-
-
-def _sparse_attn_fwd_x3_wide(dk, q, v, kp, h, scale, need_attn, need_lse):
-    """The fp32-class single-bag forward of a native head width (snf_sparse_attn_fwd_x3_dk<dk>)."""
-    me = "sparse_attn_fwd_x3_dk%d" % dk
-    if q.dtype != torch.float32 or v.dtype != torch.float32:
-        raise TypeError("%s: q and v must be float32" % me)
-    q = _rows16(q, "q")
-    v = _rows16(v, "v")
-    kp = _req(kp, torch.float32, "kp", 2)
-    n, d = q.shape
-    k = kp.shape[0]
-    if d != dk * h or kp.shape[1] != d or v.shape != q.shape:
-        raise ValueError("%s: inconsistent shapes q %s v %s kp %s h %d (d_model must be %d h)"
-                         % (me, tuple(q.shape), tuple(v.shape), tuple(kp.shape), h, dk))
-    scale = 1.0 / math.sqrt(dk) if scale is None else scale
-    lib = _ffi.load()
-    wsb = getattr(lib, "snf_%s_workspace_bytes" % me)(n, k, h)
-    if wsb == 0:
-        raise ValueError("%s: unsupported shape n=%d k=%d h=%d (1 <= k <= %d)" % (me, n, k, h, WIDE_KEYS))
-    out = torch.empty(k, d, dtype=torch.float32, device=q.device)
-    attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
-    lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
-    ws = _ws(wsb, q.device)
-    check(getattr(lib, "snf_" + me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), n, k, h, float(scale), _p(out), _p(attn), _p(lse),
-                                    _p(ws), wsb, _stream()), "snf_" + me)
+    check(getattr(lib, c_fwd)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), n, k, h, dk, float(scale), _p(out), _p(attn), _p(lse), _p(ws), wsb,
+                              _stream()), c_fwd)
     return out, attn, lse
 
 
@@ -1020,12 +1064,12 @@ def sparse_attn_fwd_x3_dk192(q, v, kp, h, scale=None, need_attn=False, need_lse=
     """fp32-class sparse attention on the matrix cores at head width 192, fused (snf_sparse_attn_fwd_x3_dk192: no materialised
     [h, n, k] probabilities between the softmax and P^T V): q, v [n, 192 h] f32 (row-strided views allowed: the halves of a fused
     [Q | V] projection), kp [k, 192 h] f32 -> (out [k, d], attn [h, n, k] or None, lse [h, n] or None)."""
-    return _sparse_attn_fwd_x3_wide(192, q, v, kp, h, scale, need_attn, need_lse)
+    return _sparse_attn_fwd_own_width(sparse_attn_form("x3", 192), q, v, kp, h, scale, need_attn, need_lse)
 
 
 def sparse_attn_fwd_x3_dk256(q, v, kp, h, scale=None, need_attn=False, need_lse=False):
     """As sparse_attn_fwd_x3_dk192() at head width 256 (snf_sparse_attn_fwd_x3_dk256): q, v [n, 256 h] f32, kp [k, 256 h] f32."""
-    return _sparse_attn_fwd_x3_wide(256, q, v, kp, h, scale, need_attn, need_lse)
+    return _sparse_attn_fwd_own_width(sparse_attn_form("x3", 256), q, v, kp, h, scale, need_attn, need_lse)
 
 
 _X3_HL_OK = {}
@@ -1181,9 +1225,9 @@ class PackedBags:
         return hit
 
     def plan(self, kind, *shape):
-        """(device table int32, workspace bytes) of a segmented launch: kind in {"mfma", "x3", "head"}; the key-chunked attention
-        plans "mfma_chunks" / "x3_chunks", the head-width-192 plans "mfma_dk192" / "x3_dk192" and the head-width-256 plans "mfma_dk256" /
-        "x3_dk256" (shape = (k, h)) add (chunk count, keys per chunk)."""
+        """(device table int32, workspace bytes) of a segmented launch: kind "head" or a varlen kind of SPARSE_ATTN_FORMS -- "mfma",
+        "x3" (shape = (k, h, dk)); the key-chunked attention plans "mfma_chunks" / "x3_chunks", the head-width-192 plans "mfma_dk192" /
+        "x3_dk192" and the head-width-256 plans "mfma_dk256" / "x3_dk256" (shape = (k, h)) add (chunk count, keys per chunk)."""
         import numpy as np
         key = (kind,) + tuple(shape)
         hit = self._plans.get(key)
@@ -1191,13 +1235,9 @@ class PackedBags:
             return hit
         lib = _ffi.load()
         need, wsb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        names = {"mfma": "snf_sparse_attn_varlen_plan", "x3": "snf_sparse_attn_x3_varlen_plan",
-                 "mfma_chunks": "snf_sparse_attn_varlen_chunked_plan", "x3_chunks": "snf_sparse_attn_x3_varlen_chunked_plan",
-                 "head": "snf_ln_mean_head_varlen_plan"}
-        for dk in (192, 256):
-            names.update({"mfma_dk%d" % dk: "snf_sparse_attn_varlen_dk%d_plan" % dk, "x3_dk%d" % dk: "snf_sparse_attn_x3_varlen_dk%d_plan" % dk})
-        fn = getattr(lib, names[kind])
-        chunks = (ctypes.c_int(0), ctypes.c_int(0)) if kind.endswith(("_chunks", "_dk192", "_dk256")) else ()
+        entry = _VARLEN_PLANS[kind] if kind != "head" else SparseAttnVarlen(kind, "snf_ln_mean_head_varlen_plan", None, False)
+        fn = getattr(lib, entry.c_plan)
+        chunks = (ctypes.c_int(0), ctypes.c_int(0)) if entry.chunk_outputs else ()
         extra = tuple(ctypes.byref(c) for c in chunks)
         check(fn(self._host_ptr(), self.bags, *shape, None, 0, ctypes.byref(need), ctypes.byref(wsb), *extra), "varlen plan (%s)" % kind)
         table = np.zeros(need.value, dtype=np.int32)
@@ -1271,38 +1311,33 @@ def sparse_attn_fwd_ragged(q, v, kp, packed, rag, h, scale=None, need_attn=False
 
 
 def varlen_attn_supported(precision_kind, k, dk):
-    """Single key chunk only: k <= 224 (dk = 128) / 256 (dk = 64); the fp32-class kernel is built for 2, 4, 7 (8) key blocks."""
-    return (dk == 128 and 1 <= k <= 224) or (dk == 64 and 1 <= k <= 256)
+    """The varlen attention at 64 / 128 within one key chunk (snf_sparse_attn_fwd_mfma_varlen / _x3_varlen)."""
+    return sparse_attn_form_serves(sparse_attn_form(precision_kind, dk, True), k, chunks=1)
 
 
 def varlen_attn_chunks_supported(precision_kind, k, dk):
-    """The varlen attention with key chunks (snf_sparse_attn_fwd_mfma_varlen_chunked / _x3_varlen_chunked): up to 8 chunks of 224
-    (dk = 128) / 256 (dk = 64) keys; one chunk is the launch varlen_attn_supported() describes."""
-    return (dk == 128 and 1 <= k <= 8 * 224) or (dk == 64 and 1 <= k <= 8 * 256)
+    """The varlen attention at 64 / 128 with key chunks (the _chunked entry points); one chunk is varlen_attn_supported()'s launch."""
+    return sparse_attn_form_serves(sparse_attn_form(precision_kind, dk, True), k)
 
 
 def varlen_attn_dk192_supported(k):
-    """The bf16 varlen attention at head width 192 (snf_sparse_attn_fwd_mfma_varlen_dk192; the README's MAE recipe D = 768, h = 4): one
-    launch holds 128 keys, up to 8 key chunks.  The older varlen predicates keep answering for dk = 64 / 128 only."""
-    return _wide_attn_supported(k)
+    """The bf16 varlen attention at head width 192 (snf_sparse_attn_fwd_mfma_varlen_dk192)."""
+    return sparse_attn_form_serves(sparse_attn_form("bf16", 192, False), k)
 
 
 def varlen_attn_dk256_supported(k):
-    """The bf16 varlen attention at head width 256 (snf_sparse_attn_fwd_mfma_varlen_dk256; the README's SimCLR ResNet-18 recipe D = 512,
-    h = 2): one launch holds 128 keys, up to 8 key chunks.  The older varlen predicates keep answering for dk = 64 / 128 only."""
-    return _wide_attn_supported(k)
+    """The bf16 varlen attention at head width 256 (snf_sparse_attn_fwd_mfma_varlen_dk256)."""
+    return sparse_attn_form_serves(sparse_attn_form("bf16", 256, False), k)
 
 
 def varlen_attn_x3_dk192_supported(k):
-    """The fp32-class varlen attention at head width 192 (snf_sparse_attn_fwd_x3_varlen_dk192): one launch holds 128 keys, up to 8 key
-    chunks.  The older varlen predicates keep answering for dk = 64 / 128 only."""
-    return _wide_attn_supported(k)
+    """The fp32-class varlen attention at head width 192 (snf_sparse_attn_fwd_x3_varlen_dk192)."""
+    return sparse_attn_form_serves(sparse_attn_form("x3", 192, False), k)
 
 
 def varlen_attn_x3_dk256_supported(k):
-    """The fp32-class varlen attention at head width 256 (snf_sparse_attn_fwd_x3_varlen_dk256): one launch holds 128 keys, up to 8 key
-    chunks.  The older varlen predicates keep answering for dk = 64 / 128 (and 192) only."""
-    return _wide_attn_supported(k)
+    """The fp32-class varlen attention at head width 256 (snf_sparse_attn_fwd_x3_varlen_dk256)."""
+    return sparse_attn_form_serves(sparse_attn_form("x3", 256, False), k)
 
 
 def topk_segmented(scores, packed, k):
@@ -1319,6 +1354,29 @@ def topk_segmented(scores, packed, k):
     return idx
 
 
+def _sparse_attn_fwd_varlen(family, me, q, v, kp, packed, k, h, scale, need_attn, need_lse):
+    """The body of the two varlen wrappers (me: the wrapper named in the errors): plan kind and entry point are those of the record of
+    the family at q's head width -- its one-launch entry where k fits one, else (or with one entry only) its last."""
+    q, v, kp = _attn_fwd_operands(me, family, q, v, kp)
+    t, d = q.shape
+    if t != packed.total or v.shape != q.shape or kp.shape != (packed.bags * k, d) or d % h:
+        raise ValueError("%s: q %s v %s kp %s do not match %d packed rows, %d bags x %d keys"
+                         % (me, tuple(q.shape), tuple(v.shape), tuple(kp.shape), packed.total, packed.bags, k))
+    dk = d // h
+    scale = 1.0 / math.sqrt(dk) if scale is None else scale
+    form = sparse_attn_form(family, dk)
+    shell = form or sparse_attn_form(family, 64)       # a width without a record: the key-chunked entry that takes dk refuses it itself
+    entry = shell.varlen[0 if sparse_attn_form_serves(form, k, chunks=1) else -1]
+    dims = (k, h, dk) if shell.by_dk else (k, h)
+    table, wsb = packed.plan(entry.kind, *dims)[:2]
+    ws = _ws(wsb, q.device)
+    out, attn, lse = _attn_fwd_outputs(packed.bags * k, t, k, h, d, need_attn, need_lse, q.device)
+    kdt = (DT_F32 if kp.dtype == torch.float32 else DT_BF16,) if family == "bf16" else ()
+    check(getattr(_ffi.load(), entry.c_fwd)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), *kdt, packed._host_ptr(), packed.bags, *dims,
+                                            float(scale), _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()), entry.c_fwd)
+    return out, attn, lse
+
+
 def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=False, need_lse=False):
     """bf16-MFMA sparse attention of B packed bags in one launch.  q, v [T, d] bf16 (row-strided views allowed), kp [B * k, d]
     (bag b's keys in rows b k ..) -> (out [B * k, d] f32, attn [h, T, k] or None, lse [h, T] or None).  A bag's result
@@ -1327,37 +1385,7 @@ def sparse_attn_fwd_mfma_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fa
     (varlen_attn_chunks_supported) runs as the key chunks of sparse_attn_fwd_mfma(), with the same guarantees.  Head width 192
     (varlen_attn_dk192_supported) has an entry point of its own, snf_sparse_attn_fwd_mfma_varlen_dk192: 128 keys per chunk; head width
     256 (varlen_attn_dk256_supported) likewise, snf_sparse_attn_fwd_mfma_varlen_dk256, the chunks of sparse_attn_fwd_mfma_dk256()."""
-    if q.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
-        raise TypeError("sparse_attn_fwd_mfma_varlen: q and v must be bfloat16")
-    q = _rows16(q, "q")
-    v = _rows16(v, "v")
-    if kp.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("sparse_attn_fwd_mfma_varlen: kp must be float32 or bfloat16")
-    kp = _req(kp, kp.dtype, "kp", 2)
-    t, d = q.shape
-    if t != packed.total or v.shape != q.shape or kp.shape != (packed.bags * k, d) or d % h:
-        raise ValueError("sparse_attn_fwd_mfma_varlen: q %s v %s kp %s do not match %d packed rows, %d bags x %d keys"
-                         % (tuple(q.shape), tuple(v.shape), tuple(kp.shape), packed.total, packed.bags, k))
-    dk = d // h
-    scale = 1.0 / math.sqrt(dk) if scale is None else scale
-    chunked = not varlen_attn_supported("bf16", k, dk)
-    table, wsb = (packed.plan("mfma_dk%d" % dk, k, h) if dk in (192, 256) else packed.plan("mfma_chunks" if chunked else "mfma", k, h, dk))[:2]
-    ws = _ws(wsb, q.device)
-    out = torch.empty(packed.bags * k, d, dtype=torch.float32, device=q.device)
-    attn = torch.empty(h, t, k, dtype=torch.float32, device=q.device) if need_attn else None
-    lse = torch.empty(h, t, dtype=torch.float32, device=q.device) if need_lse else None
-    kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
-    lib = _ffi.load()
-    if dk in (192, 256):
-        me = "snf_sparse_attn_fwd_mfma_varlen_dk%d" % dk
-        check(getattr(lib, me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(), packed.bags, k, h, float(scale),
-                               _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()), me)
-        return out, attn, lse
-    fn = lib.snf_sparse_attn_fwd_mfma_varlen_chunked if chunked else lib.snf_sparse_attn_fwd_mfma_varlen
-    check(fn(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), kdt, packed._host_ptr(), packed.bags, k, h, dk, float(scale), _p(out),
-             _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()),
-          "snf_sparse_attn_fwd_mfma_varlen_chunked" if chunked else "snf_sparse_attn_fwd_mfma_varlen")
-    return out, attn, lse
+    return _sparse_attn_fwd_varlen("bf16", "sparse_attn_fwd_mfma_varlen", q, v, kp, packed, k, h, scale, need_attn, need_lse)
 
 
 def sparse_attn_fwd_x3_varlen(q, v, kp, packed, k, h, scale=None, need_attn=False, need_lse=False):
@@ -1366,35 +1394,7 @@ def sparse_attn_fwd_x3_varlen(q, v, kp, packed, k, h, scale=None, need_attn=Fals
     (varlen_attn_chunks_supported) runs as the key chunks of sparse_attn_fwd_x3(), with the same guarantees.  Head width 192
     (varlen_attn_x3_dk192_supported) has an entry point of its own, snf_sparse_attn_fwd_x3_varlen_dk192: 128 keys per chunk, the chunks
     of sparse_attn_fwd_x3_dk192(); head width 256 (varlen_attn_x3_dk256_supported) likewise, snf_sparse_attn_fwd_x3_varlen_dk256."""
-    if q.dtype != torch.float32 or v.dtype != torch.float32:
-        raise TypeError("sparse_attn_fwd_x3_varlen: q and v must be float32")
-    q = _rows16(q, "q")
-    v = _rows16(v, "v")
-    kp = _req(kp, torch.float32, "kp", 2)
-    t, d = q.shape
-    if t != packed.total or v.shape != q.shape or kp.shape != (packed.bags * k, d) or d % h:
-        raise ValueError("sparse_attn_fwd_x3_varlen: q %s v %s kp %s do not match %d packed rows, %d bags x %d keys"
-                         % (tuple(q.shape), tuple(v.shape), tuple(kp.shape), packed.total, packed.bags, k))
-    dk = d // h
-    scale = 1.0 / math.sqrt(dk) if scale is None else scale
-    chunked = not varlen_attn_supported("fp32", k, dk)
-    table, wsb = (packed.plan("x3_dk%d" % dk, k, h) if dk in (192, 256)
-                  else packed.plan("x3_chunks" if chunked else "x3", k, h, dk))[:2]
-    ws = _ws(wsb, q.device)
-    out = torch.empty(packed.bags * k, d, dtype=torch.float32, device=q.device)
-    attn = torch.empty(h, t, k, dtype=torch.float32, device=q.device) if need_attn else None
-    lse = torch.empty(h, t, dtype=torch.float32, device=q.device) if need_lse else None
-    lib = _ffi.load()
-    if dk in (192, 256):
-        me = "snf_sparse_attn_fwd_x3_varlen_dk%d" % dk
-        check(getattr(lib, me)(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h, float(scale),
-                               _p(out), _p(attn), _p(lse), _p(table), _p(ws), wsb, _stream()), me)
-        return out, attn, lse
-    fn = lib.snf_sparse_attn_fwd_x3_varlen_chunked if chunked else lib.snf_sparse_attn_fwd_x3_varlen
-    check(fn(_p(q), q.stride(0), _p(v), v.stride(0), _p(kp), packed._host_ptr(), packed.bags, k, h, dk, float(scale), _p(out), _p(attn),
-             _p(lse), _p(table), _p(ws), wsb, _stream()),
-          "snf_sparse_attn_fwd_x3_varlen_chunked" if chunked else "snf_sparse_attn_fwd_x3_varlen")
-    return out, attn, lse
+    return _sparse_attn_fwd_varlen("x3", "sparse_attn_fwd_x3_varlen", q, v, kp, packed, k, h, scale, need_attn, need_lse)
 
 
 def ln_mean_head_varlen(z, packed, gamma, beta, eps, w_head, b_head, add_bf16=None, add_bias=None, slot=None, delta_rows=None):
@@ -1439,14 +1439,8 @@ def dropout_mask(h, n, k, p, seed, offset, device):
 def sparse_attn_fwd_mfma(q, v, kp, n, h, scale=None, need_attn=False, need_lse=False, dropout=None):
     """bf16-MFMA sparse attention.  q, v [n, d] row-major (both f32 or both bf16; row-strided views such as the two halves
     of a fused [n, 2d] projection are taken in place); kp [k, d] f32 or bf16 (f32 is rounded to bf16 by the library, one
-    extra small launch)."""
-    if q.dtype not in (torch.float32, torch.bfloat16) or v.dtype != q.dtype:
-        raise TypeError("sparse_attn_fwd_mfma: q and v must both be float32 or both bfloat16")
-    q = _rows16(q, "q")
-    v = _rows16(v, "v")
-    if kp.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("sparse_attn_fwd_mfma: kp must be float32 or bfloat16")
-    kp = _req(kp, kp.dtype, "kp", 2)
+    extra small launch).  The wrapper of the bf16 records at 64, 128 and 192; dropout = (p, seed, offset): the in-kernel Philox mask."""
+    q, v, kp = _attn_fwd_operands("sparse_attn_fwd_mfma", "bf16", q, v, kp, f32_too=True)
     d = q.shape[1]
     if kp.shape[1] != d:
         raise ValueError("sparse_attn_fwd_mfma: kp %s does not match the width %d of q" % (tuple(kp.shape), d))
@@ -1457,20 +1451,24 @@ def sparse_attn_fwd_mfma(q, v, kp, n, h, scale=None, need_attn=False, need_lse=F
     dk = d // h
     scale = 1.0 / math.sqrt(dk) if scale is None else scale
     lib = _ffi.load()
-    out = torch.empty(k, d, dtype=torch.float32, device=q.device)
-    attn = torch.empty(h, n, k, dtype=torch.float32, device=q.device) if need_attn else None
-    lse = torch.empty(h, n, dtype=torch.float32, device=q.device) if need_lse else None
-    wsb = lib.snf_sparse_attn_fwd_workspace_bytes(n, k, h, dk, 1)
+    c_fwd, c_dropout, c_workspace = _MFMA_C
+    out, attn, lse = _attn_fwd_outputs(k, n, k, h, d, need_attn, need_lse, q.device)
+    wsb = getattr(lib, c_workspace)(n, k, h, dk, 1)
     ws = _ws(wsb, q.device)
     dt = DT_F32 if q.dtype == torch.float32 else DT_BF16
     kdt = DT_F32 if kp.dtype == torch.float32 else DT_BF16
     pdrop, seed, offset = dropout if dropout is not None else (0.0, 0, 0)
-    if pdrop > 0 and not (mfma_attn_train_chunks_supported(k, dk) or (dk == 192 and mfma_attn_dk192_supported(k))):
-        raise ValueError("sparse_attn_fwd_mfma: in-kernel dropout needs at most 8 key chunks (k <= %d at dk = %d), got k = %d"
-                         % (8 * {128: 224, 192: 128}.get(dk, 256), dk, k))
-    check(lib.snf_sparse_attn_fwd_mfma_dropout(_p(q), q.stride(0), _p(v), v.stride(0), dt, _p(kp), kdt, n, k, h, dk, float(scale),
-                                               _p(out), _p(attn), _p(lse), float(pdrop), int(seed) & (2 ** 64 - 1),
-                                               int(offset) & (2 ** 64 - 1), _p(ws), wsb, _stream()), "snf_sparse_attn_fwd_mfma")
+    form = sparse_attn_form("bf16", dk)
+    if form is not None and form.wrapper != "sparse_attn_fwd_mfma":
+        form = None
+    if pdrop > 0 and not sparse_attn_form_serves(form, k, chunks="dropout_chunks"):
+        said = form or sparse_attn_form("bf16", 64)              # a width that is not this wrapper's: the message has always said 64's
+        raise ValueError("sparse_attn_fwd_mfma: in-kernel dropout needs at most %d key chunks (k <= %d at dk = %d), got k = %d"
+                         % (said.dropout_chunks, said.dropout_chunks * said.keys, dk, k))
+    # one entry point serves both: the dropout form at p = 0 is the plain forward, under whose name errors are reported
+    check(getattr(lib, c_dropout)(_p(q), q.stride(0), _p(v), v.stride(0), dt, _p(kp), kdt, n, k, h, dk, float(scale), _p(out), _p(attn),
+                                  _p(lse), float(pdrop), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), _p(ws), wsb, _stream()),
+          c_fwd)
     return out, attn, lse
 
 

@@ -100,8 +100,7 @@ def pack_groups(net, bags):
     sizes = [x.shape[-2] for x in bags]
     uniform_dims = (d % 4 == 0 and (SF.ops.varlen_attn_supported(cfg.compute, k1 + k2, d // h)
                                     or key_chunks_ok(layers, cfg.compute, d, h, k1 + k2, len(bags), sum(sizes))
-                                    or dk192_ok(cfg.compute, d, h, k1 + k2) or x3_dk192_ok(cfg.compute, d, h, k1 + k2)
-                                    or dk256_ok(cfg.compute, d, h, k1 + k2) or x3_dk256_ok(cfg.compute, d, h, k1 + k2))
+                                    or any(_wide_ok(row, cfg.compute, d, h, k1 + k2) for row in _WIDE))
                     and (cfg.compute == "bf16" or SF.FP32_ATTENTION == "x3"))
     on_device = k2 > 0 and device_draws(cfg) and SF.ops.draw_packed_supported(min(max(sizes), 65536), k1, k2, len(layers))
     if k2 > 0 and not on_device:
@@ -124,31 +123,37 @@ def device_draws(cfg):
     return PACK_DEVICE_SAMPLER and cfg.sampler == "device"
 
 
-def _wide_ok(switch, precision, dk, supported, compute, d, h, k):
-    """A native head width packs: its switch is on, the model computes in the kernel's precision, and the key count is the kernel's."""
-    return bool(switch and compute == precision and h >= 1 and d == dk * h and supported(k))
+# The packed switches of the native head widths: (switch, the precision the model computes in, head width).  Each precision has a
+# switch of its own at each width: the bf16 switches leave precision="fp32" per bag and the other way round.
+_WIDE = (("PACK_DK192", "bf16", 192), ("PACK_X3_DK192", "fp32", 192), ("PACK_DK256", "bf16", 256), ("PACK_X3_DK256", "fp32", 256))
+
+
+def _wide_ok(row, compute, d, h, k):
+    """A native head width packs: its switch is on, the model computes in the kernel's precision, and the key count is inside the
+    varlen kernel of the width's record in ops.SPARSE_ATTN_FORMS."""
+    switch, precision, dk = row
+    return bool(globals()[switch] and compute == precision and h >= 1 and d == dk * h
+                and SF.ops.sparse_attn_form_serves(SF.ops.sparse_attn_form(precision, dk), k))
 
 
 def dk192_ok(compute, d, h, k):
-    """PACK_DK192: the bf16 model at head width 192 with a key count inside the dk = 192 varlen kernels.  precision="fp32" stays per
-    bag whatever THIS switch: its packed route at this width is the fused fp32-class kernel behind PACK_X3_DK192 (x3_dk192_ok)."""
-    return _wide_ok(PACK_DK192, "bf16", 192, SF.ops.varlen_attn_dk192_supported, compute, d, h, k)
-
-
-def dk256_ok(compute, d, h, k):
-    """PACK_DK256: the bf16 model at head width 256 with a key count inside the dk = 256 bf16 varlen kernels.  precision="fp32" is not
-    THIS switch's: its packed route at this width is the fused fp32-class kernel behind PACK_X3_DK256 (x3_dk256_ok)."""
-    return _wide_ok(PACK_DK256, "bf16", 256, SF.ops.varlen_attn_dk256_supported, compute, d, h, k)
+    """PACK_DK192: the bf16 model at head width 192."""
+    return _wide_ok(_WIDE[0], compute, d, h, k)
 
 
 def x3_dk192_ok(compute, d, h, k):
-    """PACK_X3_DK192: the fp32 model at head width 192 with a key count inside the fused fp32-class varlen kernel of that width."""
-    return _wide_ok(PACK_X3_DK192, "fp32", 192, SF.ops.varlen_attn_x3_dk192_supported, compute, d, h, k)
+    """PACK_X3_DK192: the fp32 model at head width 192 (the fused fp32-class varlen kernel of that width)."""
+    return _wide_ok(_WIDE[1], compute, d, h, k)
+
+
+def dk256_ok(compute, d, h, k):
+    """PACK_DK256: the bf16 model at head width 256."""
+    return _wide_ok(_WIDE[2], compute, d, h, k)
 
 
 def x3_dk256_ok(compute, d, h, k):
-    """PACK_X3_DK256: the fp32 model at head width 256 with a key count inside the fused fp32-class varlen kernel of that width."""
-    return _wide_ok(PACK_X3_DK256, "fp32", 256, SF.ops.varlen_attn_x3_dk256_supported, compute, d, h, k)
+    """PACK_X3_DK256: the fp32 model at head width 256 (the fused fp32-class varlen kernel of that width)."""
+    return _wide_ok(_WIDE[3], compute, d, h, k)
 
 
 def key_chunks_ok(layers, compute, d, h, k, bags, rows):
