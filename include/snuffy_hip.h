@@ -671,6 +671,29 @@ int snf_tile_preprocess_u8(const void* img_u8, int b, int h, int w, int c, int o
                            const float* std_, float* out_f32, void* cols_bf16, int patch, snf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Training augmentations, batched on the device     replaces the per-crop PIL transforms of DataAugmentationDINO
+ *     (main_dino_adapter.py:674-745) and of the MAE pre-training loader (main_pretrain_adapter.py: RandomResizedCrop + flip)
+ *   tiles_u8 [b, h, w, 3] uint8 (decoded tiles, RGB).  records: n_records 64-byte records (n_records a multiple of b, record r
+ *   crops tile r % b), 16 little-endian words each:
+ *     int32 top, left, ch, cw (crop box), flip, jitter (colour jitter applied), order (jitter operation k in bits 2k .. 2k + 1:
+ *     0 brightness, 1 contrast, 2 saturation, 3 hue), gray; float brightness, contrast, saturation, hue factors, blur (Gaussian
+ *     radius, <= 0: none); int32 solarize, fallback (written by the draw: the centred crop was taken), pad.
+ *   snf_augment_apply_u8: crop -> bicubic resize to size x size -> flip -> jitter -> grayscale -> blur -> solarise, every stage
+ *     uint8 and bit-identical to Pillow, then (u8 / 255 - mean) / std -> out_f32 [n_records, 3, size, size].  mean / std: HOST
+ *     arrays of 3 floats.  workspace: snf_augment_workspace_bytes(h, w, size, n_records) bytes, 16-byte aligned (SNF_EWORKSPACE if
+ *     smaller).  Bounds: size <= 256, h, w <= 1024 and <= 8 * size (every crop then reduces by at most 8: 33 taps); outside:
+ *     SNF_EUNSUPPORTED before any launch.  A record outside the tile is clamped into it, not reported: check tables on the host.
+ *   snf_augment_draw: fills views * b records (record v * b + i = view v of tile i) from Philox4x32-10 (key = state[0], counter =
+ *     (record, block, state[1])); state as for snf_sampler_advance, which the caller runs behind the draw.  policies: HOST array
+ *     of views * 20 doubles: scale lo, hi; p_flip; p_jitter; brightness lo, hi; contrast lo, hi; saturation lo, hi; hue lo, hi;
+ *     p_gray; p_blur; blur radius lo, hi; p_solarize; 3 unused.  views <= 16.  The blocks and words: DESIGN.md 4.
+ * --------------------------------------------------------------------------------------------------------- */
+size_t snf_augment_workspace_bytes(int h, int w, int size, int n_records);
+int snf_augment_draw(const void* state, const double* policies, int views, int b, int h, int w, void* records, snf_stream_t stream);
+int snf_augment_apply_u8(const void* tiles_u8, int b, int h, int w, const void* records, int n_records, int size, const float* mean,
+                         const float* std_, float* out_f32, void* workspace, size_t workspace_bytes, snf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Varlen path: MANY bags in one launch (bags of <= 8 k patches are launch-latency bound).
  *     The reference runs one bag per forward (train.py:468-473 batch_size 1; snuffy.py:130-131 indexes with a 1-D tensor); this
  *     is the same per-bag arithmetic with the bags' rows PACKED into one [T, .] tensor, offsets[bags + 1] = first row of each bag.

@@ -18,7 +18,10 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-
 # (-inf is still honoured: the padded-key masking relies on exp2(-inf) == 0.)
 # The SLP vectoriser is off for the attention kernel: it pairs the running softmax sums into v_pk_add_f32 and then needs
 # three v_mov per four probabilities to re-pair them for the explicit v_pk_mul / v_cvt_pk of the normalisation.
-EXTRA_FLAGS = {"sparse_attn_mfma.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
+# augment.hip restates Pillow's float arithmetic bit for bit: every multiply and add rounds on its own (augment_math.h also says so
+# with a pragma; the flag covers the whole file).
+EXTRA_FLAGS = {"augment.hip": ["-ffp-contract=off"],
+               "sparse_attn_mfma.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
                "sparse_attn_mfma_dk64.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
                "sparse_attn_mfma_dk192.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
                "sparse_attn_mfma_varlen.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],

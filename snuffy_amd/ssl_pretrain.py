@@ -438,7 +438,8 @@ class MultiCropAugment:
     """Stand-in for DataAugmentationDINO (main_dino_adapter.py:674-745) on tile TENSORS [B, 3, H, W] in [0, 1]: 2 global crops
     (scale in global_scale, 224-class size) + n local crops (scale in local_scale, 96-class size), random resized crop + horizontal
     flip, on the device.  The reference's colour jitter / blur / solarisation are torchvision PIL transforms (not available here);
-    the training step is indifferent to where its crops come from."""
+    the training step is indifferent to where its crops come from.  The reference's full recipe on decoded uint8 tiles, bit-identical
+    to Pillow: augment.DINOAugment."""
 
     def __init__(self, global_size=224, local_size=96, local_crops_number=8, global_scale=(0.4, 1.0), local_scale=(0.05, 0.4), generator=None):
         self.gs, self.ls, self.n = global_size, local_size, local_crops_number
@@ -494,10 +495,11 @@ def pretrain_dino(student, teacher, batches, epochs, niter_per_ep, out_dim, ncro
 
 
 def pretrain_mae(model, batches, epochs, niter_per_ep, lr=1.5e-4, min_lr=0.0, warmup_epochs=0, weight_decay=0.05, mask_ratio=0.75,
-                 dist=None, world_size=1, checkpoint_path=None, log=None, tune_adapters_only=True):
+                 dist=None, world_size=1, checkpoint_path=None, log=None, tune_adapters_only=True, augment=None):
     """MAE reconstruction with adapters: per-iteration half-cosine learning rate, AdamW (0.9, 0.95), one flat gradient all-reduce per
     step.  tune_adapters_only: the pre-trained trunk is frozen, adapters train (main_pretrain_adapter.py freezes everything the
-    loaded checkpoint provides).  Writes {'model', 'epoch'} after every epoch (the extractor loads 'model')."""
+    loaded checkpoint provides).  Writes {'model', 'epoch'} after every epoch (the extractor loads 'model').  augment (e.g.
+    augment.MAEAugment on decoded uint8 tiles) is applied to every batch; None: the batches are the images."""
     from .train import FlatGradAllReduce
     if tune_adapters_only:
         for n, p in model.named_parameters():
@@ -510,6 +512,8 @@ def pretrain_mae(model, batches, epochs, niter_per_ep, lr=1.5e-4, min_lr=0.0, wa
     for epoch in range(epochs):
         for i, imgs in zip(range(niter_per_ep), batches(epoch)):
             cur = adjust_learning_rate(lr, min_lr, epoch + i / niter_per_ep, warmup_epochs, epochs)
+            if augment is not None:
+                imgs = augment(imgs)
             losses.append(float(mae_train_step(model, imgs, optimizer, mask_ratio, grad_sync=sync, lr=cur)))
         if log is not None:
             log("epoch %d  loss %.4f" % (epoch, float(np.mean(losses[-niter_per_ep:]))))

@@ -21,12 +21,13 @@ def _triangle(x):
     return 1.0 - x if x < 1.0 else 0.0
 
 
-def resample_coeffs(in_size, out_size):
+def resample_coeffs(in_size, out_size, kernel=_triangle, kernel_support=1.0):
     """(bounds [out, 2] int32 = (first input pixel, count), coefficients [out, ksize] int32, ksize) of Pillow's bilinear
-    resampler with its antialiasing support for in_size -> out_size."""
+    resampler with its antialiasing support for in_size -> out_size.  kernel / kernel_support: another of Pillow's filters
+    (augment.bicubic_coeffs)."""
     scale = in_size / out_size
     filterscale = scale if scale >= 1.0 else 1.0
-    support = 1.0 * filterscale
+    support = kernel_support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((out_size, 2), dtype=np.int32)
     coef = np.zeros((out_size, ksize), dtype=np.int32)
@@ -40,7 +41,7 @@ def resample_coeffs(in_size, out_size):
         if xmax > in_size:
             xmax = in_size
         xmax -= xmin
-        w = [_triangle((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        w = [kernel((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for v in w:
             ww += v
