@@ -655,6 +655,16 @@ int snf_vit_attention_dk32_fwd_lse(const void* qkv, int dtype, int b, int t, int
                                    void* out, float* lse, snf_stream_t stream);
 int snf_vit_attention_dk32_bwd(const void* qkv, const void* dout, const float* lse, int dtype, int b, int t,
                                int h, int dk, float scale, void* dqkv, snf_stream_t stream);
+/* Row passes of the frozen-trunk training route (adapter pre-training in fp32, csrc/vit_train.hip): the erf GELU between the two GEMMs
+ * of a frozen MLP, written as the operand image of the next fp32-class GEMM; the fp32 value exists in registers only.
+ *   snf_gelu_image_f32      pre [m, n] f32 (row pitch ldp) -> the image of gelu(pre) = 0.5 pre (1 + erf(pre / sqrt 2))
+ *   snf_gelu_bwd_image_f32  da [m, n] f32 (row pitch ldda) and pre -> the image of da * gelu'(pre), gelu'(x) = Phi(x) + x phi(x)
+ *   out_dtype SNF_DT_BF16_HL: out_img [m, 2 n] as snf_split_hl_f32 writes it, n % 32 == 0; SNF_DT_BF16_SPLIT3: out_img [m, 3 n] =
+ *   [hi | hi | lo] as snf_split3_f32 writes it, n % 8 == 0.  hi = bf16(v), lo = bf16(v - hi), the same values in both images.
+ *   m >= 1, m * n < 2^33, pitches multiples of 4 floats, every buffer 16-byte aligned, out_img contiguous; else SNF_EINVAL. */
+int snf_gelu_image_f32(const float* pre, int64_t ldp, int64_t m, int n, void* out_img, int out_dtype, snf_stream_t stream);
+int snf_gelu_bwd_image_f32(const float* da, int64_t ldda, const float* pre, int64_t ldp, int64_t m, int n, void* out_img,
+                           int out_dtype, snf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Tile preprocessing for the extractor, batched on the device     replaces the per-tile CPU transforms of

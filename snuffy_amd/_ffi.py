@@ -238,6 +238,8 @@ SIGNATURES = {
     "snf_vit_attention_dk32_fwd_lse": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "snf_vit_attention_dk32_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                            c_void_p]),
+    "snf_gelu_image_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p]),
+    "snf_gelu_bwd_image_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p]),
 }
 
 # The entry points of the native head widths (csrc/attn_width.h): one workspace and one varlen-plan signature for both families, one

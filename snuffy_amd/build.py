@@ -20,7 +20,8 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-
 # three v_mov per four probabilities to re-pair them for the explicit v_pk_mul / v_cvt_pk of the normalisation.
 # augment.hip restates Pillow's float arithmetic bit for bit: every multiply and add rounds on its own (augment_math.h also says so
 # with a pragma; the flag covers the whole file).
-EXTRA_FLAGS = {"augment.hip": ["-ffp-contract=off"],
+# vit_train.hip writes one value as two image formats that have to agree bit for bit: no contraction there either.
+EXTRA_FLAGS = {"augment.hip": ["-ffp-contract=off"], "vit_train.hip": ["-ffp-contract=off"],
                "sparse_attn_mfma.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
                "sparse_attn_mfma_dk64.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
                "sparse_attn_mfma_dk192.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],

@@ -2067,6 +2067,60 @@ def split3_rows(x):
     return out
 
 
+IMAGE_FORMATS = {"hl": (DT_BF16_HL, 32, 2), "cat": (DT_BF16_SPLIT3, 8, 3)}      # fmt -> (out_dtype code, column granule, image columns per column)
+
+
+def _gelu_image_out(who, pre, fmt, out):
+    if fmt not in IMAGE_FORMATS:
+        raise ValueError("%s: fmt must be 'hl' or 'cat', got %r" % (who, fmt))
+    if pre.dtype != torch.float32:
+        raise TypeError("%s: pre must be float32" % who)
+    pre = _rows16(pre, "pre")
+    m, n = pre.shape
+    code, granule, width = IMAGE_FORMATS[fmt]
+    if m < 1 or n < granule or n % granule:
+        raise ValueError("%s: pre is %s; the %s image needs m >= 1 and n %% %d == 0" % (who, tuple(pre.shape), fmt, granule))
+    if out is None:
+        out = torch.empty(m, width * n, dtype=torch.bfloat16, device=pre.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.bfloat16 or out.device != pre.device or tuple(out.shape) != (m, width * n)
+          or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError("%s: out must be a contiguous, 16-byte aligned bfloat16 [%d, %d] tensor on %s" % (who, m, width * n, pre.device))
+    return pre, m, n, code, out
+
+
+def gelu_image(pre, fmt, out=None):
+    """pre [m, n] f32 (row-strided views allowed) -> the split image of erf-GELU(pre), the A operand of the next fp32-class GEMM: fmt "hl"
+    = [m, 2 n] interleaved as split_hl_rows writes it (n % 32 == 0), "cat" = [m, 3 n] = [hi | hi | lo] as split3_rows writes it
+    (n % 8 == 0).  The activation is split in registers and never exists in fp32 in memory (snf_gelu_image_f32)."""
+    pre, m, n, code, out = _gelu_image_out("gelu_image", pre, fmt, out)
+    check(_ffi.load().snf_gelu_image_f32(_p(pre), pre.stride(0), m, n, _p(out), code, _stream()), "snf_gelu_image_f32")
+    return out
+
+
+def gelu_bwd_image(da, pre, fmt, out=None):
+    """da, pre [m, n] f32 (row-strided views allowed) -> the split image (fmt as gelu_image) of da * gelu'(pre), gelu'(x) = Phi(x) + x phi(x):
+    the backward of gelu_image as the operand of the GEMM against the transposed weight (snf_gelu_bwd_image_f32)."""
+    if not isinstance(da, torch.Tensor) or da.dtype != torch.float32:
+        raise TypeError("gelu_bwd_image: da must be float32")
+    da = _rows16(da, "da")
+    pre, m, n, code, out = _gelu_image_out("gelu_bwd_image", pre, fmt, out)
+    if tuple(da.shape) != (m, n):
+        raise ValueError("gelu_bwd_image: da is %s, pre is %s" % (tuple(da.shape), (m, n)))
+    check(_ffi.load().snf_gelu_bwd_image_f32(_p(da), da.stride(0), _p(pre), pre.stride(0), m, n, _p(out), code, _stream()),
+          "snf_gelu_bwd_image_f32")
+    return out
+
+
+def vit_trunk_train_supported(m, n, k):
+    """Whether a projection [m, k] x [n, k]^T has an fp32-class form at all (pure host): the frozen-trunk training route of
+    ssl_pretrain (FUSED_TRUNK) serves exactly the shapes vit.image_format gives an image for -- the one-pass kernel's (hl_eligible) or the
+    concatenated form's (k % 8 == 0 and gemm_x3_supported)."""
+    from . import vit
+    if vit.FP32_GEMM != "x3":
+        return False
+    return bool(hl_eligible(m, n, k) or (k % 8 == 0 and gemm_x3_supported(m, n, k)))
+
+
 def split3_colsum(x, gate=None, out=None, col=0, want_colsum=True):
     """One pass over a gradient matrix x [m, k] f32 (row-strided views allowed): its split image [hi | hi | lo] (operand of the next
     fp32-class GEMM and of the weight-gradient contractions) and its column sums (the bias gradient); gate [m, k] bf16 (row-strided:

@@ -22,8 +22,20 @@ csrc/vit_attn_dk32.hip (dk == 32, T <= 256; switch: FUSED_ATTENTION_DK32).  The 
 asks ops.vit_attention_train_form(t, dk) once and reads the form's switch (FORM_SWITCH); ViTAttentionFn asks once in forward and runs
 the backward of the record it kept.  Other head widths (dk = 16, 96, ...), dk = 32 above
 256 tokens, CPU tensors and a block that needs no gradient stay on the
-composition of torch ops, as do every Linear, LayerNorm and GELU (library GEMMs); the other hand-written inference kernels of the extractor (snuffy_amd/vit.py under torch.no_grad) are not differentiable
-and are not used here.  State-dict keys are the reference's, so a
+composition of torch ops.
+The FROZEN part of the trunk in fp32 (both recipes freeze everything but the adapters and the head / train only the adapters) has a route of
+its own behind FUSED_TRUNK, in the arithmetic of the fp32 extractor (vit.linear_f32: split-bf16 x3 products on ops.gemm_hl / ops.gemm_x3):
+  a Linear with frozen weight and bias     split image -> GEMM with the cached weight image; backward dX = dY W is one GEMM against the
+                                           cached image of W^T (`_image_of_t`), no weight gradient, nothing saved (FrozenLinearFn)
+  frozen norm1 -> qkv                      the LayerNorm kernel writes the operand image; backward GEMM + ops.layernorm_rows_bwd (FrozenNormLinearFn)
+  frozen norm2 -> fc1 -> GELU -> fc2       LayerNorm image, GEMM -> pre (fp32, the one large saved tensor), ops.gelu_image, GEMM; backward: GEMM ->
+                                           da, ops.gelu_bwd_image(da, pre), GEMM, layernorm_rows_bwd (FrozenMlpFn; csrc/vit_train.hip)
+An input that needs no gradient (the teacher, the student's block 0) runs the same kernels without an autograd Function.  The route steps aside,
+silently and bit for bit, for trainable or partly frozen layers (the 64-wide adapters with their dropout, a frozen weight with a trainable bias),
+CPU tensors, torch.autocast (those projections are bf16 library GEMMs), other dtypes, shapes without an fp32-class form
+(ops.vit_trunk_train_supported) and with the switch off: those are torch ops (library GEMMs), as are the DINO head, the patch-embedding
+convolution, the last LayerNorm and the MAE decoder's embedding and prediction layers.  The other hand-written inference kernels of the
+extractor (snuffy_amd/vit.py under torch.no_grad) are not differentiable and are not used here.  State-dict keys are the reference's, so a
 checkpoint written here ('teacher' / 'model') loads into compute_feats exactly like the reference's (compute_feats.py:441-504).
 Several ranks: one process per GPU, gradients of the trainable (adapter + head) parameters averaged with ONE flat all-reduce per
 step (train.FlatGradAllReduce; backend "nccl" = RCCL), the DINO centre with one all-reduce of [1, out_dim].
@@ -36,6 +48,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
+from . import functional as SF
 from . import ops, vit
 
 
@@ -84,18 +97,173 @@ class ViTAttentionFn(torch.autograd.Function):
         return getattr(ops, ctx.form.bwd)(qkv, dout.contiguous(), lse, *ctx.dims), None, None, None, None
 
 
-def _attention(attn, x):
+# The frozen part of the trunk in fp32 on the fp32-class MFMA GEMMs (ops.gemm_hl / ops.gemm_x3, the arithmetic of vit.linear_f32): a Linear
+# whose weight and bias are frozen, a frozen norm2 -> fc1 -> GELU -> fc2, a frozen norm1 -> qkv; the backward to the input is the same
+# GEMM against a cached image of W^T, and no weight gradient exists.  Off, or for trainable layers, CPU tensors, autocast and shapes
+# without a form (ops.vit_trunk_train_supported): the torch ops below, as before.  profiles/vit_trunk_train.txt has the measurements
+# behind the shipped value.
+FUSED_TRUNK = True
+
+
+def _all_frozen(*mods):
+    return all(p is None or not p.requires_grad for m in mods for p in (m.weight, m.bias))
+
+
+def _trunk_route(x, *mods):
+    """The frozen-trunk route serves x through `mods`: the switch, a CUDA fp32 tensor outside autocast, nothing trainable."""
+    return (FUSED_TRUNK and x.device.type == "cuda" and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
+            and _all_frozen(*mods))
+
+
+def _image_format(m, weight, transposed=False):
+    """Image format of weight (or of its transpose: the backward to the input) for m rows; None = no fp32-class form."""
+    w = weight.t() if transposed else weight
+    return vit.image_format(m, w) if ops.vit_trunk_train_supported(m, w.shape[0], w.shape[1]) else None
+
+
+def _image_of_t(weight, fmt):
+    """Split image of W^T [k, n] (the W operand of dX = dY W), cached on the parameter and keyed as vit._image_of keys W's own."""
+    key = SF.param_key(weight)
+    name = "_snf_imgT_" + fmt
+    hit = getattr(weight, name, None)
+    if hit is None or hit[0] != key:
+        wt = weight.detach().t().contiguous()
+        hit = (key, ops.split_hl_weight(wt) if fmt == "hl" else ops.split3_weight(wt))
+        setattr(weight, name, hit)
+    return hit[1]
+
+
+def _gemm(img, fmt, w_img, bias=None):
+    """img [m, .] (format fmt) times the weight image + bias -> [m, n] f32."""
+    bias = None if bias is None else bias.detach()
+    return ops.gemm_hl(img, w_img, bias) if fmt == "hl" else ops.gemm_x3(img, w_img, bias, out_dtype=torch.float32)
+
+
+def _gemm_fwd(img, fmt, lin):
+    return _gemm(img, fmt, vit._image_of(lin.weight, fmt), lin.bias)
+
+
+def _gemm_bwd(dy, fmt, lin, image=False):
+    """dY [m, n] f32 (image: already its split image) -> dX = dY W [m, k] f32."""
+    img = dy if image else vit.split_image(dy.contiguous(), fmt).data
+    return _gemm(img, fmt, _image_of_t(lin.weight, fmt))
+
+
+class FrozenLinearFn(torch.autograd.Function):
+    """x W^T + b of a frozen Linear for an input that needs a gradient; saves no tensor (W is on the module)."""
+
+    @staticmethod
+    def forward(ctx, x2, lin, fmt, fmt_t):
+        ctx.lin, ctx.fmt_t = lin, fmt_t
+        return _gemm_fwd(vit.split_image(x2, fmt).data, fmt, lin)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        return _gemm_bwd(dy, ctx.fmt_t, ctx.lin), None, None, None
+
+
+class FrozenNormLinearFn(torch.autograd.Function):
+    """Linear(LayerNorm(x)), both frozen: the LayerNorm kernel writes the GEMM's operand image; saves x."""
+
+    @staticmethod
+    def forward(ctx, x2, norm, lin, fmt, fmt_t):
+        ctx.save_for_backward(x2)
+        ctx.mods, ctx.fmt_t = (norm, lin), fmt_t
+        return _gemm_fwd(vit.layernorm_image(x2, norm, fmt).data, fmt, lin)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        (x2,), (norm, lin) = ctx.saved_tensors, ctx.mods
+        dn = _gemm_bwd(dy, ctx.fmt_t, lin)
+        return ops.layernorm_rows_bwd(x2, dn, norm.weight, norm.eps, want_param_grads=False)[0], None, None, None, None
+
+
+def _mlp_forward(x2, norm, mlp, fmt1, fmt2):
+    """fc2(GELU(fc1(LayerNorm(x)))): LayerNorm image -> GEMM -> pre [m, 4 D] f32 -> GELU image -> GEMM.  -> (y, pre)"""
+    pre = _gemm_fwd(vit.layernorm_image(x2, norm, fmt1).data, fmt1, mlp.fc1)
+    return _gemm_fwd(ops.gelu_image(pre, fmt2), fmt2, mlp.fc2), pre
+
+
+class FrozenMlpFn(torch.autograd.Function):
+    """norm2 -> fc1 -> GELU -> fc2, all frozen.  Saves x and pre (fc1's output); pre and da are the only fp32 [m, 4 D] tensors written."""
+
+    @staticmethod
+    def forward(ctx, x2, norm, mlp, fmts):
+        y, pre = _mlp_forward(x2, norm, mlp, fmts[0], fmts[1])
+        ctx.save_for_backward(x2, pre)
+        ctx.mods, ctx.fmts = (norm, mlp), fmts
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        (x2, pre), (norm, mlp), (_, _, fmt1_t, fmt2_t) = ctx.saved_tensors, ctx.mods, ctx.fmts
+        da = _gemm_bwd(dy, fmt2_t, mlp.fc2)
+        dn = _gemm_bwd(ops.gelu_bwd_image(da, pre, fmt1_t), fmt1_t, mlp.fc1, image=True)
+        return ops.layernorm_rows_bwd(x2, dn, norm.weight, norm.eps, want_param_grads=False)[0], None, None, None
+
+
+def _rows(x):
+    x2 = x.reshape(-1, x.shape[-1])
+    return x2, torch.is_grad_enabled() and x2.requires_grad
+
+
+def _linear(x, lin):
+    """F.linear(x, lin.weight, lin.bias); a frozen Linear on the frozen-trunk route (no autograd Function when x needs no gradient)."""
+    if _trunk_route(x, lin):
+        x2, need = _rows(x)
+        m = x2.shape[0]
+        fmt, fmt_t = _image_format(m, lin.weight), _image_format(m, lin.weight, True) if need else None
+        if fmt is not None and (fmt_t is not None or not need):
+            y = FrozenLinearFn.apply(x2, lin, fmt, fmt_t) if need else _gemm_fwd(vit.split_image(x2, fmt).data, fmt, lin)
+            return y.view(*x.shape[:-1], -1)
+    return F.linear(x, lin.weight, lin.bias)
+
+
+def _norm_linear(norm, lin, x):
+    """lin(LayerNorm(x)); both frozen: on the frozen-trunk route."""
+    if _trunk_route(x, norm, lin) and norm.weight is not None:
+        x2, need = _rows(x)
+        m = x2.shape[0]
+        fmt, fmt_t = _image_format(m, lin.weight), _image_format(m, lin.weight, True) if need else None
+        if fmt is not None and (fmt_t is not None or not need):
+            x2 = x2.contiguous()
+            y = FrozenNormLinearFn.apply(x2, norm, lin, fmt, fmt_t) if need else _gemm_fwd(vit.layernorm_image(x2, norm, fmt).data, fmt, lin)
+            return y.view(*x.shape[:-1], -1)
+    return _linear(F.layer_norm(x, (x.shape[-1],), norm.weight, norm.bias, norm.eps), lin)
+
+
+def _norm_mlp(norm, mlp, x):
+    """fc2(GELU(fc1(LayerNorm(x)))); all three frozen: on the frozen-trunk route."""
+    if _trunk_route(x, norm, mlp.fc1, mlp.fc2) and norm.weight is not None:
+        x2, need = _rows(x)
+        m = x2.shape[0]
+        fmts = (_image_format(m, mlp.fc1.weight), _image_format(m, mlp.fc2.weight),
+                _image_format(m, mlp.fc1.weight, True) if need else None, _image_format(m, mlp.fc2.weight, True) if need else None)
+        if None not in fmts[:2] and (None not in fmts or not need):
+            x2 = x2.contiguous()
+            y = FrozenMlpFn.apply(x2, norm, mlp, fmts) if need else _mlp_forward(x2, norm, mlp, fmts[0], fmts[1])[0]
+            return y.view(*x.shape[:-1], -1)
+    y = F.layer_norm(x, (x.shape[-1],), norm.weight, norm.bias, norm.eps)
+    return _linear(F.gelu(_linear(y, mlp.fc1)), mlp.fc2)
+
+
+def _attention(attn, x, qkv=None):
+    """Self-attention of the normalised tokens x [b, t, d]; qkv: the qkv projection where the caller already has it."""
     b, t, d = x.shape
     h = attn.num_heads
-    qkv = F.linear(x, attn.qkv.weight, attn.qkv.bias)
+    if qkv is None:
+        qkv = _linear(x, attn.qkv)
     if qkv.is_cuda and qkv.requires_grad and qkv.dtype in (torch.float32, torch.bfloat16):
         form = ops.vit_attention_train_form(t, d // h)
         if form is not None and globals()[FORM_SWITCH[form.name]]:
             o = ViTAttentionFn.apply(qkv.view(b * t, 3 * d), b, t, h, attn.scale)
-            return F.linear(o.view(b, t, d), attn.proj.weight, attn.proj.bias)
+            return _linear(o.view(b, t, d), attn.proj)
     qkv = qkv.view(b, t, 3, h, d // h).permute(2, 0, 3, 1, 4)
     p = ((qkv[0] @ qkv[1].transpose(-2, -1)) * attn.scale).softmax(dim=-1)
-    return F.linear((p @ qkv[2]).transpose(1, 2).reshape(b, t, d), attn.proj.weight, attn.proj.bias)
+    return _linear((p @ qkv[2]).transpose(1, 2).reshape(b, t, d), attn.proj)
 
 
 def _adapter(ad, x, training):
@@ -108,12 +276,9 @@ def _adapter(ad, x, training):
 
 def block_autograd(blk, x, training):
     """x + attn(norm1 x); then x + mlp(norm2 x) + adapter(x)  (drop_path is 0 in every recipe of the reference)."""
-    n1, n2 = blk.norm1, blk.norm2
-    x = x + _attention(blk.attn, F.layer_norm(x, (x.shape[-1],), n1.weight, n1.bias, n1.eps))
+    x = x + _attention(blk.attn, x, _norm_linear(blk.norm1, blk.attn.qkv, x))
     ad = _adapter(blk.adaptmlp, x, training) if hasattr(blk, "adaptmlp") else 0.0
-    y = F.layer_norm(x, (x.shape[-1],), n2.weight, n2.bias, n2.eps)
-    y = F.linear(F.gelu(F.linear(y, blk.mlp.fc1.weight, blk.mlp.fc1.bias)), blk.mlp.fc2.weight, blk.mlp.fc2.bias)
-    return x + y + ad
+    return x + _norm_mlp(blk.norm2, blk.mlp, x) + ad
 
 
 def vit_forward_autograd(model, x):
