@@ -351,9 +351,8 @@ class LinearX3Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        img = ops.split3_rows(x.float() if x.dtype != torch.float32 else x)
-        y = ops.gemm_x3(img, SF.split3_cached(weight), None if bias is None else bias.detach().float().contiguous(),
-                          out_dtype=torch.float32)
+        img = ops.CAT.rows(x.float() if x.dtype != torch.float32 else x)
+        y = ops.CAT.gemm(img, SF.weight_image(weight, ops.CAT), None if bias is None else bias.detach().float().contiguous())
         ctx.save_for_backward(img, weight)
         ctx.has_bias = bias is not None
         return y
@@ -362,10 +361,10 @@ class LinearX3Fn(torch.autograd.Function):
     def backward(ctx, dy):
         img, weight = ctx.saved_tensors
         n_out, k = weight.shape
-        dimg = ops.split3_rows(dy.float().contiguous())
+        dimg = ops.CAT.rows(dy.float().contiguous())
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = ops.gemm_x3(dimg, SF.split3_cached(weight, transposed=True), None, out_dtype=torch.float32)
+            dx = ops.CAT.gemm(dimg, SF.weight_image(weight, ops.CAT, transposed=True))
         if ctx.needs_input_grad[1]:
             # dyh^T xh + dyh^T xl + dyl^T xh over the bag axis: three fp32-output GEMMs on column blocks of the two images, in place
             # (one GEMM over [dyh | dyl]^T [xh | xl] also computes the dropped lo lo block: a quarter more work, measured 682 vs 3 x 170 us)
@@ -638,16 +637,16 @@ def fused_layer0_ok(x2, sel, layer, precision):
     return any(_fused_layer0_admits(adm, layer, x2.shape[0], x2.shape[1], sel.numel()) for adm in _FUSED_LAYER0_ADMISSIONS)
 
 
-def _x3_train_weights(layer, hl=False):
-    """Operands of EncoderLayer0X3Fn, cached on the layer per parameter version: the LayerNorm affines folded into the following
-    projection in fp32 (LN(x) W^T + b = xhat (W * gamma)^T + (W beta + b)) and the split images [Wh | Wl | Wh] (hl: the interleaved
-    images) of the folded Q | V and FFN-in weights, of W2 and of W2^T (the operand of the FFN-out input gradient)."""
+def _x3_train_weights(layer, fmt):
+    """Operands of EncoderLayer0X3Fn, cached on the layer per parameter version and format: the LayerNorm affines folded into the
+    following projection in fp32 (LN(x) W^T + b = xhat (W * gamma)^T + (W beta + b)) and the split images (format fmt) of the folded
+    Q | V and FFN-in weights, of W2 and of W2^T (the operand of the FFN-out input gradient)."""
     n0, n1 = layer.sublayer[0].norm, layer.sublayer[1].norm
     lq, lk, lv, lo = layer.self_attn.linears
     ff = layer.feed_forward
     plist = [n0.weight, n0.bias, n1.weight, n1.bias, lq.weight, lq.bias, lv.weight, lv.bias, ff.w_1.weight, ff.w_1.bias, ff.w_2.weight]
     key = tuple(SF.param_key(p) for p in plist)
-    attr = "_fold3t_hl" if hl else "_fold3t"
+    attr = "_fold3t_hl" if fmt is ops.HL else "_fold3t"
     ent = getattr(layer, attr, None)
     if ent is not None and ent[0] == key:
         return ent[1]
@@ -655,23 +654,20 @@ def _x3_train_weights(layer, hl=False):
         wqv = torch.cat([lq.weight, lv.weight]).float()
         w1 = ff.w_1.weight.float()
         w1f = (w1 * n1.weight).contiguous()
-        out = dict(bqv=(wqv @ n0.bias + torch.cat([lq.bias, lv.bias])).float().contiguous(), w1f=w1f,
-                   b1=(w1 @ n1.bias + ff.w_1.bias).float().contiguous())
-        if hl:
-            w2 = ff.w_2.weight.float()
-            out.update(wqv_hl=ops.split_hl_rows((wqv * n0.weight).contiguous()), w1_hl=ops.split_hl_rows(w1f),
-                       w2_hl=ops.split_hl_rows(w2.contiguous()), w2t_hl=ops.split_hl_rows(w2.t().contiguous()))
+        w2 = ff.w_2.weight.float()
+        if fmt is ops.HL:
+            # an hl image interleaves a weight as it does rows: the split kernel writes these device matrices (the cat weight image
+            # [Wh | Wl | Wh] differs from the row image and has a kernel of its own, which also applies the column scale)
+            wqv_img = fmt.rows((wqv * n0.weight).contiguous())
+            image = fmt.rows
         else:
-            out.update(wqv3=ops.split3_weight(wqv, n0.weight), w1_3=ops.split3_weight(w1f), w2_3=ops.split3_weight(ff.w_2.weight),
-                       w2t_3=ops.split3_weight(ff.w_2.weight.t().contiguous()))
+            wqv_img = fmt.weight(wqv, n0.weight)
+            image = fmt.weight
+        out = dict(bqv=(wqv @ n0.bias + torch.cat([lq.bias, lv.bias])).float().contiguous(), w1f=w1f,
+                   b1=(w1 @ n1.bias + ff.w_1.bias).float().contiguous(),
+                   wqv=wqv_img, w1=image(w1f), w2=image(w2.contiguous()), w2t=image(w2.t().contiguous()))
     setattr(layer, attr, (key, out))
     return out
-
-
-def _hl_planes_sum(img):
-    """fp32 value hi + lo of every element of a (small) hl image [r, 2 k] -> [r, k]."""
-    v = img.view(img.shape[0], -1, 2, 32).float()
-    return (v[:, :, 0] + v[:, :, 1]).reshape(img.shape[0], -1)
 
 
 def _x3_train_hl_ok(n, d, f):
@@ -694,7 +690,7 @@ def _tn3(a3, b3, p, q, chunks=None):
     if ops.gemm_tn_supported(a3.shape[0], p, q, a3, b3):
         # round 6: the contraction on the matrix cores straight from the row-major images (snf_gemm_tn_f32: transposing LDS reads, the
         # three products per staged step, tiles cut into row parts and summed in part order)
-        return ops.gemm_tn(a3, b3, p, q, (p, 2 * p), (q, 2 * q))
+        return ops.CAT.tn(a3, b3, p, q)
     if chunks is None:
         chunks = 4 if p * q >= (1 << 21) else 8
     ah, al = a3[:, p:2 * p], a3[:, 2 * p:]
@@ -720,6 +716,12 @@ def _tn3(a3, b3, p, q, chunks=None):
     return out
 
 
+def _tn(fmt, a_img, b_img, p, q):
+    """a^T b over the bag axis of two images of format fmt -> [p, q] f32.  The hl chain runs inside gemm_tn's domain by construction
+    (_x3_train_hl_ok); the cat chain also serves shapes below it, where _tn3 falls back to library GEMMs."""
+    return _tn3(a_img, b_img, p, q) if fmt is ops.CAT else fmt.tn(a_img, b_img, p, q)
+
+
 class EncoderLayer0X3Fn(torch.autograd.Function):
     """EncoderLayer.forward + backward (snuffy.py:126-157) for the FIRST layer of an fp32 training step in fp32-class arithmetic (every
     large product as split-bf16 x 3 on the matrix cores), as one hand-ordered chain -- the fp32 twin of EncoderLayer0Bf16Fn (round 5).
@@ -739,14 +741,10 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
         h = mha.h
         k = sel.numel()
         eps = layer.sublayer[0].norm.eps
-        hl = _x3_train_hl_ok(n, d, w1.shape[0])
-        fw = _x3_train_weights(layer, hl)
-        if hl:
-            xn3 = ops.layernorm_rows_hl(x2, None, None, eps)                           # xhat = LN_0(x) without its affine, hl image [N, 2D]
-            qv = ops.gemm_hl(xn3, fw["wqv_hl"], fw["bqv"])                             # [N, 2D] f32 = [Q | V]
-        else:
-            xn3 = ops.layernorm_rows_split3(x2, None, None, eps)                      # ... as [hi | hi | lo], [N, 3D]
-            qv = ops.gemm_x3(xn3, fw["wqv3"], fw["bqv"])
+        fmt = ops.HL if _x3_train_hl_ok(n, d, w1.shape[0]) else ops.CAT
+        fw = _x3_train_weights(layer, fmt)
+        xn3 = fmt.layernorm(x2, None, None, eps)                                       # xhat = LN_0(x) without its affine, as its image
+        qv = fmt.gemm(xn3, fw["wqv"], fw["bqv"])                                       # [N, 2D] f32 = [Q | V]
         q, v = qv[:, :d], qv[:, d:]
         xs, _slot = ops.gather_slot_map(x2, sel)
         # the K-row projections in plain fp32 (10 us each, as the generic chain runs them under autograd): the gradient that reaches the
@@ -761,7 +759,7 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
         drop_a = (p_a,) + draw_dropout_state() if p_a > 0.0 else None
         drop_h = (p_h,) + draw_dropout_state() if p_h > 0.0 else None
         drop_z = (p_z,) + draw_dropout_state() if p_z > 0.0 else None
-        if not hl and (drop_a or drop_h or drop_z):
+        if fmt is not ops.HL and (drop_a or drop_h or drop_z):
             raise ops._ffi.SnuffyHipError("EncoderLayer0X3Fn: encoder dropout needs the one-pass (hl) chain; fused_layer0_x3_ok declines this shape")
         layer.last_dropout_states = {"attn": drop, "A": drop_a, "H": drop_h, "Z": drop_z}
         delta = F.linear(o, wo, bo)
@@ -772,25 +770,23 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
         x_sel = xs + delta                                                             # snuffy.py:108 at the K rows
         xhat0_sel = xn3.index_select(0, sel)
         # LayerNorm_1 sees y = x with the K rows replaced: the image is re-normalised at those rows, every other row is shared
-        if hl:
+        if fmt is ops.HL:                                                              # the in-place K-row patch exists for the hl image only
             ops.layernorm_rows_hl_patch_(xn3, sel, x_sel, None, eps=eps)
-            b2 = bb2.detach().float().contiguous()
-            if drop_h is not None:                                                     # mask and 1 / (1 - p) behind the ReLU, before the hi / lo split
-                hid3 = ops.gemm_hl_dropout(xn3, fw["w1_hl"], fw["b1"], drop_h, "relu", hl_out=True)
-            else:
-                hid3 = ops.gemm_hl(xn3, fw["w1_hl"], fw["b1"], "relu", hl_out=True)    # [N, 2F] image
-            if drop_z is not None:                                                     # z = x + M_Z o (hid W2^T + b2): the residual is not masked
-                z = ops.gemm_hl_dropout(hid3, fw["w2_hl"], b2, drop_z, resid=x2)
-            else:
-                z = ops.gemm_hl(hid3, fw["w2_hl"], b2, resid=x2)
         else:
-            xn3.index_copy_(0, sel, ops.split3_rows(ops.layernorm_rows(x_sel, None, None, eps)))
-            hid3 = ops.gemm_x3(xn3, fw["w1_3"], fw["b1"], "relu", split3=True)         # [N, 3F]
-            z = ops.gemm_x3(hid3, fw["w2_3"], bb2.detach().float().contiguous(), resid=x2)  # x + f + b2: the residual rides in the epilogue
+            xn3.index_copy_(0, sel, fmt.rows(ops.layernorm_rows(x_sel, None, None, eps)))
+        b2 = bb2.detach().float().contiguous()
+        if drop_h is not None:                                                         # hl only (checked above): mask and 1 / (1 - p) behind the ReLU, before the hi / lo split
+            hid3 = ops.gemm_hl_dropout(xn3, fw["w1"], fw["b1"], drop_h, "relu", hl_out=True)
+        else:
+            hid3 = fmt.gemm(xn3, fw["w1"], fw["b1"], "relu", image=fmt)                # the hidden layer's image
+        if drop_z is not None:                                                         # hl only: z = x + M_Z o (hid W2^T + b2): the residual is not masked
+            z = ops.gemm_hl_dropout(hid3, fw["w2"], b2, drop_z, resid=x2)
+        else:
+            z = fmt.gemm(hid3, fw["w2"], b2, resid=x2)                                 # x + f + b2: the residual rides in the epilogue
         z.index_add_(0, sel, delta)                                                    # snuffy.py:110,154-155
         ctx.save_for_backward(sel, xhat0_sel, qv, kp, p, mask, o, xs, x_sel, hid3, g0, b0, g1, b1, wq, wv, wo, w1, mask_a)
         ctx.xn3, ctx.fw = xn3, fw       # xn3: written in place after the Q | V projection read it (outside the version check)
-        ctx.h, ctx.eps, ctx.hl = h, eps, hl
+        ctx.h, ctx.eps, ctx.fmt = h, eps, fmt
         ctx.scale_h = 1.0 / (1.0 - p_h) if drop_h is not None else None
         ctx.drop_z = drop_z
         ctx.drop = drop if regen else None
@@ -804,44 +800,32 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
         sel, xhat0_sel, qv, kp, p, mask, o, xs, x_sel, hid3, g0, b0, g1, b1, wq, wv, wo, w1, mask_a = ctx.saved_tensors
         xn3, fw = ctx.xn3, ctx.fw
         d = xs.shape[1]
-        hl = ctx.hl
-        f = hid3.shape[1] // (2 if hl else 3)
+        fmt = ctx.fmt
+        f = hid3.shape[1] // fmt.width
         h, eps = ctx.h, ctx.eps
         dk = d // h
         dz = dz.float().contiguous()
         # ---- FFN: z = y + relu(xhat1 W1'^T + b1') W2^T + b2                                                  (snuffy.py:224-225)
-        if hl:
-            # operand image + bias gradient, one pass (encoder dropout: of df = M_Z o dz, the mask regenerated from its Philox state)
-            dz3, db2 = ops.split_hl_colsum(dz, dropout=ctx.drop_z)
-            dw2 = ops.gemm_tn(dz3, hid3, d, f, hl=True)                                # [D, F]
-            if X3_TRAIN_GATED_GEMM and 2 * f <= 8192:
-                # the ReLU mask (hi values of the output image) in the GEMM's epilogue, which writes the gated gradient as its hl image: no
-                # fp32 dhid, no split pass; the bias gradient is one column-sum pass over the image, the K rows come back out of it
-                dhid3 = ops.gemm_hl_gated(dz3, fw["w2t_hl"], hid3)
-                del dz3
-                db1f = ops.hl_colsum(dhid3)
-                dw1f = ops.gemm_tn(dhid3, xn3, f, d, hl=True)                          # [F, D], gradient of the FOLDED weight
-                dhid_s, gate_s = _hl_planes_sum(dhid3.index_select(0, sel)), None
-                del dhid3
-            else:
-                dhid = ops.gemm_hl(dz3, fw["w2t_hl"])                                  # [N, F] f32, not yet gated
-                del dz3
-                dhid3, db1f = ops.split_hl_colsum(dhid, gate_hl=hid3)
-                dw1f = ops.gemm_tn(dhid3, xn3, f, d, hl=True)
-                del dhid3
-                dhid_s = dhid.index_select(0, sel)
-                gate_s = hid3.index_select(0, sel).view(sel.numel(), f // 32, 2, 32)[:, :, 0].reshape(sel.numel(), f)
-                del dhid
-        else:
-            dz3, db2 = ops.split3_colsum(dz)
-            dw2 = _tn3(dz3, hid3, d, f)
-            dhid = ops.gemm_x3(dz3, fw["w2t_3"])
+        # operand image + bias gradient, one pass (encoder dropout, hl only: of df = M_Z o dz, the mask regenerated from its Philox state)
+        dz3, db2 = fmt.colsum(dz, dropout=ctx.drop_z)
+        dw2 = _tn(fmt, dz3, hid3, d, f)                                                # [D, F]
+        if fmt is ops.HL and X3_TRAIN_GATED_GEMM and 2 * f <= 8192:
+            # hl only (no such kernel reads cat images): the ReLU mask (hi values of the output image) in the GEMM's epilogue, which writes
+            # the gated gradient as its hl image: no fp32 dhid, no split pass; the bias gradient is one column-sum pass over the image, the K
+            # rows come back out of it
+            dhid3 = ops.gemm_hl_gated(dz3, fw["w2t"], hid3)
             del dz3
-            gate = hid3[:, f:2 * f]                                                    # ReLU mask from the hi plane of the output image
-            dhid3, db1f = ops.split3_colsum(dhid, gate=gate)
-            dw1f = _tn3(dhid3, xn3, f, d)
+            db1f = ops.hl_colsum(dhid3)
+            dw1f = _tn(fmt, dhid3, xn3, f, d)                                          # [F, D], gradient of the FOLDED weight
+            dhid_s, gate_s = fmt.decode(dhid3.index_select(0, sel)), None
             del dhid3
-            dhid_s, gate_s = dhid.index_select(0, sel), gate.index_select(0, sel)
+        else:
+            dhid = fmt.gemm(dz3, fw["w2t"])                                            # [N, F] f32, not yet gated
+            del dz3
+            dhid3, db1f = fmt.colsum(dhid, gate=hid3)                                  # gated by the hi values of the output image
+            dw1f = _tn(fmt, dhid3, xn3, f, d)
+            del dhid3
+            dhid_s, gate_s = dhid.index_select(0, sel), fmt.hi(hid3.index_select(0, sel))
             del dhid
         if ctx.scale_h is not None:
             # FFN dropout: the hi plane of the stored (dropped) hid3 is > 0 exactly where the element was kept behind an open ReLU, so the gate
@@ -863,18 +847,11 @@ class EncoderLayer0X3Fn(torch.autograd.Function):
         # xn3 holds LayerNorm 1's rows at S since the forward re-normalised them in place; the Q | V projection saw LayerNorm 0's:
         # dW = dqv^T xn3 + dqv[S]^T (xhat0[S] - xhat1[S]), a K-row correction of the big product
         x1_sel = xn3.index_select(0, sel)
-        if hl:
-            corr = _hl_planes_sum(xhat0_sel) - _hl_planes_sum(x1_sel)
-            dqv3 = torch.empty(xn3.shape[0], 4 * d, dtype=torch.bfloat16, device=dq.device)   # ONE image of [dQ | dV]
-            _, dbq = ops.split_hl_colsum(dq, out=dqv3, col=0)
-            _, dbv = ops.split_hl_colsum(dv, out=dqv3, col=d)
-            dwqvf = ops.gemm_tn(dqv3, xn3, 2 * d, d, hl=True)                          # [2D, D] folded
-        else:
-            corr = (xhat0_sel[:, d:2 * d].float() + xhat0_sel[:, 2 * d:].float()) - (x1_sel[:, d:2 * d].float() + x1_sel[:, 2 * d:].float())
-            dqv3 = torch.empty(xn3.shape[0], 6 * d, dtype=torch.bfloat16, device=dq.device)
-            _, dbq = ops.split3_colsum(dq, out=dqv3, col=0)
-            _, dbv = ops.split3_colsum(dv, out=dqv3, col=d)
-            dwqvf = _tn3(dqv3, xn3, 2 * d, d)
+        corr = fmt.decode(xhat0_sel) - fmt.decode(x1_sel)
+        dqv3 = torch.empty(xn3.shape[0], fmt.width * 2 * d, dtype=torch.bfloat16, device=dq.device)   # ONE image of [dQ | dV]
+        _, dbq = fmt.colsum(dq, out=dqv3, col=0)
+        _, dbv = fmt.colsum(dv, out=dqv3, col=d)
+        dwqvf = _tn(fmt, dqv3, xn3, 2 * d, d)                                          # [2D, D] folded
         del dqv3
         dwqvf += torch.cat([dq.index_select(0, sel), dv.index_select(0, sel)], dim=1).t() @ corr
         dwqf, dwvf = dwqvf[:d], dwqvf[d:]

@@ -168,17 +168,27 @@ def param_key(p):
     return (id(p), p.data_ptr(), p._version, _PARAM_EPOCH[0])
 
 
-def split3_cached(weight, transposed=False):
-    """[Wh | Wl | Wh] image of a parameter (ops.split3_weight) -- or of its transpose -- cached on the parameter until it is
-    written again (optimizer step, load_state_dict)."""
+def _image_attr(fmt, transposed):
+    return "_snf_img%s_%s" % ("T" if transposed else "", fmt.name)
+
+
+def weight_image(weight, fmt, transposed=False):
+    """Split image (fmt: a record of ops.IMAGE_FORMATS or its name) of a parameter [n, ...] taken as [n, k] -- or of its transpose
+    [k, n], the W operand of dX = dY W -- cached on the parameter until it is written again (optimizer step, load_state_dict).
+    drop_param_caches forgets all of them."""
+    fmt = ops.IMAGE_FORMATS.get(fmt, fmt)
     key = param_key(weight)
-    name = "_snf_x3t" if transposed else "_snf_x3"
+    name = _image_attr(fmt, transposed)
     hit = getattr(weight, name, None)
     if hit is None or hit[0] != key:
-        w = weight.detach()
-        hit = (key, ops.split3_weight(w.t().contiguous() if transposed else w))
+        w = weight.detach().reshape(weight.shape[0], -1)
+        hit = (key, fmt.weight(w.t().contiguous() if transposed else w))
         setattr(weight, name, hit)
     return hit[1]
+
+
+def split3_cached(weight, transposed=False):
+    return weight_image(weight, ops.CAT, transposed)
 
 
 def _needs_grad(*tensors):
@@ -597,11 +607,11 @@ def _hl_weights_folded(layer, dkp=None):
     return out
 
 
-_PARAM_CACHES = ("_snf_x3", "_snf_x3t", "_snf_img_hl", "_snf_img_cat")
+_PARAM_CACHES = tuple(_image_attr(fmt, t) for fmt in ops.IMAGE_FORMATS.values() for t in (False, True))
 
 
 def drop_param_caches(module):
-    """Forget the split images cached ON the parameters of `module` (split3_cached here, vit._image_of): they are keyed on
+    """Forget the split images cached ON the parameters of `module` (weight_image): they are keyed on
     (data_ptr, _version), and an edit through `p.data` changes neither -- invalidate() is the documented way to say so."""
     for prm in module.parameters():
         for name in _PARAM_CACHES:
@@ -630,22 +640,22 @@ def _rows_linear(x, lin):
     n = lin.weight.shape[0]
     if FP32_GEMM == "x3" and not _needs_grad(x, lin.weight, lin.bias) and x.dtype == torch.float32 and lin.weight.dtype == torch.float32:
         if m >= 2048 and ops.gemm_x3_supported(m, n, k):
-            return ops.gemm_x3(ops.split3_rows(x), split3_cached(lin.weight), None if lin.bias is None else lin.bias.detach(),
-                               out_dtype=torch.float32)
+            return ops.CAT.gemm(ops.CAT.rows(x), weight_image(lin.weight, ops.CAT), None if lin.bias is None else lin.bias.detach())
         if m < 2048 and ops.linear_rows_x3_supported(m, n, k):
             # the K rows of one bag: skinny kernel, operands split in registers (the fp32 library GEMM took ~10 us per projection)
             return ops.linear_rows_x3(x, lin.weight.detach(), None if lin.bias is None else lin.bias.detach())
     return F.linear(x, lin.weight, lin.bias)
 
 
-def _ffn_out_hl(hid3, w2, b2, x2, deferred_ok):
-    """z = x + W2 hid + b2 on the one-pass kernel -> (z, DeferredK or None).  Where z goes straight to the head (the last layer of an
-    eval forward) and the shape's last round of tiles splits, the split's second K part stays unsummed in its slabs and the head adds it
-    as it reads (ops.gemm_hl_deferred): no slab round trip, no ticket, no workgroup waiting for another inside the GEMM."""
-    if deferred_ok and ops.GEMM_HL_DEFERRED and ops.GEMM_HL_SPLITK \
+def _ffn_out(fmt, hid3, w2, b2, x2, deferred_ok):
+    """z = x + W2 hid + b2, the residual in the GEMM's epilogue -> (z, DeferredK or None).  Where z goes straight to the head (the last
+    layer of an eval forward) and the one-pass kernel's last round of tiles splits for this shape, the split's second K part stays
+    unsummed in its slabs and the head adds it as it reads (ops.gemm_hl_deferred, hl only): no slab round trip, no ticket, no workgroup
+    waiting for another inside the GEMM."""
+    if fmt is ops.HL and deferred_ok and ops.GEMM_HL_DEFERRED and ops.GEMM_HL_SPLITK \
             and ops.gemm_hl_deferred_ws_bytes(hid3.shape[0], w2.shape[0], hid3.shape[1] // 2):
         return ops.gemm_hl_deferred(hid3, w2, b2, resid=x2)
-    return ops.gemm_hl(hid3, w2, b2, resid=x2), None
+    return fmt.gemm(hid3, w2, b2, resid=x2), None
 
 
 def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None, last=False):
@@ -708,10 +718,11 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
         # large bags: the one-pass kernel on interleaved [hi(32) | lo(32)] images (one full-line DMA per operand row and K step,
         # 96 MFMAs per 24 fragment reads); otherwise the concatenated form over [hi | hi | lo]
         hl = d % 32 == 0 and f % 32 == 0 and ops.hl_eligible(n, 2 * dp, d) and ops.hl_eligible(n, f, d) and ops.hl_eligible(n, d, f)
-        fh = _hl_weights(layer, fw) if hl else None
+        fmt = ops.HL if hl else ops.CAT
+        wi = _hl_weights(layer, fw) if hl else fw                                   # the weight images of that format (the biases are fw's)
         shared = hl and shared_norm_layer(layer)
         fhf = _hl_weights_folded(layer, dkp) if shared else None
-        xn3 = _take_xn3(layer, x2, n0, shared)                                      # left by the critic pass, if any
+        xn3 = _take_xn3(layer, x2, n0, shared)                                      # left by the critic pass, if any: an hl image
         fp = _padded_heads(layer, dkp) if dkp != dk else None
         wk, bk = (lk.weight.detach(), None if lk.bias is None else lk.bias.detach()) if fp is None else (fp["wk"], fp["bk"])
         scale = 1.0 / math.sqrt(dk)                                                 # of the TRUE head width (snuffy.py:162)
@@ -731,16 +742,14 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             kp = _rows_linear_padded(xs, wk, bk)
         else:
             kp = _rows_linear(xs, lk)
-        if hl:
+        if shared:                                                                  # hl only: xhat without its affine, folded weights
             if xn3 is None:
-                xn3 = ops.layernorm_rows_hl(x2, None if shared else n0.weight, None if shared else n0.bias, n0.eps)   # snuffy.py:107
-            if shared:
-                qv = ops.gemm_hl(xn3, fhf["wqv"], fhf["bqv"], hl_out=hl_attn)
-            else:
-                qv = ops.gemm_hl(xn3, fh["wqv"], fw["bqv"], hl_out=hl_attn)         # [N, 2D] f32 = [Q | V] (or its [N, 4D] image)
+                xn3 = ops.layernorm_rows_hl(x2, None, None, n0.eps)
+            qv = ops.gemm_hl(xn3, fhf["wqv"], fhf["bqv"], hl_out=hl_attn)
         else:
-            xn3 = ops.layernorm_rows_split3(x2, n0.weight, n0.bias, n0.eps)
-            qv = ops.gemm_x3(xn3, fw["wqv"], fw["bqv"], out_dtype=torch.float32, hl_out=hl_attn)
+            if xn3 is None or not hl:
+                xn3 = fmt.layernorm(x2, n0.weight, n0.bias, n0.eps)                 # snuffy.py:107
+            qv = fmt.gemm(xn3, wi["wqv"], fw["bqv"], image=ops.HL if hl_attn else None)   # [N, 2D] f32 = [Q | V] (or its [N, 4D] hl image)
         if not shared:
             del xn3
         q, v = (None, None) if hl_attn else (qv[:, :dp], qv[:, dp:])
@@ -776,22 +785,13 @@ def encoder_layer(x2, sel, layer, need_attn, precision, packed=None, ragged=None
             ops.layernorm_rows_hl_patch_(xn3, sel, xs, delta, eps=n1.eps)
             hid3 = ops.gemm_hl(xn3, fhf["w1"], fhf["b1"], ff.activation_name, hl_out=True)   # snuffy.py:224-225, [N, 2F] image
             del xn3
-            z, zk = _ffn_out_hl(hid3, fh["w2"], fw["b2"], x2, last and packed is None)   # x + W2 hid + b2: the residual rides in the epilogue
-        elif hl:
-            if x_sel is None:
-                x_sel = xs + delta                                                  # snuffy.py:108
-            yn3 = ops.layernorm_rows_hl(x2, n1.weight, n1.bias, n1.eps, slot=slot, patch_rows=x_sel)   # LN(y), y never built
-            hid3 = ops.gemm_hl(yn3, fh["w1"], fw["b1"], ff.activation_name, hl_out=True)   # snuffy.py:224-225, [N, 2F] image
-            del yn3
-            z, zk = _ffn_out_hl(hid3, fh["w2"], fw["b2"], x2, last and packed is None)   # x + W2 hid + b2: the residual rides in the epilogue
         else:
             if x_sel is None:
                 x_sel = xs + delta                                                  # snuffy.py:108
-            yn3 = ops.layernorm_rows_split3(x2, n1.weight, n1.bias, n1.eps, slot=slot, patch_rows=x_sel)
-            hid3 = ops.gemm_x3(yn3, fw["w1"], fw["b1"], ff.activation_name, split3=True)   # [N, 3F] image
+            yn3 = fmt.layernorm(x2, n1.weight, n1.bias, n1.eps, slot=slot, patch_rows=x_sel)   # LN(y), y never built
+            hid3 = fmt.gemm(yn3, wi["w1"], fw["b1"], ff.activation_name, image=fmt)     # snuffy.py:224-225, the hidden layer's image
             del yn3
-            z = ops.gemm_x3(hid3, fw["w2"], fw["b2"], out_dtype=torch.float32, resid=x2)   # x + W2 hid + b2: the residual rides in the epilogue
-            zk = None
+        z, zk = _ffn_out(fmt, hid3, wi["w2"], fw["b2"], x2, last and packed is None)
         del hid3
         if last:                                                                    # rows S: x -> x_sel (snuffy.py:155), in the head's read
             return Parts(z, slot=slot, delta=delta, deferred=zk), (attn.unsqueeze(0) if attn is not None else None)

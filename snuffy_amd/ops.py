@@ -1794,15 +1794,7 @@ def hl_eligible(m, n, k):
 def split_hl_rows(x):
     """x [m, k] f32 (row-strided views allowed, k % 32 == 0) -> its interleaved split image [m, 2 k] bf16: every 32 columns as
     [hi(32) | lo(32)] (snf_split_hl_f32) -- the A operand of gemm_hl."""
-    if x.dtype != torch.float32:
-        raise TypeError("split_hl_rows: x must be float32")
-    x = _rows16(x, "x")
-    m, k = x.shape
-    if k % 32:
-        raise ValueError("split_hl_rows: k = %d is not a multiple of 32" % k)
-    out = torch.empty(m, 2 * k, dtype=torch.bfloat16, device=x.device)
-    check(_ffi.load().snf_split_hl_f32(_p(x), x.stride(0), m, k, _p(out), _stream()), "snf_split_hl_f32")
-    return out
+    return _split_rows(HL, "split_hl_rows", x)
 
 
 def split_hl_weight(w):
@@ -1816,19 +1808,7 @@ def split_hl_weight(w):
 
 def layernorm_rows_hl(x, gamma, beta, eps=1e-5, slot=None, patch_rows=None):
     """LayerNorm over rows (as layernorm_rows) written as the interleaved split image [n, 2 d] (d % 32 == 0)."""
-    x = _req(x, torch.float32, "x", 2)
-    n, d = x.shape
-    if gamma is not None:
-        gamma = _req(gamma, torch.float32, "gamma", 1)
-    if beta is not None:
-        beta = _req(beta, torch.float32, "beta", 1)
-    if slot is not None:
-        slot = _req(slot, torch.int32, "slot", 1)
-        patch_rows = _req(patch_rows, torch.float32, "patch_rows", 2)
-    out = torch.empty(n, 2 * d, dtype=torch.bfloat16, device=x.device)
-    check(_ffi.load().snf_layernorm_rows_hl_f32(_p(x), n, d, _p(slot), _p(patch_rows), _p(gamma), _p(beta), float(eps), _p(out),
-                                                _stream()), "snf_layernorm_rows_hl_f32")
-    return out
+    return _layernorm_image(HL, x, gamma, beta, eps, slot, patch_rows)
 
 
 def layernorm_rows_hl_patch_(img, rows, x, addend=None, gamma=None, beta=None, eps=1e-5):
@@ -1850,21 +1830,42 @@ def layernorm_rows_hl_patch_(img, rows, x, addend=None, gamma=None, beta=None, e
     return img
 
 
-def gemm_hl(a_hl, w_hl, bias=None, act="none", out_dtype=torch.float32, out=None, hl_out=False, resid=None):
-    """fp32-class act(A W^T + bias) in ONE pass over the interleaved split images a_hl [m, 2 k], w_hl [n, 2 k] (split_hl_rows /
-    layernorm_rows_hl / a previous call with hl_out=True; split_hl_weight): every product hi hi + hi lo + lo hi, fp32 accumulate.
-    Returns [m, n] (out_dtype) or, with hl_out, the hl image [m, 2 n] of the result.  resid [m, n] f32 (fp32 output only) is added
-    after the activation, in the epilogue."""
+def _hl_gemm_operands(who, a_hl, w_hl, bias=None, resid=None, f32_out=True, resid_needs="an fp32 [m, n] tensor and an fp32 output",
+                      shapes=None, splitk=False):
+    """What the one-pass GEMM wrappers share: the two hl images checked and made row-addressable, bias and resid checked, the split-K
+    workspace sized (splitk) -> (a_hl, w_hl, bias, resid, ldr, m, n, k, ws, ws_bytes).  f32_out: the result is a plain fp32 matrix
+    (resid allowed); shapes: the caller's own message for mismatched images."""
     if a_hl.dtype != torch.bfloat16 or w_hl.dtype != torch.bfloat16:
-        raise TypeError("gemm_hl: operands must be bfloat16 hl images")
+        raise TypeError("%s: operands must be bfloat16 hl images" % who)
     a_hl = _rows16(a_hl, "a_hl")
     w_hl = _rows16(w_hl, "w_hl")
     m, k2 = a_hl.shape
     n = w_hl.shape[0]
     if w_hl.shape[1] != k2 or k2 % 64:
-        raise ValueError("gemm_hl: images are %s and %s" % (tuple(a_hl.shape), tuple(w_hl.shape)))
+        raise ValueError("%s: %s" % (who, shapes or "images are %s and %s" % (tuple(a_hl.shape), tuple(w_hl.shape))))
     if bias is not None:
         bias = _req(bias, torch.float32, "bias", 1)
+    ldr = 0
+    if resid is not None:
+        if not f32_out or resid.dtype != torch.float32 or tuple(resid.shape) != (m, n):
+            raise ValueError("%s: resid needs %s" % (who, resid_needs))
+        resid = _rows16(resid, "resid")
+        ldr = resid.stride(0)
+    ws, ws_bytes = None, 0
+    if splitk and GEMM_HL_SPLITK:
+        ws_bytes = int(_ffi.load().snf_gemm_hl_ws_bytes(m, n, k2 // 2))
+        if ws_bytes:
+            ws = _hl_workspace(a_hl.device, ws_bytes)
+    return a_hl, w_hl, bias, resid, ldr, m, n, k2 // 2, ws, ws_bytes
+
+
+def gemm_hl(a_hl, w_hl, bias=None, act="none", out_dtype=torch.float32, out=None, hl_out=False, resid=None):
+    """fp32-class act(A W^T + bias) in ONE pass over the interleaved split images a_hl [m, 2 k], w_hl [n, 2 k] (split_hl_rows /
+    layernorm_rows_hl / a previous call with hl_out=True; split_hl_weight): every product hi hi + hi lo + lo hi, fp32 accumulate.
+    Returns [m, n] (out_dtype) or, with hl_out, the hl image [m, 2 n] of the result.  resid [m, n] f32 (fp32 output only) is added
+    after the activation, in the epilogue."""
+    f32_out = not hl_out and (out_dtype if out is None else out.dtype) == torch.float32
+    a_hl, w_hl, bias, resid, ldr, m, n, k, ws, ws_bytes = _hl_gemm_operands("gemm_hl", a_hl, w_hl, bias, resid, f32_out, splitk=True)
     if hl_out:
         if out is None:
             out = torch.empty(m, 2 * n, dtype=torch.bfloat16, device=a_hl.device)
@@ -1873,20 +1874,8 @@ def gemm_hl(a_hl, w_hl, bias=None, act="none", out_dtype=torch.float32, out=None
         if out is None:
             out = torch.empty(m, n, dtype=out_dtype, device=a_hl.device)
         odt = DT_F32 if out.dtype == torch.float32 else DT_BF16
-    ldr = 0
-    if resid is not None:
-        if hl_out or out.dtype != torch.float32 or resid.dtype != torch.float32 or tuple(resid.shape) != (m, n):
-            raise ValueError("gemm_hl: resid needs an fp32 [m, n] tensor and an fp32 output")
-        resid = _rows16(resid, "resid")
-        ldr = resid.stride(0)
-    lib = _ffi.load()
-    ws, ws_bytes = None, 0
-    if GEMM_HL_SPLITK:
-        ws_bytes = int(lib.snf_gemm_hl_ws_bytes(m, n, k2 // 2))
-        if ws_bytes:
-            ws = _hl_workspace(a_hl.device, ws_bytes)
-    check(lib.snf_gemm_hl_ws_bf16(_p(a_hl), a_hl.stride(0), _p(w_hl), w_hl.stride(0), _p(bias), _p(resid), ldr, m, n, k2 // 2,
-                                  ACT_CODES[act], _p(out), out.stride(0), odt, _p(ws), ws_bytes, _stream()), "snf_gemm_hl_ws_bf16")
+    check(_ffi.load().snf_gemm_hl_ws_bf16(_p(a_hl), a_hl.stride(0), _p(w_hl), w_hl.stride(0), _p(bias), _p(resid), ldr, m, n, k,
+                                          ACT_CODES[act], _p(out), out.stride(0), odt, _p(ws), ws_bytes, _stream()), "snf_gemm_hl_ws_bf16")
     return out
 
 
@@ -1904,50 +1893,32 @@ def gemm_hl_dropout(a_hl, w_hl, bias, dropout, act="none", hl_out=False, resid=N
         raise TypeError("gemm_hl_dropout: operands must be bfloat16 hl images")
     if (act, bool(hl_out)) not in (("relu", True), ("none", False)):
         raise ValueError("gemm_hl_dropout: only relu -> hl image and none -> fp32 (+ resid) exist")
-    a_hl = _rows16(a_hl, "a_hl")
-    w_hl = _rows16(w_hl, "w_hl")
-    m, k2 = a_hl.shape
-    n = w_hl.shape[0]
-    if w_hl.shape[1] != k2 or k2 % 64 or (hl_out and n % 32):
+    a_hl, w_hl, bias, resid, ldr, m, n, k, ws, ws_bytes = _hl_gemm_operands("gemm_hl_dropout", a_hl, w_hl, bias, resid, not hl_out, splitk=True)
+    if hl_out and n % 32:
         raise ValueError("gemm_hl_dropout: images are %s and %s" % (tuple(a_hl.shape), tuple(w_hl.shape)))
-    if bias is not None:
-        bias = _req(bias, torch.float32, "bias", 1)
     if out is None:
         out = torch.empty(m, 2 * n, dtype=torch.bfloat16, device=a_hl.device) if hl_out else \
             torch.empty(m, n, dtype=torch.float32, device=a_hl.device)
-    odt = DT_BF16_HL if hl_out else DT_F32
-    ldr = 0
-    if resid is not None:
-        if hl_out or resid.dtype != torch.float32 or tuple(resid.shape) != (m, n):
-            raise ValueError("gemm_hl_dropout: resid needs an fp32 [m, n] tensor and an fp32 output")
-        resid = _rows16(resid, "resid")
-        ldr = resid.stride(0)
     p, seed, offset = dropout
-    lib = _ffi.load()
-    ws, ws_bytes = None, 0
-    if GEMM_HL_SPLITK:
-        ws_bytes = int(lib.snf_gemm_hl_ws_bytes(m, n, k2 // 2))
-        if ws_bytes:
-            ws = _hl_workspace(a_hl.device, ws_bytes)
-    check(lib.snf_gemm_hl_ws_dropout_bf16(_p(a_hl), a_hl.stride(0), _p(w_hl), w_hl.stride(0), _p(bias), _p(resid), ldr, m, n, k2 // 2,
-                                          ACT_CODES[act], _p(out), out.stride(0), odt, float(p), int(seed) & (2 ** 64 - 1),
-                                          int(offset) & (2 ** 64 - 1), _p(ws), ws_bytes, _stream()), "snf_gemm_hl_ws_dropout_bf16")
+    check(_ffi.load().snf_gemm_hl_ws_dropout_bf16(_p(a_hl), a_hl.stride(0), _p(w_hl), w_hl.stride(0), _p(bias), _p(resid), ldr, m, n, k,
+                                                  ACT_CODES[act], _p(out), out.stride(0), DT_BF16_HL if hl_out else DT_F32, float(p),
+                                                  int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), _p(ws), ws_bytes, _stream()),
+          "snf_gemm_hl_ws_dropout_bf16")
     return out
 
 
 def gemm_hl_gated(a_hl, w_hl, gate_hl):
     """The hl image [m, 2 n] of (A W^T) o [gate > 0] in one pass (snf_gemm_hl_gated_bf16): the FFN input gradient behind its ReLU; gate_hl
     [m, 2 n] = the activation's own hl image (its hi values decide)."""
-    a_hl, w_hl, gate_hl = _rows16(a_hl, "a_hl"), _rows16(w_hl, "w_hl"), _rows16(gate_hl, "gate_hl")
-    if a_hl.dtype != torch.bfloat16 or w_hl.dtype != torch.bfloat16 or gate_hl.dtype != torch.bfloat16:
+    a_hl, w_hl, _, _, _, m, n, k, _, _ = _hl_gemm_operands("gemm_hl_gated", a_hl, w_hl, shapes="inconsistent shapes")
+    gate_hl = _rows16(gate_hl, "gate_hl")
+    if gate_hl.dtype != torch.bfloat16:
         raise TypeError("gemm_hl_gated: operands must be bfloat16 hl images")
-    m, k2 = a_hl.shape
-    n = w_hl.shape[0]
-    if w_hl.shape[1] != k2 or k2 % 64 or n % 32 or tuple(gate_hl.shape) != (m, 2 * n):
+    if n % 32 or tuple(gate_hl.shape) != (m, 2 * n):
         raise ValueError("gemm_hl_gated: inconsistent shapes")
     out = torch.empty(m, 2 * n, dtype=torch.bfloat16, device=a_hl.device)
     check(_ffi.load().snf_gemm_hl_gated_bf16(_p(a_hl), a_hl.stride(0), _p(w_hl), w_hl.stride(0), _p(gate_hl), gate_hl.stride(0), m, n,
-                                             k2 // 2, _p(out), out.stride(0), _stream()), "snf_gemm_hl_gated_bf16")
+                                             k, _p(out), out.stride(0), _stream()), "snf_gemm_hl_gated_bf16")
     return out
 
 
@@ -1990,34 +1961,20 @@ def gemm_hl_deferred(a_hl, w_hl, bias=None, resid=None, workspace=None):
     tensor of its own (caching allocator / graph pool) owned by the DeferredK: it lives until the reader has run, whatever gemm_hl calls
     follow.  workspace (optional): a uint8 tensor of at least gemm_hl_deferred_ws_bytes to use instead; its contents do not matter.
     Shapes whose last round does not split (gemm_hl_deferred_ws_bytes == 0) raise."""
-    if a_hl.dtype != torch.bfloat16 or w_hl.dtype != torch.bfloat16:
-        raise TypeError("gemm_hl_deferred: operands must be bfloat16 hl images")
-    a_hl = _rows16(a_hl, "a_hl")
-    w_hl = _rows16(w_hl, "w_hl")
-    m, k2 = a_hl.shape
-    n = w_hl.shape[0]
-    if w_hl.shape[1] != k2 or k2 % 64:
-        raise ValueError("gemm_hl_deferred: images are %s and %s" % (tuple(a_hl.shape), tuple(w_hl.shape)))
-    if bias is not None:
-        bias = _req(bias, torch.float32, "bias", 1)
-    ldr = 0
-    if resid is not None:
-        if resid.dtype != torch.float32 or tuple(resid.shape) != (m, n):
-            raise ValueError("gemm_hl_deferred: resid needs an fp32 [m, n] tensor")
-        resid = _rows16(resid, "resid")
-        ldr = resid.stride(0)
+    a_hl, w_hl, bias, resid, ldr, m, n, k, _, _ = _hl_gemm_operands("gemm_hl_deferred", a_hl, w_hl, bias, resid,
+                                                                   resid_needs="an fp32 [m, n] tensor")
     lib = _ffi.load()
     off = ctypes.c_size_t(0)
-    ws_bytes = int(lib.snf_gemm_hl_deferred_ws_bytes(m, n, k2 // 2, ctypes.byref(off)))
+    ws_bytes = int(lib.snf_gemm_hl_deferred_ws_bytes(m, n, k, ctypes.byref(off)))
     if not ws_bytes:
-        raise ValueError("gemm_hl_deferred: m=%d n=%d k=%d has no split last round" % (m, n, k2 // 2))
+        raise ValueError("gemm_hl_deferred: m=%d n=%d k=%d has no split last round" % (m, n, k))
     ws = workspace
     if ws is None:
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a_hl.device)
     elif ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_contiguous() or ws.numel() < ws_bytes or ws.device != a_hl.device:
         raise ValueError("gemm_hl_deferred: workspace must be a contiguous uint8 tensor of >= %d bytes on %s" % (ws_bytes, a_hl.device))
     out = torch.empty(m, n, dtype=torch.float32, device=a_hl.device)
-    check(lib.snf_gemm_hl_deferred_f32(_p(a_hl), a_hl.stride(0), _p(w_hl), w_hl.stride(0), _p(bias), _p(resid), ldr, m, n, k2 // 2,
+    check(lib.snf_gemm_hl_deferred_f32(_p(a_hl), a_hl.stride(0), _p(w_hl), w_hl.stride(0), _p(bias), _p(resid), ldr, m, n, k,
                                        ACT_CODES["none"], _p(out), out.stride(0), DT_F32, _p(ws), ws_bytes, _stream()),
           "snf_gemm_hl_deferred_f32")
     tm, tn = (m + 255) // 256, (n + 255) // 256
@@ -2054,32 +2011,185 @@ def split3_weight(w, colscale=None):
 
 def split3_rows(x):
     """x [m, k] f32 (row-strided views allowed) -> [m, 3 k] bf16 = [hi | hi | lo] (snf_split3_f32)."""
-    if x.dtype != torch.float32:
-        raise TypeError("split3_rows: x must be float32")
-    x = _rows16(x, "x")
-    m, k = x.shape
-    if k % 8:
+    return _split_rows(CAT, "split3_rows", x)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The two split-image formats of an fp32 matrix [m, k] (DESIGN.md, "Split images"): everything that depends on the format lives in
+# the two records below; a chain picks one record (by shape) and calls the same method names whichever it got.
+# ----------------------------------------------------------------------------------------------------------------------
+class _HlFormat:
+    """[hi(32) | lo(32)] interleaved per 32 columns, [m, 2 k]: what the one-pass kernel (gemm_hl) reads."""
+    name, code, granule, width = "hl", DT_BF16_HL, 32, 2
+    # the wrappers' bodies: C entries of the row split and the LayerNorm; a wider `out` of colsum comes in whole 64-column groups; its
+    # gate is the activation's own image
+    c_rows, c_layernorm, out_granule, gate_width = "snf_split_hl_f32", "snf_layernorm_rows_hl_f32", 64, 2
+    gate_what = "the bfloat16 hl image of a matrix of the shape of x"
+
+    def rows(self, x):
+        """x [m, k] f32 -> its image."""
+        return split_hl_rows(x)
+
+    def weight(self, w, colscale=None):
+        """W [n, k] f32 (x diag(colscale)) -> the image the GEMM takes as its W operand."""
+        return split_hl_weight(w if colscale is None else w.detach().float() * colscale.detach().float())
+
+    def layernorm(self, x, gamma, beta, eps=1e-5, slot=None, patch_rows=None):
+        """LayerNorm over rows, written as the image."""
+        return layernorm_rows_hl(x, gamma, beta, eps, slot=slot, patch_rows=patch_rows)
+
+    def gemm(self, a_img, w_img, bias=None, act="none", image=None, resid=None):
+        """act(A W^T + bias) (+ resid) -> fp32 [m, n], or (image = a record) the image of the result in that format."""
+        if image is not None and image is not self:
+            raise ValueError("gemm_hl: the one-pass kernel writes fp32 or an hl image, no %s image" % image.name)
+        return gemm_hl(a_img, w_img, bias, act, hl_out=image is not None, resid=resid)
+
+    def colsum(self, x, gate=None, out=None, col=0, want_colsum=True, dropout=None):
+        """One pass over x [m, k] f32 -> (its image, column sums); gate: the image (this format) of the activation whose ReLU gates x."""
+        return split_hl_colsum(x, gate_hl=gate, out=out, col=col, want_colsum=want_colsum, dropout=dropout)
+
+    def tn(self, a_img, b_img, p, q):
+        """a^T b over the rows of two images -> [p, q] f32 (gemm_tn's domain)."""
+        return gemm_tn(a_img, b_img, p, q, hl=True)
+
+    def decode(self, img):
+        """image -> hi + lo in fp32, [m, k] (activation and weight images alike)."""
+        v = img.view(img.shape[0], -1, 2, 32).float()
+        return (v[:, :, 0] + v[:, :, 1]).reshape(img.shape[0], -1)
+
+    def hi(self, img):
+        """The hi plane [m, k] bf16 of an activation image: > 0 where a ReLU behind it is open."""
+        return img.view(img.shape[0], -1, 2, 32)[:, :, 0].reshape(img.shape[0], -1)
+
+    def _colsum_launch(self, lib, x, m, k, gate, ldg, out, col, part, dropout):
+        dst = out if col == 0 else out[:, 2 * col:]
+        if dropout is not None:
+            check(lib.snf_split_hl_colsum_dropout_f32(_p(x), x.stride(0), m, k, _p(gate), ldg, float(dropout[0]), int(dropout[1]) & (2 ** 64 - 1),
+                                                      int(dropout[2]) & (2 ** 64 - 1), _p(dst), out.stride(0), _p(part), _stream()),
+                  "snf_split_hl_colsum_dropout_f32")
+        else:
+            check(lib.snf_split_hl_colsum_f32(_p(x), x.stride(0), m, k, _p(gate), ldg, _p(dst), out.stride(0), _p(part), _stream()),
+                  "snf_split_hl_colsum_f32")
+
+    def _rows_off_granule(self, x):
+        raise ValueError("split_hl_rows: k = %d is not a multiple of 32" % x.shape[1])
+
+
+class _CatFormat:
+    """[hi | hi | lo] for activations, [Wh | Wl | Wh] for weights, [m, 3 k]: what the concatenated-K GEMM (gemm_x3) reads.  The methods
+    are _HlFormat's."""
+    name, code, granule, width = "cat", DT_BF16_SPLIT3, 8, 3
+    # a wider `out` of colsum is three planes; its gate is the hi plane of the activation's image
+    c_rows, c_layernorm, out_granule, gate_width = "snf_split3_f32", "snf_layernorm_rows_split3_f32", 3, 1
+    gate_what = "bfloat16 of the shape of x"
+
+    def rows(self, x):
+        return split3_rows(x)
+
+    def weight(self, w, colscale=None):
+        return split3_weight(w, colscale)
+
+    def layernorm(self, x, gamma, beta, eps=1e-5, slot=None, patch_rows=None):
+        return layernorm_rows_split3(x, gamma, beta, eps, slot=slot, patch_rows=patch_rows)
+
+    def gemm(self, a_img, w_img, bias=None, act="none", image=None, resid=None):
+        return gemm_x3(a_img, w_img, bias, act, split3=image is self, hl_out=image is HL, resid=resid)
+
+    def colsum(self, x, gate=None, out=None, col=0, want_colsum=True, dropout=None):
+        if dropout is not None:
+            raise ValueError("split3_colsum: dropout exists in the hl pass only (split_hl_colsum)")
+        return split3_colsum(x, gate=None if gate is None else self.hi(gate), out=out, col=col, want_colsum=want_colsum)
+
+    def tn(self, a_img, b_img, p, q):
+        return gemm_tn(a_img, b_img, p, q, (p, 2 * p), (q, 2 * q))
+
+    def decode(self, img):
+        k = img.shape[1] // 3
+        return img[:, k:2 * k].float() + img[:, 2 * k:].float()                   # planes 1 + 2: hi + lo of an activation, Wl + Wh of a weight
+
+    def hi(self, img):
+        k = img.shape[1] // 3
+        return img[:, k:2 * k]
+
+    def _colsum_launch(self, lib, x, m, k, gate, ldg, out, col, part, dropout):
+        dst = out if col == 0 else out[:, col:]
+        check(lib.snf_split3_colsum_f32(_p(x), x.stride(0), m, k, _p(gate), ldg, _p(dst), out.stride(0), out.shape[1] // 3, _p(part), _stream()),
+              "snf_split3_colsum_f32")
+
+    def _rows_off_granule(self, x):
         hi = x.to(torch.bfloat16)
         lo = (x - hi.float()).to(torch.bfloat16)
         return torch.cat([hi, hi, lo], dim=1).contiguous()
-    out = torch.empty(m, 3 * k, dtype=torch.bfloat16, device=x.device)
-    check(_ffi.load().snf_split3_f32(_p(x), x.stride(0), m, k, _p(out), _stream()), "snf_split3_f32")
+
+
+HL, CAT = _HlFormat(), _CatFormat()
+IMAGE_FORMATS = {fmt.name: fmt for fmt in (HL, CAT)}
+
+
+def _split_rows(fmt, who, x):
+    if x.dtype != torch.float32:
+        raise TypeError("%s: x must be float32" % who)
+    x = _rows16(x, "x")
+    m, k = x.shape
+    if k % fmt.granule:
+        return fmt._rows_off_granule(x)
+    out = torch.empty(m, fmt.width * k, dtype=torch.bfloat16, device=x.device)
+    check(getattr(_ffi.load(), fmt.c_rows)(_p(x), x.stride(0), m, k, _p(out), _stream()), fmt.c_rows)
     return out
 
 
-IMAGE_FORMATS = {"hl": (DT_BF16_HL, 32, 2), "cat": (DT_BF16_SPLIT3, 8, 3)}      # fmt -> (out_dtype code, column granule, image columns per column)
+def _layernorm_image(fmt, x, gamma, beta, eps, slot, patch_rows):
+    x = _req(x, torch.float32, "x", 2)
+    n, d = x.shape
+    if gamma is not None:
+        gamma = _req(gamma, torch.float32, "gamma", 1)
+    if beta is not None:
+        beta = _req(beta, torch.float32, "beta", 1)
+    if slot is not None:
+        slot = _req(slot, torch.int32, "slot", 1)
+        patch_rows = _req(patch_rows, torch.float32, "patch_rows", 2)
+    out = torch.empty(n, fmt.width * d, dtype=torch.bfloat16, device=x.device)
+    check(getattr(_ffi.load(), fmt.c_layernorm)(_p(x), n, d, _p(slot), _p(patch_rows), _p(gamma), _p(beta), float(eps), _p(out), _stream()),
+          fmt.c_layernorm)
+    return out
+
+
+def _split_colsum(fmt, who, x, gate, out, col, want_colsum, dropout=None):
+    if x.dtype != torch.float32:
+        raise TypeError("%s: x must be float32" % who)
+    x = _rows16(x, "x")
+    m, k = x.shape
+    if k % fmt.granule or k > 8192:
+        raise ValueError("%s: k=%d must be a multiple of %d and <= 8192" % (who, k, fmt.granule))
+    ldg = 0
+    if gate is not None:
+        if gate.dtype != torch.bfloat16 or tuple(gate.shape) != (m, fmt.gate_width * k):
+            raise ValueError("%s: gate must be %s" % (who, fmt.gate_what))
+        gate = _rows16(gate, "gate")
+        ldg = gate.stride(0)
+    if out is None:
+        out = torch.empty(m, fmt.width * k, dtype=torch.bfloat16, device=x.device)
+        col = 0
+    elif (out.dtype != torch.bfloat16 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] != m or out.shape[1] % fmt.out_granule
+          or col % fmt.granule or fmt.width * (col + k) > out.shape[1]):
+        raise ValueError("%s: bad out image" % who)
+    lib = _ffi.load()
+    part = torch.empty(lib.snf_colsum_blocks(m), k, dtype=torch.float32, device=x.device) if want_colsum else None
+    fmt._colsum_launch(lib, x, m, k, gate, ldg, out, col, part, dropout)
+    return out, (part.sum(0) if part is not None else None)
 
 
 def _gelu_image_out(who, pre, fmt, out):
-    if fmt not in IMAGE_FORMATS:
+    fmt = IMAGE_FORMATS.get(fmt, fmt)                                          # a record or its name
+    if fmt is not HL and fmt is not CAT:
         raise ValueError("%s: fmt must be 'hl' or 'cat', got %r" % (who, fmt))
     if pre.dtype != torch.float32:
         raise TypeError("%s: pre must be float32" % who)
     pre = _rows16(pre, "pre")
     m, n = pre.shape
-    code, granule, width = IMAGE_FORMATS[fmt]
+    code, granule, width = fmt.code, fmt.granule, fmt.width
     if m < 1 or n < granule or n % granule:
-        raise ValueError("%s: pre is %s; the %s image needs m >= 1 and n %% %d == 0" % (who, tuple(pre.shape), fmt, granule))
+        raise ValueError("%s: pre is %s; the %s image needs m >= 1 and n %% %d == 0" % (who, tuple(pre.shape), fmt.name, granule))
     if out is None:
         out = torch.empty(m, width * n, dtype=torch.bfloat16, device=pre.device)
     elif (not isinstance(out, torch.Tensor) or out.dtype != torch.bfloat16 or out.device != pre.device or tuple(out.shape) != (m, width * n)
@@ -2127,31 +2237,7 @@ def split3_colsum(x, gate=None, out=None, col=0, want_colsum=True):
     the hi plane of the activation's own split image) zeroes the elements behind a closed ReLU first.  out / col: write into columns
     col .. col + k of each plane of a wider image out [m, 3 w] ([dQ | dV] share one).  Returns (image, colsum [k] or None).  See
     snf_split3_colsum_f32."""
-    if x.dtype != torch.float32:
-        raise TypeError("split3_colsum: x must be float32")
-    x = _rows16(x, "x")
-    m, k = x.shape
-    if k % 8 or k > 8192:
-        raise ValueError("split3_colsum: k=%d must be a multiple of 8 and <= 8192" % k)
-    ldg = 0
-    if gate is not None:
-        if gate.dtype != torch.bfloat16 or tuple(gate.shape) != (m, k):
-            raise ValueError("split3_colsum: gate must be bfloat16 of the shape of x")
-        gate = _rows16(gate, "gate")
-        ldg = gate.stride(0)
-    if out is None:
-        out = torch.empty(m, 3 * k, dtype=torch.bfloat16, device=x.device)
-        col = 0
-    elif (out.dtype != torch.bfloat16 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] != m or out.shape[1] % 3
-          or col % 8 or col + k > out.shape[1] // 3):
-        raise ValueError("split3_colsum: bad out image")
-    plane = out.shape[1] // 3
-    lib = _ffi.load()
-    part = torch.empty(lib.snf_colsum_blocks(m), k, dtype=torch.float32, device=x.device) if want_colsum else None
-    dst = out if col == 0 else out[:, col:]
-    check(lib.snf_split3_colsum_f32(_p(x), x.stride(0), m, k, _p(gate), ldg, _p(dst), out.stride(0), plane, _p(part), _stream()),
-          "snf_split3_colsum_f32")
-    return out, (part.sum(0) if part is not None else None)
+    return _split_colsum(CAT, "split3_colsum", x, gate, out, col, want_colsum)
 
 
 def split_hl_colsum(x, gate_hl=None, out=None, col=0, want_colsum=True, dropout=None):
@@ -2160,35 +2246,7 @@ def split_hl_colsum(x, gate_hl=None, out=None, col=0, want_colsum=True, dropout=
     a wider image out [m, 2 w].  Returns (image, colsum [k] or None).  snf_split_hl_colsum_f32.
     dropout = (p, seed, offset): image and sums of M o x, M = dropout_mask(1, m, k, p, seed, offset) regenerated in the pass
     (snf_split_hl_colsum_dropout_f32)."""
-    if x.dtype != torch.float32:
-        raise TypeError("split_hl_colsum: x must be float32")
-    x = _rows16(x, "x")
-    m, k = x.shape
-    if k % 32 or k > 8192:
-        raise ValueError("split_hl_colsum: k=%d must be a multiple of 32 and <= 8192" % k)
-    ldg = 0
-    if gate_hl is not None:
-        if gate_hl.dtype != torch.bfloat16 or tuple(gate_hl.shape) != (m, 2 * k):
-            raise ValueError("split_hl_colsum: gate must be the bfloat16 hl image of a matrix of the shape of x")
-        gate_hl = _rows16(gate_hl, "gate")
-        ldg = gate_hl.stride(0)
-    if out is None:
-        out = torch.empty(m, 2 * k, dtype=torch.bfloat16, device=x.device)
-        col = 0
-    elif (out.dtype != torch.bfloat16 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] != m or out.shape[1] % 64
-          or col % 32 or 2 * (col + k) > out.shape[1]):
-        raise ValueError("split_hl_colsum: bad out image")
-    lib = _ffi.load()
-    part = torch.empty(lib.snf_colsum_blocks(m), k, dtype=torch.float32, device=x.device) if want_colsum else None
-    dst = out if col == 0 else out[:, 2 * col:]
-    if dropout is not None:
-        check(lib.snf_split_hl_colsum_dropout_f32(_p(x), x.stride(0), m, k, _p(gate_hl), ldg, float(dropout[0]), int(dropout[1]) & (2 ** 64 - 1),
-                                                  int(dropout[2]) & (2 ** 64 - 1), _p(dst), out.stride(0), _p(part), _stream()),
-              "snf_split_hl_colsum_dropout_f32")
-        return out, (part.sum(0) if part is not None else None)
-    check(lib.snf_split_hl_colsum_f32(_p(x), x.stride(0), m, k, _p(gate_hl), ldg, _p(dst), out.stride(0), _p(part), _stream()),
-          "snf_split_hl_colsum_f32")
-    return out, (part.sum(0) if part is not None else None)
+    return _split_colsum(HL, "split_hl_colsum", x, gate_hl, out, col, want_colsum, dropout)
 
 
 def linear_rows_x3_supported(r, c, k):
@@ -2240,19 +2298,7 @@ def gemm_x3_supported(m, n, k):
 
 def layernorm_rows_split3(x, gamma, beta, eps=1e-5, slot=None, patch_rows=None):
     """LayerNorm over rows (as layernorm_rows) written as the split bf16 image [n, 3 d]."""
-    x = _req(x, torch.float32, "x", 2)
-    n, d = x.shape
-    if gamma is not None:
-        gamma = _req(gamma, torch.float32, "gamma", 1)
-    if beta is not None:
-        beta = _req(beta, torch.float32, "beta", 1)
-    if slot is not None:
-        slot = _req(slot, torch.int32, "slot", 1)
-        patch_rows = _req(patch_rows, torch.float32, "patch_rows", 2)
-    out = torch.empty(n, 3 * d, dtype=torch.bfloat16, device=x.device)
-    check(_ffi.load().snf_layernorm_rows_split3_f32(_p(x), n, d, _p(slot), _p(patch_rows), _p(gamma), _p(beta), float(eps),
-                                                    _p(out), _stream()), "snf_layernorm_rows_split3_f32")
-    return out
+    return _layernorm_image(CAT, x, gamma, beta, eps, slot, patch_rows)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

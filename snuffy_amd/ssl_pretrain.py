@@ -122,25 +122,17 @@ def _image_format(m, weight, transposed=False):
 
 
 def _image_of_t(weight, fmt):
-    """Split image of W^T [k, n] (the W operand of dX = dY W), cached on the parameter and keyed as vit._image_of keys W's own."""
-    key = SF.param_key(weight)
-    name = "_snf_imgT_" + fmt
-    hit = getattr(weight, name, None)
-    if hit is None or hit[0] != key:
-        wt = weight.detach().t().contiguous()
-        hit = (key, ops.split_hl_weight(wt) if fmt == "hl" else ops.split3_weight(wt))
-        setattr(weight, name, hit)
-    return hit[1]
+    """Split image of W^T [k, n] (the W operand of dX = dY W), cached on the parameter beside W's own."""
+    return SF.weight_image(weight, fmt, transposed=True)
 
 
 def _gemm(img, fmt, w_img, bias=None):
     """img [m, .] (format fmt) times the weight image + bias -> [m, n] f32."""
-    bias = None if bias is None else bias.detach()
-    return ops.gemm_hl(img, w_img, bias) if fmt == "hl" else ops.gemm_x3(img, w_img, bias, out_dtype=torch.float32)
+    return ops.IMAGE_FORMATS[fmt].gemm(img, w_img, None if bias is None else bias.detach())
 
 
 def _gemm_fwd(img, fmt, lin):
-    return _gemm(img, fmt, vit._image_of(lin.weight, fmt), lin.bias)
+    return _gemm(img, fmt, SF.weight_image(lin.weight, fmt), lin.bias)
 
 
 def _gemm_bwd(dy, fmt, lin, image=False):

@@ -37,38 +37,23 @@ FP32_GEMM = "x3"
 # bf16 path: the blocks with the LayerNorms folded into the consumer GEMMs and the residual adds into the producers' epilogues
 # (VisionTransformer._blocks_fused, round 6); False = the round-2 block (residual_ln passes between the GEMMs)
 BF16_FUSED_BLOCK = True
-
-
-def _image_of(weight, fmt):
-    """Split image of a parameter ("hl": interleaved [hi(32) | lo(32)], ops.split_hl_weight; "cat": [Wh | Wl | Wh],
-    ops.split3_weight), cached on the parameter until it is written again."""
-    key = SF.param_key(weight)
-    name = "_snf_img_" + fmt
-    hit = getattr(weight, name, None)
-    if hit is None or hit[0] != key:
-        w2 = weight.detach().reshape(weight.shape[0], -1)
-        hit = (key, ops.split_hl_weight(w2) if fmt == "hl" else ops.split3_weight(w2))
-        setattr(weight, name, hit)
-    return hit[1]
+# fp32 path: the formats whose GEMM adds a block's residual in its epilogue; a projection on the other adds it in a pass of its own
+RESID_IN_EPILOGUE = ("hl",)
 
 
 class SplitImage:
-    """An fp32 activation held as its bf16 split image: fmt "hl" ([m, 2 k], interleaved) or "cat" ([m, 3 k] = [hi | hi | lo])."""
+    """An fp32 activation [m, k] held as its bf16 split image; fmt: the format's name in ops.IMAGE_FORMATS ("hl" or "cat")."""
 
     def __init__(self, data, fmt, k):
         self.data, self.fmt, self.k = data, fmt, k
 
     def to_f32(self):
-        m = self.data.shape[0]
-        if self.fmt == "hl":
-            v = self.data.view(m, self.k // 32, 2, 32).float()
-            return (v[:, :, 0] + v[:, :, 1]).reshape(m, self.k)
-        return self.data[:, :self.k].float() + self.data[:, 2 * self.k:].float()
+        return ops.IMAGE_FORMATS[self.fmt].decode(self.data)
 
 
 def image_format(m, weight):
-    """Format of the split image a projection with `weight` wants for m rows: "hl" (one-pass kernel) where 256 x 256 tiles fill the
-    chip, "cat" (concatenated K) where only the 32-deep-step kernel applies, None = plain fp32 (library GEMM)."""
+    """Format (its name in ops.IMAGE_FORMATS) of the split image a projection with `weight` wants for m rows: "hl" (one-pass kernel) where
+    256 x 256 tiles fill the chip, "cat" (concatenated K) where only the 32-deep-step kernel applies, None = plain fp32 (library GEMM)."""
     n, k = weight.shape[0], weight[0].numel()
     if FP32_GEMM != "x3":
         return None
@@ -79,15 +64,14 @@ def image_format(m, weight):
 
 def split_image(x, fmt):
     x = x.float() if x.dtype != torch.float32 else x
-    return SplitImage(ops.split_hl_rows(x) if fmt == "hl" else ops.split3_rows(x), fmt, x.shape[1])
+    return SplitImage(ops.IMAGE_FORMATS[fmt].rows(x), fmt, x.shape[1])
 
 
 def layernorm_image(x2, norm, fmt):
     """LayerNorm(x2) as the image a following projection wants (written by the LayerNorm kernel itself), or plain fp32."""
-    if fmt == "hl" and x2.shape[1] % 32 == 0:
-        return SplitImage(ops.layernorm_rows_hl(x2, norm.weight, norm.bias, norm.eps), "hl", x2.shape[1])
-    if fmt == "cat":
-        return SplitImage(ops.layernorm_rows_split3(x2, norm.weight, norm.bias, norm.eps), "cat", x2.shape[1])
+    rec = ops.IMAGE_FORMATS.get(fmt)
+    if rec is not None and x2.shape[1] % rec.granule == 0:
+        return SplitImage(rec.layernorm(x2, norm.weight, norm.bias, norm.eps), fmt, x2.shape[1])
     y = ops.layernorm_rows(x2, norm.weight, norm.bias, norm.eps)
     return split_image(y, fmt) if fmt else y
 
@@ -96,16 +80,17 @@ def linear_f32(x, weight, bias, act="none", image_for=None, resid=None, scale=No
     """act(x W^T + b) of the fp32 path.  x: [m, k] f32 or a SplitImage.  FP32_GEMM == "x3": split-bf16 x3 products on the hand-written
     MFMA GEMMs -- the one-pass kernel on interleaved images where the shape fills the chip, the concatenated form otherwise -- else
     (or for shapes outside both kernels' domains) the fp32 library GEMM + the activation kernel.  image_for = the weight of the
-    NEXT projection: the result is returned as the split image that projection wants, straight from this GEMM's epilogue (it never
-    exists in fp32).  resid [m, n] f32 (fp32 results only): added to the result -- in the one-pass kernel's epilogue, so a block's
-    residual adds cost no pass of their own (round 6).  scale: the result is scale * (x W^T + b) (the adapter's scalar; act "none")."""
+    NEXT projection: the result is returned as the split image that projection wants, straight from this GEMM's epilogue where the
+    kernel writes that format and no residual is due (it never exists in fp32 then).  resid [m, n] f32: added to the result -- in the
+    one-pass kernel's epilogue where that writes fp32, so a block's residual adds cost no pass of their own (round 6).  scale: the
+    result is scale * (x W^T + b) (the adapter's scalar; act "none")."""
     m = x.data.shape[0] if isinstance(x, SplitImage) else x.shape[0]
     n = weight.shape[0]
     if scale is not None:
         weight, bias = _scaled(weight, bias, float(scale))
     fmt = image_format(m, weight)
     out_fmt = image_format(m, image_for) if image_for is not None else None
-    if out_fmt == "hl" and n % 32:
+    if out_fmt is not None and n % ops.IMAGE_FORMATS[out_fmt].granule:           # n % 32 != 0 has no hl image
         out_fmt = "cat"
     b = None if bias is None else bias.detach().float().contiguous()
     if fmt is not None:
@@ -113,19 +98,14 @@ def linear_f32(x, weight, bias, act="none", image_for=None, resid=None, scale=No
             x = split_image(x, fmt)
         elif x.fmt != fmt:
             x = split_image(x.to_f32(), fmt)
-        w_img = _image_of(weight, fmt)
-        if fmt == "hl":
-            if out_fmt == "hl":
-                return SplitImage(ops.gemm_hl(x.data, w_img, b, act, hl_out=True), "hl", n)
-            y = ops.gemm_hl(x.data, w_img, b, act, resid=resid if out_fmt is None else None)
-            if resid is not None and out_fmt is not None:
-                y = y + resid
-        else:
-            if out_fmt == "cat" and resid is None:
-                return SplitImage(ops.gemm_x3(x.data, w_img, b, act, split3=True), "cat", n)
-            y = ops.gemm_x3(x.data, w_img, b, act, out_dtype=torch.float32)
-            if resid is not None:
-                y += resid
+        w_img = SF.weight_image(weight, fmt)
+        rec = ops.IMAGE_FORMATS[fmt]
+        if out_fmt == fmt and resid is None:
+            return SplitImage(rec.gemm(x.data, w_img, b, act, image=rec), fmt, n)
+        rides = resid is not None and out_fmt is None and fmt in RESID_IN_EPILOGUE
+        y = rec.gemm(x.data, w_img, b, act, resid=resid if rides else None)
+        if resid is not None and not rides:
+            y += resid
         return split_image(y, out_fmt) if out_fmt else y
     if isinstance(x, SplitImage):
         x = x.to_f32()

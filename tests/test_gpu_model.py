@@ -414,7 +414,7 @@ def test_module_stays_picklable_and_copyable_after_forwards():
 
 
 def test_invalidate_after_data_edit_drops_split_weight_caches():
-    """the split-weight images cached on the parameters (_snf_x3 / _snf_x3t, keyed on data_ptr and _version) survive an
+    """the split-weight images cached on the parameters (_snf_img_cat / _snf_imgT_cat, keyed on data_ptr and _version) survive an
     edit through `.data`; MILNet.invalidate() is the documented remedy and must drop them: the forward after edit + invalidate
     equals the forward of a freshly built net with the edited weights."""
     from snuffy_amd import functional as SF
@@ -425,12 +425,12 @@ def test_invalidate_after_data_edit_drops_split_weight_caches():
         net(x)                                             # populates every cache derived from the weights
         lk = net.b_classifier.encoder.layers[0].self_attn.linears[1]
         SF.split3_cached(lk.weight)                        # the training-path cache on the parameter itself
-        assert hasattr(lk.weight, "_snf_x3")
+        assert hasattr(lk.weight, "_snf_img_cat")
         for p_ in net.parameters():
             if p_.dim() > 1:
                 p_.data.mul_(1.25)                         # an EMA-style edit: same storage, same version counter
         net.invalidate()
-        assert not hasattr(lk.weight, "_snf_x3")
+        assert not hasattr(lk.weight, "_snf_img_cat")
         _, logits, _ = net(x)
         fresh = synth_state(D, h, 1).to(DEV).eval().configure(precision="fp32")
         fresh.load_state_dict(net.state_dict())
